@@ -8,7 +8,13 @@ protocol requires, include/dsp_dynamic.h:429-438) over one frame of a synthetic 
 stream (dsp-map_amd/scene.py).  Clouds are generated and resident in HBM before the timed region;
 the D2H readout of the result grid is not part of update() and is not timed.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload B|C|C_sat|E]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload B|C|C_sat|E] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else the line
+can carry: the stage-profiled repeat of the timed frames and the roofline built on it, the extra workloads of the
+default line (saturated, realistic, rollout, variants, host, node, preprocess, origin, projection) and the CPU baseline.
+--dump-outputs DIR writes what the last timed step left in the map (voxel results grid, device counters) as .npy files;
+the depth stream is generated deterministically, so the same arguments feed the same clouds from run to run.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): see DESIGN.md "multi-GPU".
 Prints ONE JSON line on rank 0.
@@ -47,6 +53,7 @@ WORKLOADS = {
 }
 REC = 32  # bytes of one live particle record in SURVEY 8(d)'s accounting
 COUNTER_KEYS = ("n_live_in", "n_fov", "n_born", "n_obs", "n_moved", "n_out_of_map", "n_voxel_full", "n_pyramid_full", "n_live_out")
+DUMP_GRID_BYTES = 48 << 20   # --dump-outputs: the results grid of one map in full up to this size, a seeded sample of its rows above
 
 
 def csrc_fingerprint():
@@ -277,10 +284,13 @@ def main():
     ap.add_argument("--workload", default=None)
     ap.add_argument("--prefill", type=int, default=300, help="untimed frames before warmup (steady state: the live count of workload B levels off after ~8 s of stream)")
     ap.add_argument("--estimator", type=int, default=2, help="velocity estimator of the realistic workloads: 0 static tags, 1 host stage, 2 device (default)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the saturated extra measurements")
-    ap.add_argument("--only", default="", help="comma list: run only these extra blocks of the default line (saturated, realistic, rollout, variants, "
-                                              "host, node, preprocess, origin, projection); the contract measurement always runs")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps: stage profiling + roofline, the extra blocks and the CPU "
+                                                         "baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the saturated extra measurements")
+    ap.add_argument("--only", default="", help="with --full, comma list: run only these extra blocks of the default line (saturated, realistic, "
+                                              "rollout, variants, host, node, preprocess, origin, projection); the contract measurement always runs")
     args = ap.parse_args()
 
     import numpy as np
@@ -331,11 +341,18 @@ def main():
         sc = scene_mod.CorridorScene(w["nx"] * w["res"], w["ny"] * w["res"], w["nz"] * w["res"], seed=seed,
                                      device=dev, scale=1.0 if w["res"] >= 0.15 else 1.33)
         out = []
-        for f in range(n):
-            t = t0 + f / 30.0
-            pts, pos, quat = sc.frame(t)
-            out.append((pts, pos, quat, t))
-        torch.cuda.synchronize()
+        # the scene's voxel filter sums centroids with index_add_, whose device version adds with float atomics in any order:
+        # deterministic algorithms make the clouds (and so the inputs of every timed step) the same bits from run to run
+        was_deterministic = torch.are_deterministic_algorithms_enabled()
+        torch.use_deterministic_algorithms(True)
+        try:
+            for f in range(n):
+                t = t0 + f / 30.0
+                pts, pos, quat = sc.frame(t)
+                out.append((pts, pos, quat, t))
+            torch.cuda.synchronize()
+        finally:
+            torch.use_deterministic_algorithms(was_deterministic)
         return out
 
     def quiet_host():
@@ -344,6 +361,24 @@ def main():
         land inside a 20-step timed region at random.  Collect now, keep the collector off until the region ends."""
         gc.collect()
         gc.disable()
+
+    def step_outputs(mm, cnt, suffix=""):
+        """--dump-outputs: what a caller of the timed path receives after its last step -- the voxel results grid ([V, 4]:
+        occupancy mass, mean vx, vy, vz, in the reference's voxel order) and the step's device counters.  A grid larger than
+        DUMP_GRID_BYTES (shared by the ranks of an N > 1 run) is written as a fixed, seeded sample of its rows together with
+        the rows' indices."""
+        if not args.dump_outputs:
+            return None
+        budget = DUMP_GRID_BYTES // world
+        res = mm.results()
+        out = {"counters" + suffix: np.array([cnt[k] for k in COUNTER_KEYS], np.float64)}
+        if res.nbytes <= budget:
+            out["voxel_results" + suffix] = res
+        else:   # 16 B of grid + 8 B of index per sampled row
+            rows = np.sort(np.random.default_rng(0).choice(res.shape[0], budget // (res.strides[0] + 8), replace=False))
+            out["voxel_results_sample" + suffix] = np.ascontiguousarray(res[rows])
+            out["voxel_results_sample_index" + suffix] = rows.astype(np.float64)
+        return out
 
     def run_frames(m, frames):
         for pts, pos, quat, t in frames:
@@ -377,6 +412,7 @@ def main():
         measure.host_issue_ms = t_issue / steps * 1e3
         measure.est_path = m.estimator_path()   # (of the TIMED frames: the stage-profiled ones below keep the frame on one stream)
         cnt = m.counters()
+        measure.outputs = step_outputs(m, cnt)   # before the stage-profiled frames change the map
         stage = None
         if profile:
             m.set_profiling(True)
@@ -401,8 +437,8 @@ def main():
         rk = sharded.CppShardedRank(D, dict(nx=w["nx"], ny=w["ny"], nz=w["nz"], res=w["res"], ppv=w["ppv"], seed=1234),
                                     world, rank, local_rank, broadcast=bcast)
         # every rank must be fed the SAME cloud, bit for bit (the ranks bin the same observations and all-reduce arrays whose
-        # length follows the point count): the scene's voxel filter sums with float atomics, so rank 0 generates the
-        # frames and hands them to the others once, before anything is timed
+        # length follows the point count): rank 0 generates the frames and hands them to the others once, before anything is
+        # timed, so that no rank relies on its own device and software reproducing rank 0's floating-point results
         frames = gen_frames(w, prefill + warmup + steps, seed=1234)
         if world > 1:
             shared = []
@@ -440,47 +476,54 @@ def main():
             cnt_all[k] = int(v)
         cnt_all["n_obs"] = cnt["n_obs"]  # every rank bins the same observations
         cnt_all["message_records"] = rk.map.L.dspmap_mgpu_message_records(rk.map.h)
+        measure.outputs = step_outputs(rk.map, cnt, suffix="_rank%d" % rank)   # this rank's slab
         return rk.map, frames, dt, cnt_all, None
 
     only = set(x for x in args.only.split(",") if x)
 
     def want(name):
-        return rank == 0 and not sharded_run and not args.no_extra and wl_name == "B" and (not only or name in only)
+        return args.full and rank == 0 and not sharded_run and not args.no_extra and wl_name == "B" and (not only or name in only)
 
     # ------------------------------------------------------------------ main measurement
     if not sharded_run:
-        m, frames, dt, cnt, stage = measure(wl, args.steps, args.warmup, args.prefill, estimator=args.estimator if not wl["sat"] else 0)
+        m, frames, dt, cnt, stage = measure(wl, args.steps, args.warmup, args.prefill, profile=args.full,
+                                            estimator=args.estimator if not wl["sat"] else 0)
     else:
         m, frames, dt, cnt, stage = measure_sharded(wl, args.steps, args.warmup, 5 if wl["sat"] else args.prefill)
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in measure.outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     fps = args.steps / dt
     V, T = (m.V_local, m.T) if not sharded_run else (m.V, m.T)
     balg = b_alg(cnt, V, T)
     ms = dt / args.steps * 1e3
     peak = 8000.0
     traffic_db, traffic_meta = {}, {}
-    try:   # HBM bytes per launch from the committed PMC passes of the same commands -- only if measured on THESE sources
-        tj = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-        fp_now = csrc_fingerprint()
-        if tj.get("csrc_sha16") == fp_now:
-            traffic_db = tj["workloads"]
-            KERNEL_US.update(tj.get("kernel_us", {}))
-            SQ_DB.update(tj.get("sq", {}))
-            traffic_meta = {"commit": tj.get("commit"), "csrc_sha16": fp_now}
-        else:
-            traffic_meta = {"stale": "profiles/pmc_traffic.json was measured on other kernel sources (fingerprint %s, commit %s; this "
-                                     "run: %s): traffic not reported" % (tj.get("csrc_sha16"), tj.get("commit"), fp_now)}
-    except Exception:
-        pass
     mw = (2 * wl["ppv"] + 63) // 64
+    roof = None   # a plain single-GPU run has no stage-profiled frames: the per-kernel roofline is a --full figure
     if stage is not None:
+        try:   # HBM bytes per launch from the committed PMC passes of the same commands -- only if measured on THESE sources
+            tj = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+            fp_now = csrc_fingerprint()
+            if tj.get("csrc_sha16") == fp_now:
+                traffic_db = tj["workloads"]
+                KERNEL_US.update(tj.get("kernel_us", {}))
+                SQ_DB.update(tj.get("sq", {}))
+                traffic_meta = {"commit": tj.get("commit"), "csrc_sha16": fp_now}
+            else:
+                traffic_meta = {"stale": "profiles/pmc_traffic.json was measured on other kernel sources (fingerprint %s, commit %s; this "
+                                         "run: %s): traffic not reported" % (tj.get("csrc_sha16"), tj.get("commit"), fp_now)}
+        except Exception:
+            pass
         roof = roofline_block(stage, cnt, V, T, mw, traffic_db, wl_name, peak, traffic_meta, getattr(measure, "event_overhead_ms", 0.0))
         if V < 500_000:   # the metric's own size: the frame is a chain of dependent launches of 5-35 us, none of them bandwidth-bound
             roof["note"] = ("at this map size every kernel is a latency chain (one wave per SIMD, ~0.2 TB/s for the whole frame); "
                             "the HBM-bound case is saturated_132x132x60 in this same line")
-    else:  # sharded run: whole-frame algorithmic bytes over all ranks against N x 8 TB/s
+    elif sharded_run:  # whole-frame algorithmic bytes over all ranks against N x 8 TB/s
         roof = {"bound": "hbm", "kernel": "whole frame (all ranks)", "achieved": round(balg / (ms * 1e-3) / 1e9, 3),
                 "peak": peak * world, "unit": "GB/s", "frac": round(balg / (ms * 1e-3) / 1e9 / (peak * world), 6),
                 "traffic": None, "algorithmic_bytes": int(balg)}
@@ -776,7 +819,7 @@ def main():
             result["preprocess_640x480"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ strong-scaling origin: config E on ONE GPU, unsharded
-    if rank == 0 and not args.no_extra and (wl_name == "B" or sharded_run) and os.environ.get("DSPMAP_BENCH_ORIGIN", "1") == "1" and (sharded_run or want("origin")):
+    if args.full and rank == 0 and not args.no_extra and (wl_name == "B" or sharded_run) and os.environ.get("DSPMAP_BENCH_ORIGIN", "1") == "1" and (sharded_run or want("origin")):
         try:
             if sharded_run:
                 m.close()
@@ -941,7 +984,7 @@ def main():
             result["projected_8gpu_264x264x80"] = {"error": repr(e)}
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N=1 only)
-    if rank == 0 and not sharded_run and not args.no_cpu:
+    if args.full and rank == 0 and not sharded_run and not args.no_cpu:
         try:
             from oracle import oracle_py as O
             import subprocess

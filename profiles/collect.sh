@@ -8,17 +8,17 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-r01_e}
 cd /tmp
 declare -A ARGS
-ARGS[B]="--steps 300 --warmup 30 --no-cpu --no-extra"
-ARGS[C_sat]="--workload C_sat --steps 40 --warmup 5 --prefill 3 --no-cpu --no-extra"
-ARGS[E_sat]="--workload E_sat --steps 12 --warmup 2 --prefill 3 --no-cpu --no-extra"
+ARGS[B]="--steps 300 --warmup 30 --full --no-cpu --no-extra"
+ARGS[C_sat]="--workload C_sat --steps 40 --warmup 5 --prefill 3 --full --no-cpu --no-extra"
+ARGS[E_sat]="--workload E_sat --steps 12 --warmup 2 --prefill 3 --full --no-cpu --no-extra"
 for W in B C_sat E_sat; do
   rm -rf /tmp/ks_$W
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$W -- python $R/bench.py ${ARGS[$W]} > /tmp/ks_$W.log 2>&1
   cp $(find /tmp/ks_$W -name "*kernel_stats.csv" | head -1) $R/gpurun_out/${TAG}_${W}_kernel_stats.csv
   grep '^{"metric' /tmp/ks_$W.log | tail -1 > $R/gpurun_out/${TAG}_${W}_bench.json
 done
-ARGS[B]="--steps 100 --warmup 10 --no-cpu --no-extra"
-ARGS[C_sat]="--workload C_sat --steps 20 --warmup 3 --prefill 3 --no-cpu --no-extra"
+ARGS[B]="--steps 100 --warmup 10 --full --no-cpu --no-extra"
+ARGS[C_sat]="--workload C_sat --steps 20 --warmup 3 --prefill 3 --full --no-cpu --no-extra"
 for W in B C_sat; do
   for C in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_${W}_$C

@@ -14,13 +14,13 @@ sys.path.insert(0, HERE)
 import summarize  # noqa: E402
 
 CMD = {
-    "B": "python bench.py --steps 300 --warmup 30 --no-cpu --no-extra",
-    "C_sat": "python bench.py --workload C_sat --steps 40 --warmup 5 --prefill 3 --no-cpu --no-extra",
-    "E_sat": "python bench.py --workload E_sat --steps 12 --warmup 2 --prefill 3 --no-cpu --no-extra",
+    "B": "python bench.py --steps 300 --warmup 30 --full --no-cpu --no-extra",
+    "C_sat": "python bench.py --workload C_sat --steps 40 --warmup 5 --prefill 3 --full --no-cpu --no-extra",
+    "E_sat": "python bench.py --workload E_sat --steps 12 --warmup 2 --prefill 3 --full --no-cpu --no-extra",
 }
 PMC_CMD = {
-    "B": "python bench.py --steps 100 --warmup 10 --no-cpu --no-extra",
-    "C_sat": "python bench.py --workload C_sat --steps 20 --warmup 3 --prefill 3 --no-cpu --no-extra",
+    "B": "python bench.py --steps 100 --warmup 10 --full --no-cpu --no-extra",
+    "C_sat": "python bench.py --workload C_sat --steps 20 --warmup 3 --prefill 3 --full --no-cpu --no-extra",
 }
 
 

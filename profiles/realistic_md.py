@@ -17,7 +17,7 @@ def main(tag):
     fr, wrr = cal.get("fetch_ratio", 0.5), cal.get("write_ratio", 1.0)
     out = ["# %s -- the realistic fill of 264x264x80 (depth stream from an empty map, ~510 k live particles in ~12 k of 87 120 tiles): "
            "HBM traffic, durations and issue slots per kernel" % tag, "",
-           "`rocprofv3 --pmc <C> --kernel-trace -- python bench.py --workload E --steps 60 --warmup 10 --no-cpu --no-extra` (separate "
+           "`rocprofv3 --pmc <C> --kernel-trace -- python bench.py --workload E --steps 60 --warmup 10 --full --no-cpu --no-extra` (separate "
            "counter-only passes; `TAG=%s tools/prof/pmc_realistic_E.sh`); corrected bytes = FETCH_SIZE*1024/%.3f + WRITE_SIZE*1024/%.3f "
            "(the calibration of `profiles/%s_pmc_traffic.md`); duration = the SQ pass's kernel trace; `VALU issue` = 4 x "
            "SQ_ACTIVE_INST_VALU / (duration x 2.4 GHz x 1024 SIMDs), at most 1 by construction." % (tag, fr, wrr, tag), "",

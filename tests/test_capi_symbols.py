@@ -191,15 +191,59 @@ def test_rebuild_decision_follows_the_source_hash_not_the_clock(dsp, tmp_path, m
     assert build_ext.needs_build()
 
 
-def test_reference_caller_type_checks_against_the_drop_in_header():
-    """tools/check_reference_caller.sh: g++ -fsyntax-only on the reference's own src/map_sim_example.cpp, in place, against
-    include/dsp_dynamic.h (declaration-only ROS / PCL / Eigen stubs in a temp dir).  Only where the reference tree exists (the build
-    container); the GPU box has none."""
-    import shutil
-    import subprocess
-    import pytest
-    if not os.path.exists("/root/reference/src/map_sim_example.cpp") or not shutil.which("g++"):
-        pytest.skip("no reference tree here")
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "check_reference_caller.sh")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "OK: the reference's caller type-checks" in r.stdout
+def _reference_caller_source(surface, with_eigen):
+    """a translation unit that uses the DSPMap surface the way the reference's node does (tests/golden/reference_caller_surface.json):
+    a global map built during static initialisation, every recorded member called with arguments of the recorded types, the
+    configuration macros as constant expressions and array bounds, the std names unqualified; with_eigen: also the globals of Eigen
+    types, which the caller gets through the header alone"""
+    src = ["#include <%s>" % h for h in surface["own_includes"]] + ['#include "%s"' % surface["header"], ""]
+    obj = surface["global_object"]
+    src += ["DSPMap %s;" % obj, ""]
+    src += ["static %s std_name_%d;" % (n, i) for i, (n, kind) in enumerate(surface["unqualified_std_names"].items()) if kind == "type"]
+    if with_eigen:
+        src += ["static %s eigen_global_%d;" % (n, i) for i, n in enumerate(surface["eigen_globals"])]
+    src += ["static_assert(%s > 0, \"%s\");" % (c, c) for c in surface["int_constants"]]
+    src += ["static float array_%d%s;" % (i, "".join("[%s]" % b for b in dims)) for i, dims in enumerate(surface["static_array_bounds"])]
+    src += ["", "int main() {"]
+    src += ["    const float constant_%d = %s * %s / 2;" % (i, c, surface["int_constants"][0]) for i, c in enumerate(surface["float_constants"])]
+    src += ["    std::cout << constant_%d << %s;" % (i, n) for i in range(len(surface["float_constants"]))
+            for n, kind in surface["unqualified_std_names"].items() if kind == "manipulator"]
+    for i, call in enumerate(surface["calls"]):
+        names = []
+        for j, t in enumerate(call["args"]):
+            names.append("a%d_%d" % (i, j))
+            src.append("    %s %s{};" % (t.rstrip("&"), names[-1]))
+        expr = "%s%s(%s)" % ("DSPMap::" if call["static"] else obj + ".", call["member"], ", ".join(names))
+        src.append("    if (!%s) return 1;" % expr if call["result_as_condition"] else "    %s;" % expr)
+    src += ["    return 0;", "}", ""]
+    return "\n".join(src)
+
+
+def test_reference_caller_type_checks_against_the_drop_in_header(tmp_path):
+    """include/dsp_dynamic.h offers what the reference's node (its src/map_sim_example.cpp) needs to compile against it unchanged:
+    g++ -fsyntax-only on a caller generated from the recorded surface (tests/golden/reference_caller_surface.json), once with the
+    header's own minimal pcl containers and once with PCL and Eigen installations in front of it (declaration-only stubs in a temp
+    dir), where the Eigen types of the node's globals must arrive through the header's include"""
+    import json
+    surface = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_caller_surface.json")))
+    assert len(surface["calls"]) >= 9 and surface["eigen_globals"]
+    pcl = tmp_path / "stubs" / "pcl"
+    pcl.mkdir(parents=True)
+    (pcl / "point_types.h").write_text(
+        "#pragma once\n#include <vector>\n#include <memory>\n#include <cstddef>\nnamespace pcl {\nstruct PointXYZ { float x, y, z; };\n"
+        "struct PointXYZINormal { float x, y, z, intensity, normal_x, normal_y, normal_z; };\n"
+        "template <class T> struct PointCloud { typedef std::shared_ptr<PointCloud<T> > Ptr; std::vector<T> points; unsigned width, height;\n"
+        "    void push_back(const T&); void clear(); size_t size() const; bool empty() const; T& operator[](size_t); };\n}\n")
+    (pcl / "point_cloud.h").write_text("#include <pcl/point_types.h>\n")
+    eigen = tmp_path / "stubs" / "Eigen"
+    eigen.mkdir()
+    (eigen / "Eigen").write_text("#pragma once\nnamespace Eigen {\nstruct Vector3d { double x() const; double y() const; double z() const; };\n"
+                                 "struct Quaternionf { float w() const; float x() const; float y() const; float z() const; };\n}\n")
+    flags = ["g++", "-std=c++14", "-fsyntax-only", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-Wno-sign-compare",
+             "-Wno-unused-function", "-I" + os.path.join(ROOT, "include")]
+    for with_libs in (False, True):
+        caller = tmp_path / ("caller_%d.cpp" % with_libs)
+        caller.write_text(_reference_caller_source(surface, with_eigen=with_libs))
+        extra = ["-I" + str(tmp_path / "stubs")] if with_libs else []
+        r = subprocess.run(flags + extra + [str(caller)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, caller.read_text() + r.stderr[-4000:]

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 N=${1:-3}; shift
 for i in $(seq 1 $N); do
   for arm in "$@"; do
-    v=$(env $arm python bench.py --gpus 1 --steps 20 --warmup 5 --prefill 20 --only saturated --no-cpu 2>/dev/null | grep '^{' | python -c "
+    v=$(env $arm python bench.py --gpus 1 --steps 20 --warmup 5 --prefill 20 --full --only saturated --no-cpu 2>/dev/null | grep '^{' | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); s=d['saturated_132x132x60']; print(s.get('ms_per_step'), s.get('frac_of_8TBps'), s.get('counters',{}).get('n_live_in'), s.get('error'))")
     echo "run $i [$arm] : $v" >> $out
   done

@@ -5,7 +5,7 @@ out=gpurun_out/ab_extras.txt
 mkdir -p gpurun_out
 : > $out
 for arm in "$@"; do
-  env $arm python bench.py --gpus 1 --steps 20 --warmup 5 --prefill 20 --only saturated,rollout,origin,realistic --no-cpu 2>/dev/null | grep '^{' | python -c "
+  env $arm python bench.py --gpus 1 --steps 20 --warmup 5 --prefill 20 --full --only saturated,rollout,origin,realistic --no-cpu 2>/dev/null | grep '^{' | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 s=d.get('saturated_132x132x60',{}); r=d.get('rollout_D_132x132x60_T10',{}); e=d.get('single_gpu_264x264x80',{}); f=d.get('realistic_fill',{})

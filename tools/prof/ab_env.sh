@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: ab_env.sh "<bench args>" ENVVAR val1 val2 ...
-args="$1"; var="$2"; shift; shift
+args="$1 --full"; var="$2"; shift; shift
 for v in "$@"; do
   env $var=$v python bench.py $args > gpurun_out/ab_$v.json 2> gpurun_out/ab_$v.err
   python - <<PY

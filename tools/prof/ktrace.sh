@@ -2,7 +2,7 @@
 # usage: ktrace.sh "<bench args>" [ENV=val ...]   -> per-kernel average durations
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-args="$1"; shift
+args="$1 --full"; shift
 cd /tmp; rm -rf /tmp/kt
 env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $R/bench.py $args > /tmp/kt.log 2>&1
 f=$(find /tmp/kt -name "*kernel_stats.csv" | head -1)

@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp
-A="--workload E --steps 60 --warmup 10 --no-cpu --no-extra"
+A="--workload E --steps 60 --warmup 10 --full --no-cpu --no-extra"
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pe_$C
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d /tmp/pe_$C -- python $R/bench.py $A > /tmp/pe_$C.log 2>&1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: run_variants.sh "<bench args>" v0 v1 ...
-args="$1"; shift
+args="$1 --full"; shift
 for v in "$@"; do
   cp scratch/so/$v.so dsp-map_amd/lib/libdspmap_hip.so
   python bench.py $args > gpurun_out/exp_$v.json 2> gpurun_out/exp_$v.err

@@ -5,7 +5,7 @@ cd /tmp; rm -rf /tmp/tl
 # usage: timeline.sh [workload [steps [warmup]]]   (frames from the TIMED region: the stage-profiled frames at the end of a
 # bench run keep large maps on one stream)
 W=${1:-B}; S=${2:-60}; WU=${3:-10}
-rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python $R/bench.py --workload $W --steps $S --warmup $WU --no-cpu --no-extra > /tmp/tl.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -- python $R/bench.py --workload $W --steps $S --warmup $WU --full --no-cpu --no-extra > /tmp/tl.log 2>&1
 f=$(find /tmp/tl -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY'
 import csv, sys
