@@ -125,6 +125,7 @@ SIGNATURES = {
     "dspmap_get_observations": (_i, [_P, _P, _P, _P, _fp]),
     "dspmap_set_expected_newborn": (_i, [_P, _f]),
     "dspmap_get_pyramid_counts": (_i, [_P, _P]),
+    "dspmap_get_pyramid_candidates": (_i, [_P, _P]),
     "dspmap_mgpu_bind": (_i, [_P, _P, _P, _i]),
     "dspmap_mgpu_place_interior": (_i, [_P]),
     "dspmap_mgpu_begin": (_i, [_P, _i, _P, _i, _P, _P, _d, _P]),
@@ -500,6 +501,12 @@ class DSPMap:
     def pyramid_counts(self):
         out = np.zeros(self.NP, np.int32)
         self._chk(self.L.dspmap_get_pyramid_counts(self.h, _ptr(out)))
+        return out
+
+    def pyramid_candidates(self):
+        """particles the last prediction tried to register per pyramid, before the cut (not clamped to the capacity)"""
+        out = np.zeros(self.NP, np.int32)
+        self._chk(self.L.dspmap_get_pyramid_candidates(self.h, _ptr(out)))
         return out
 
     def observations(self):

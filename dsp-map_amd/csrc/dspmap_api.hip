@@ -126,6 +126,7 @@ static void derive_dims(dspmap* m) {
     const int safe_particle_num = (int)((double)d.v_glob * d.M + 1e5); // :64
     d.capp = safe_particle_num / pyramid_num * 2;                      // :66
     d.capa = 2 * d.capp + 64;
+    d.pool = (int)std::min<long long>((long long)d.np * d.capa, 1 << 22);   // (a cold path: as many entries as the lists, at most 4 M)
     d.T = c.prediction_times;
     d.res = c.voxel_resolution;
     d.half_x = (d.res * (float)c.nx) * 0.5f;                           // :528-530
@@ -214,7 +215,7 @@ static void free_dev(dspmap* m) {
     if (m->mgpu_count) chk(hipFree(m->mgpu_count), "hipFree");
     void* ptrs[] = {s.fpar, s.obs_ckf, s.part_inv, s.fut_stat, s.mask, s.nbmask, s.pos, s.vel, s.w, s.vz0, s.res4, s.fut, s.fut_out, s.obs, s.obs_ck,
                     s.obs_cnt, s.obs_maxlen, s.planes_h, s.planes_v, s.planes_h0, s.planes_v0, s.pt_rot, s.pt_pyr,
-                    s.birth, s.plan, s.plan_pbase, s.plan_inside, s.nstatic, s.fov_rec, s.fov_slot, s.fov_key, s.fov_spos, s.fov_rec_s, s.fov_slot_s, s.pyr_cnt, s.in_n, s.pmask, s.ta, s.dflag, s.dirty,
+                    s.birth, s.plan, s.plan_pbase, s.plan_inside, s.nstatic, s.fov_rec, s.fov_slot, s.fov_key, s.fov_spos, s.fov_rec_s, s.fov_slot_s, s.pyr_cnt, s.pool_pyr, s.in_n, s.pmask, s.ta, s.dflag, s.dirty,
                     s.blk_cnt, s.occ_xyz, s.p_tab, s.v_tab, s.r_tab, s.fs, m->k.mv_rec, m->k.ro_cnt, m->k.in_rec, m->k.in_cnt, m->k.tile_bits, m->k.omask, m->k.ck_items, m->k.wu_items, m->k.n_items, m->k.nb_tab, m->k.expmask,
                     s.tile_moving, m->k.ro_stat, m->k.ro_sub, m->k.part_predict, m->k.tile_fov, m->k.view_list, m->k.tile_cls, s.tile_live, s.fut_dirty, m->k.part_resample, m->k.vb_cnt, m->k.vb_idx, m->k.work_list, m->k.child, m->k.part_birth, m->k.vz_q, m->pts_dev, s.birth_ovf, s.birth_cvr};
     for (void* p : ptrs) if (p) chk(hipFree(p), "hipFree");
@@ -420,10 +421,11 @@ extern "C" int dspmap_init_device(dspmap_t* m) {
     HIPCHK(m, dalloc(&s.obs_maxlen, (size_t)d.np));
     HIPCHK(m, dalloc(&s.planes_h, (size_t)(d.np_h + 1) * 3)); HIPCHK(m, dalloc(&s.planes_v, (size_t)(d.np_v + 1) * 3));
     HIPCHK(m, dalloc(&s.planes_h0, (size_t)(d.np_h + 1) * 3)); HIPCHK(m, dalloc(&s.planes_v0, (size_t)(d.np_v + 1) * 3));
-    HIPCHK(m, dalloc(&s.fov_rec, (size_t)d.np * d.capa));
-    HIPCHK(m, dalloc(&s.fov_slot, (size_t)d.np * d.capa));
-    HIPCHK(m, dalloc(&s.fov_key, (size_t)d.np * d.capa));
-    HIPCHK(m, dalloc(&s.fov_spos, (size_t)d.np * d.capa));
+    HIPCHK(m, dalloc(&s.fov_rec, (size_t)d.np * d.capa + d.pool));
+    HIPCHK(m, dalloc(&s.fov_slot, (size_t)d.np * d.capa + d.pool));
+    HIPCHK(m, dalloc(&s.fov_key, (size_t)d.np * d.capa + d.pool));
+    HIPCHK(m, dalloc(&s.fov_spos, (size_t)d.np * d.capa + d.pool));
+    HIPCHK(m, dalloc(&s.pool_pyr, (size_t)d.pool));
     HIPCHK(m, dalloc(&s.fov_rec_s, (size_t)d.np * d.capp));
     HIPCHK(m, dalloc(&s.fov_slot_s, (size_t)d.np * d.capp));
     HIPCHK(m, dalloc(&s.pyr_cnt, (size_t)d.np));
@@ -2009,6 +2011,13 @@ extern "C" int dspmap_get_pyramid_counts(dspmap_t* m, int* out) {
     HIPCHK(m, hipStreamSynchronize(m->stream));
     HIPCHK(m, hipMemcpy(out, m->s.pyr_kept ? m->s.pyr_kept : m->s.pyr_cnt, sizeof(int) * m->d.np, hipMemcpyDeviceToHost));   // (a sharded map's global cut: what this rank keeps)
     for (int i = 0; i < m->d.np; i++) if (out[i] > m->d.capp) out[i] = m->d.capp;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_pyramid_candidates(dspmap_t* m, int* out) {
+    READY(m);
+    if (!out) return DSPMAP_E_ARG;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(out, m->s.pyr_cnt, sizeof(int) * m->d.np, hipMemcpyDeviceToHost));   // (every registration bumps the count, kept or not)
     return DSPMAP_OK;
 }
 extern "C" int dspmap_set_profiling(dspmap_t* m, int on) {

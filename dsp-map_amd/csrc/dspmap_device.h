@@ -340,6 +340,25 @@ __device__ __forceinline__ int pyr_len(const MapDims& d, const DevState& s, int 
     return s.pyr_kept ? s.pyr_kept[b] : min(s.pyr_cnt[b], d.capp);
 }
 
+// A candidate that comes after its pyramid's capa list entries (the atomic ARRIVAL order, not the reference's sweep order) goes to
+// the frame's spill pool; k_pyr_prepare cuts list and pool entries together by their sweep keys.  Returns the entry's ref (index into
+// the fov_* arrays), or -1: the pool is full too -- the particle is turned away here, counted as inexact.  A cold path.
+__device__ __forceinline__ int spill_entry(const MapDims& d, const DevState& s, int pyr, float4 rec, int cell, int key) {
+    const int q = atomicAdd(&s.fs->n_pool, 1);
+    if (q >= d.pool) { atomicAdd(&s.fs->n_overflow_inexact, 1); return -1; }
+    const int ref = d.np * d.capa + q;
+    s.pool_pyr[q] = pyr;
+    s.fov_rec[ref] = rec;
+    s.fov_slot[ref] = cell;
+    s.fov_key[ref] = key;
+    return ref;
+}
+// the pyramid of a list or pool entry (k_place_fix)
+__device__ __forceinline__ int ref_pyramid(const MapDims& d, const DevState& s, int ref) {
+    const int r0 = d.np * d.capa;
+    return ref < r0 ? ref / d.capa : s.pool_pyr[ref - r0];
+}
+
 #define GU 16
 // obs_gather_wave: one wave per pyramid (k_obs_gather; in a whole frame the extra workgroups of k_predict).  Appends matching points in INPUT order
 // (stable, ballot + prefix popcount) to the pyramid's bin, keeps the first 99

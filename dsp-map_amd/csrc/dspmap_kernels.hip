@@ -57,7 +57,7 @@ __global__ void k_reset(MapDims d, DevState s, int flags) {
     if (flags & RESET_PRED) {
         for (int i = gt; i < d.np; i += gn) s.pyr_cnt[i] = 0;
         if (gt == 0) {
-            s.fs->n_voxel_full_import = 0; s.fs->n_exp_up = 0; s.fs->n_exp_down = 0; s.fs->n_pyr_removed = 0; s.fs->n_dirty = 0; s.fs->n_overflow_inexact = 0; s.fs->n_place_vf = 0; s.fs->n_place_pf = 0; s.fs->n_view_tiles = 0; s.fs->pred_epoch = s.fs->pred_epoch + 1; s.fs->live_hint = s.fs->live_acc; s.hint_out[0] = s.fs->live_acc; s.fs->live_acc = 0; s.hint_out[1] = s.fs->mv_acc; s.fs->mv_acc = 0;
+            s.fs->n_voxel_full_import = 0; s.fs->n_exp_up = 0; s.fs->n_exp_down = 0; s.fs->n_pyr_removed = 0; s.fs->n_pool = 0; s.fs->n_dirty = 0; s.fs->n_overflow_inexact = 0; s.fs->n_place_vf = 0; s.fs->n_place_pf = 0; s.fs->n_view_tiles = 0; s.fs->pred_epoch = s.fs->pred_epoch + 1; s.fs->live_hint = s.fs->live_acc; s.hint_out[0] = s.fs->live_acc; s.fs->live_acc = 0; s.hint_out[1] = s.fs->mv_acc; s.fs->mv_acc = 0;
         }
     }
 }
@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(256) k_obs_points(MapDims d, DevState s, const
             s.fs->cur_pos[0] = cpx; s.fs->cur_pos[1] = cpy; s.fs->cur_pos[2] = cpz;
             s.fs->n_valid = 0; s.fs->n_obs = 0; s.fs->has_expected_override = 0;   // k_obs_gather accumulates the first two
             s.fs->bits_on = bits_blk0 >= 0 ? 1 : 0;
-            s.fs->n_voxel_full_import = 0; s.fs->n_exp_up = 0; s.fs->n_exp_down = 0; s.fs->n_pyr_removed = 0; s.fs->n_dirty = 0; s.fs->n_overflow_inexact = 0; s.fs->n_place_vf = 0; s.fs->n_place_pf = 0; s.fs->n_view_tiles = 0; s.fs->pred_epoch = s.fs->pred_epoch + 1; s.fs->live_hint = s.fs->live_acc; s.hint_out[0] = s.fs->live_acc; s.fs->live_acc = 0; s.hint_out[1] = s.fs->mv_acc; s.fs->mv_acc = 0;
+            s.fs->n_voxel_full_import = 0; s.fs->n_exp_up = 0; s.fs->n_exp_down = 0; s.fs->n_pyr_removed = 0; s.fs->n_pool = 0; s.fs->n_dirty = 0; s.fs->n_overflow_inexact = 0; s.fs->n_place_vf = 0; s.fs->n_place_pf = 0; s.fs->n_view_tiles = 0; s.fs->pred_epoch = s.fs->pred_epoch + 1; s.fs->live_hint = s.fs->live_acc; s.hint_out[0] = s.fs->live_acc; s.fs->live_acc = 0; s.hint_out[1] = s.fs->mv_acc; s.fs->mv_acc = 0;
         }
     } else {
         for (int i = threadIdx.x; i < (d.np_h + 1) * 3; i += blockDim.x) s_ph[i] = s.planes_h[i];
@@ -182,19 +182,24 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
     __shared__ int s_scan[17];
     const int tid = threadIdx.x;
     PSTAMP(0);
-    const int P_all = min(s.pyr_cnt[b], d.capa);
+    const int cnt = s.pyr_cnt[b];
+    const int P_all = min(cnt, d.capa);
+    // the candidates after the list's capa entries are in the spill pool (spill_entry): a cold path that scans the whole pool for
+    // this pyramid's entries in each pass below
+    const int n_sp = cnt > d.capa ? min(s.fs->n_pool, d.pool) : 0;
+    const size_t sp0 = (size_t)d.np * d.capa;
 #ifdef PYR_PROF
     if (tid == 0 && b < 1024) g_pprof[b * 8 + 7] = P_all;
 #endif
-    if (tid == 0 && s.pyr_gcnt) s.pyr_gcnt[b] = P_all;   // (a sharded map: the ranks' list lengths are summed by the Ck all-reduce)
+    if (tid == 0 && s.pyr_gcnt) s.pyr_gcnt[b] = cnt;   // (a sharded map: the ranks' list lengths are summed by the Ck all-reduce)
     if (P_all == 0) return;
     const float4* __restrict__ src = s.fov_rec + (size_t)b * d.capa;
     const int* __restrict__ src_slot = s.fov_slot + (size_t)b * d.capa;
     int* __restrict__ src_key = s.fov_key + (size_t)b * d.capa;
     // A full list (:1245-1259): the reference registers a pyramid's particles in the order of its voxel / slot sweep and
     // turns away what comes after SAFE_PARTICLE_NUM_PYRAMID entries.  The list here was filled in arrival order, but
-    // every entry carries its sweep key: the capp SMALLEST keys stay (radix select of the capp-th key, 4 x 8 bits),
-    // the others lose their slot -- the same particles as in the reference, independent of the arrival order.
+    // every entry carries its sweep key: the capp SMALLEST keys of the list and its spill-pool entries stay (radix select of
+    // the capp-th key), the others lose their slot -- the same particles as in the reference, independent of the arrival order.
     int kstar = 0x7fffffff;
     if (s.pyr_kstar) {
         // a sharded map: SAFE_PARTICLE_NUM_PYRAMID bounds the list over ALL ranks -- the threshold was selected over the union of
@@ -238,6 +243,11 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
                 } else if (bin >= 0) atomicAdd(&s_sel[bin], 1);
                 }
             }
+            for (int q = tid; q < n_sp; q += 1024) {
+                if (s.pool_pyr[q] != b) continue;
+                const unsigned k = (unsigned)src_key[sp0 - (size_t)b * d.capa + q];
+                if (ps == npass - 1 || (k >> (shift + 13)) == (prefix >> (shift + 13))) atomicAdd(&s_sel[(k >> shift) & 8191u], 1);
+            }
             __syncthreads();
             {   // the bin that holds the want-th key: thread t owns bins [8t, 8t + 8); exclusive prefix over the threads
                 int c8[8], mine = 0;
@@ -264,6 +274,21 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
     if (tid < PS_NBK) s_hist[tid] = 0;
     __syncthreads();
     int removed = 0;
+    // turned away: the particle vanishes (-2): its cell -> (voxel, slot) -> occupancy bit.  The entry is marked so that a second
+    // preparation of the same lists (stage API: after the prediction and again before the update) changes nothing.
+    auto turn_away = [&](size_t i) {
+        src_key[i] = 0x7fffffff;
+        const int c = src_slot[i];
+        const int tile = c / (64 * d.slots), rem = c - tile * 64 * d.slots, slot = rem >> 6, lv = tile * 64 + (rem & 63);
+        atomicAnd(&s.mask[(size_t)lv * d.mw + (slot >> 6)], ~(1ull << (slot & 63)));
+        // the reference hands the slot back AT ONCE (:1256-1259): the arrivals that the sweep serves after this particle may
+        // take it.  k_place ran before the lists were cut, so the voxel is noted for k_place_fix, which re-slots its arrivals
+        atomicOr(&s.ta[(size_t)lv * d.mw + (slot >> 6)], 1ull << (slot & 63));
+        if (atomicExch(&s.dflag[lv], 1) == 0) {
+            const int q = atomicAdd(&s.fs->n_dirty, 1);
+            if (q < DSP_DIRTY_CAP) s.dirty[q] = lv; else atomicAdd(&s.fs->n_overflow_inexact, 1);
+        }
+    };
     // (PSU entries per thread and step, their loads issued together: a step is one memory round trip, ~1.5 us, and a list of config E
     // has 55 k entries -- 54 steps per pass at one entry per thread: 75 + 80 us for the two passes of the longest lists, round 5)
     for (int i0 = tid; i0 < P_all; i0 += 1024 * PSU) {
@@ -282,24 +307,15 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
         const int key_i = key_u[u];
         const float4 r_i = r_u[u];
         if (key_i <= kstar) atomicAdd(&s_hist[range_bucket(d, r_i)], 1);
-        else if (key_i != 0x7fffffff) {
-            // turned away: the particle vanishes (-2): its cell -> (voxel, slot) -> occupancy bit.  The entry is marked so
-            // that a second preparation of the same lists (stage API: after the prediction and again before the update)
-            // changes nothing.
-            src_key[i] = 0x7fffffff;
-            const int c = src_slot[i];
-            const int tile = c / (64 * d.slots), rem = c - tile * 64 * d.slots, slot = rem >> 6, lv = tile * 64 + (rem & 63);
-            atomicAnd(&s.mask[(size_t)lv * d.mw + (slot >> 6)], ~(1ull << (slot & 63)));
-            // the reference hands the slot back AT ONCE (:1256-1259): the arrivals that the sweep serves after this particle may
-            // take it.  k_place ran before the lists were cut, so the voxel is noted for k_place_fix, which re-slots its arrivals
-            atomicOr(&s.ta[(size_t)lv * d.mw + (slot >> 6)], 1ull << (slot & 63));
-            if (atomicExch(&s.dflag[lv], 1) == 0) {
-                const int q = atomicAdd(&s.fs->n_dirty, 1);
-                if (q < DSP_DIRTY_CAP) s.dirty[q] = lv; else atomicAdd(&s.fs->n_overflow_inexact, 1);
-            }
-            ++removed;
+        else if (key_i != 0x7fffffff) { turn_away(i); ++removed; }
         }
-        }
+    }
+    for (int q = tid; q < n_sp; q += 1024) {   // (the spill pool: its entries of this pyramid, relative to the list's base)
+        if (s.pool_pyr[q] != b) continue;
+        const size_t i = sp0 - (size_t)b * d.capa + q;
+        const int key_i = src_key[i];
+        if (key_i <= kstar) atomicAdd(&s_hist[range_bucket(d, src[i])], 1);
+        else if (key_i != 0x7fffffff) { turn_away(i); ++removed; }
     }
     if (__ballot(removed != 0)) { removed = wave_sum_i(removed); if (lane_id() == 0 && removed) atomicAdd(&s.fs->n_pyr_removed, removed); }
     __syncthreads();
@@ -354,6 +370,20 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
                 for (int u = 0; u < PSU; ++u) { key_u[u] = key_n[u]; sl_u[u] = sl_n[u]; r_u[u] = r_n[u]; }
             }
         }
+        for (int q = tid; q < n_sp; q += 1024) {   // the kept entries of the spill pool
+            if (s.pool_pyr[q] != b) continue;
+            const size_t i = sp0 + q;
+            const int key = s.fov_key[i];
+            if (key > kstar) continue;
+            const float4 r = s.fov_rec[i];
+            const int c = s.fov_slot[i];
+            const int k = range_bucket(d, r);
+            const int pos = s_base[k] + atomicAdd(&s_hist[k], 1);
+            s.fov_rec_s[(size_t)b * d.capp + pos] = r;
+            s.fov_slot_s[(size_t)b * d.capp + pos] = c;
+            const int tile = c / (64 * d.slots), rem = c - tile * 64 * d.slots;
+            if (key != g_of_lv(d, tile * 64 + (rem & 63)) * d.slots + (rem >> 6)) s.fov_spos[i] = pos;
+        }
     }
     __syncthreads();
     PSTAMP(3);
@@ -390,10 +420,13 @@ __global__ void __launch_bounds__(256) k_pyr_hist(MapDims d, DevState s, int pas
     const int2 st = pass > 0 ? sel[b] : make_int2(0, 0);
     if (pass == 0 || st.y >= 0) {
         const int shift = 24 - 8 * pass;
-        const int P_all = min(s.pyr_cnt[b], d.capa);
+        const int cnt = s.pyr_cnt[b];
+        const int P_all = min(cnt, d.capa), n_sp = cnt > d.capa ? min(s.fs->n_pool, d.pool) : 0;
         const int* __restrict__ key = s.fov_key + (size_t)b * d.capa;
-        for (int i = tid; i < P_all; i += 256) {
-            const unsigned k = (unsigned)key[i];
+        const int* __restrict__ pkey = s.fov_key + (size_t)d.np * d.capa;
+        for (int i = tid; i < P_all + n_sp; i += 256) {   // the list, then the spill pool's entries of this pyramid
+            if (i >= P_all && s.pool_pyr[i - P_all] != b) continue;
+            const unsigned k = (unsigned)(i < P_all ? key[i] : pkey[i - P_all]);
             if (k == 0x7fffffffu) continue;   // (turned away by an earlier preparation of the same lists)
             if (pass > 0 && (k >> (shift + 8)) != ((unsigned)st.x >> (shift + 8))) continue;
             atomicAdd(&s_h[(k >> shift) & 255u], 1);
@@ -441,10 +474,13 @@ __global__ void __launch_bounds__(256) k_pyr_kept(MapDims d, DevState s, const i
     const int b = (int)blockIdx.x, tid = threadIdx.x;
     if (tid == 0) s_n = 0;
     __syncthreads();
-    const int P_all = min(s.pyr_cnt[b], d.capa), ks = kstar[b];
+    const int cnt = s.pyr_cnt[b];
+    const int P_all = min(cnt, d.capa), n_sp = cnt > d.capa ? min(s.fs->n_pool, d.pool) : 0, ks = kstar[b];
     const int* __restrict__ key = s.fov_key + (size_t)b * d.capa;
+    const int* __restrict__ pkey = s.fov_key + (size_t)d.np * d.capa;
     int n = 0;
     for (int i = tid; i < P_all; i += 256) { const int k = key[i]; n += (k <= ks && k != 0x7fffffff) ? 1 : 0; }
+    for (int q = tid; q < n_sp; q += 256) { if (s.pool_pyr[q] != b) continue; const int k = pkey[q]; n += (k <= ks && k != 0x7fffffff) ? 1 : 0; }
     n = wave_sum_i(n);
     if (lane_id() == 0 && n) atomicAdd(&s_n, n);
     __syncthreads();
@@ -616,7 +652,7 @@ __device__ __forceinline__ void place_fix_wave(const MapDims& d, const DevState&
                 if (ref >= 0 && s.fov_key[ref] != 0x7fffffff) {
                     const int didx = (int)(tcell + (size_t)to[j] * 64 + ln);
                     s.fov_slot[ref] = didx;
-                    const int b = ref / d.capa, sp = s.fov_spos[ref];
+                    const int b = ref_pyramid(d, s, ref), sp = s.fov_spos[ref];
                     if (sp >= 0 && sp < d.capp) s.fov_slot_s[(size_t)b * d.capp + sp] = didx;
                 }
             }

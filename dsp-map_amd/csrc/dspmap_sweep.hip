@@ -668,13 +668,15 @@ __global__ void __launch_bounds__(NW * 64, PRED_LB) k_predict(MapDims d, DevStat
             st_rec(i, a, b);
             const int pyr = __float_as_int(a.x), sl = __float_as_int(a.y);   // sl = (slot << 6) | lane
             const int pos = s_hist[pyr] + __float_as_int(b.z);
+            const int cell = (int)(((size_t)BX * d.slots + (sl >> 6)) * 64 + (sl & 63));
+            const int skey = (tgb + lane_goff(d, sl & 63)) * d.slots + (sl >> 6);   // a stayer's sweep key is its own cell
             if (pos < d.capa) {
                 const size_t o = (size_t)pyr * d.capa + pos;
                 s.fov_rec[o] = make_float4(a.z, a.w, b.x, b.y);
-                s.fov_slot[o] = (int)(((size_t)BX * d.slots + (sl >> 6)) * 64 + (sl & 63));
-                s.fov_key[o] = (tgb + lane_goff(d, sl & 63)) * d.slots + (sl >> 6);   // a stayer's sweep key is its own cell
-            } else {
-                // pyramid list full: the particle vanishes (-2, :1256-1259)
+                s.fov_slot[o] = cell;
+                s.fov_key[o] = skey;
+            } else if (spill_entry(d, s, pyr, make_float4(a.z, a.w, b.x, b.y), cell, skey) < 0) {
+                // beyond the list AND the spill pool: the particle vanishes (-2, :1256-1259) whatever its key (counted as inexact)
                 atomicAnd(&s_keep[((sl >> 12) & 1) * 64 + (sl & 63)], ~(1ull << ((sl >> 6) & 63)));
                 ++c_pf;
             }
@@ -695,13 +697,15 @@ __global__ void __launch_bounds__(NW * 64, PRED_LB) k_predict(MapDims d, DevStat
             float4 a, b;
             st_rec(i0 + j * NW * 64 + tid, a, b);
             const int sl = __float_as_int(a.y);   // (slot << 6) | lane
+            const int cell = (int)(((size_t)BX * d.slots + (sl >> 6)) * 64 + (sl & 63));
+            const int skey = (tgb + lane_goff(d, sl & 63)) * d.slots + (sl >> 6);
             if (pos[j] < d.capa) {
                 const size_t o = (size_t)key[j] * d.capa + pos[j];
                 s.fov_rec[o] = make_float4(a.z, a.w, b.x, b.y);
-                s.fov_slot[o] = (int)(((size_t)BX * d.slots + (sl >> 6)) * 64 + (sl & 63));
-                s.fov_key[o] = (tgb + lane_goff(d, sl & 63)) * d.slots + (sl >> 6);
-            } else {
-                // pyramid list full: the particle vanishes (-2, :1256-1259)
+                s.fov_slot[o] = cell;
+                s.fov_key[o] = skey;
+            } else if (spill_entry(d, s, key[j], make_float4(a.z, a.w, b.x, b.y), cell, skey) < 0) {
+                // beyond the list AND the spill pool: the particle vanishes (-2, :1256-1259) whatever its key (counted as inexact)
                 atomicAnd(&s_keep[((sl >> 12) & 1) * 64 + (sl & 63)], ~(1ull << ((sl >> 6) & 63)));
                 ++c_pf;
             }
@@ -946,8 +950,9 @@ __device__ __forceinline__ void place_tile(const MapDims& d, const DevState& s, 
                     s.fov_key[o] = skey;   // a mover is registered when the sweep reaches its SOURCE cell
                     ref = (int)o;
                 } else {
-                    ++c_pf;  // :1256-1259
-                    keep = false;
+                    // beyond the list: the spill pool (the cut decides by the sweep key); beyond that too, turned away (:1256-1259)
+                    ref = spill_entry(d, s, key[0], make_float4(px, py, pz, w), (int)nidx, skey);
+                    if (ref < 0) { ++c_pf; keep = false; }
                 }
             }
             gbk[cap + i] = ref;   // the arrival's list entry, beside its inbox record (k_place_fix re-points it if the arrival is moved)

@@ -50,6 +50,7 @@ struct MapDims {
     int np_h, np_v, np;    // pyramids :58-60
     int capp;              // SAFE_PARTICLE_NUM_PYRAMID :66
     int capa;              // entries a pyramid's UNSORTED list can hold (2 x capp + 64): k_pyr_prepare keeps the capp smallest keys
+    int pool;              // entries of the spill pool: the candidates beyond a list's capa entries (spill_entry, dspmap_device.h)
     int T;                 // PREDICTION_TIMES :46
     int nn;                // pyramid neighbourhood radius: 1 = 3x3 (:1135-1136), 2 = 5x5 (dsp_dynamic_multiple_neighbors.h)
     int nbins;             // (2*nn+1)^2
@@ -105,6 +106,7 @@ struct FrameScalars {
     int v_cur_in, r_cur_in;    // the velocity-table / rand() cursors before the frame's births (the fused insertion reads these, one workgroup writes the new ones)
     int n_place_vf, n_place_pf;   // arrivals k_place turned away: voxel full (:1227-1229) / pyramid list full (:1256-1259)
     int n_pyr_removed;  // particles k_pyr_prepare turned away because their pyramid's list was full (-2, :1256-1259)
+    int n_pool;         // entries claimed in the spill pool by this prediction (may exceed MapDims::pool: the rest was dropped; reset with the lists)
     float expected_newborn;  // expected_new_born_objects :292
     float newborn_w;         // updated_weight_new_born :805
     float cur_pos[3];        // current_position :131
@@ -192,13 +194,16 @@ struct DevState {
     int* birth_ovf;         // [birth_cap*32] birth indices of the children that found their destination voxel's bucket full
                             // (FrameScalars::n_birth_ovf entries; their voxel is in KernelScratch::child)
     // FOV staging
-    float4* fov_rec;   // [np*capa] {x,y,z,w}
-    int* fov_slot;     // [np*capa] cell index of the particle (pidx)
-    int* fov_spos;     // [np*capa] where the range sort put the entry (index into fov_rec_s / fov_slot_s of its pyramid), -1 = not kept
-    int* fov_key;      // [np*capa] its sweep key (source voxel * slots + slot): the reference registers a pyramid's particles in this order
+    float4* fov_rec;   // [np*capa + pool] {x,y,z,w}
+    int* fov_slot;     // [np*capa + pool] cell index of the particle (pidx)
+    int* fov_spos;     // [np*capa + pool] where the range sort put the entry (index into fov_rec_s / fov_slot_s of its pyramid), -1 = not kept
+    int* fov_key;      // [np*capa + pool] its sweep key (source voxel * slots + slot): the reference registers a pyramid's particles in this order
     float4* fov_rec_s; // the same lists ordered by range bucket (k_pyr_sort), read by the pair kernels
     int* fov_slot_s;
-    int* pyr_cnt;      // [np]
+    int* pyr_cnt;      // [np] candidates registered this prediction (not clamped: those beyond capa went to the spill pool)
+    // the spill pool: the candidates that came after a list's capa entries, {rec, slot, key, spos} at index np * capa + q of the
+    // four fov_* arrays (a list ref and a pool ref never collide), their pyramid in pool_pyr[q]
+    int* pool_pyr;     // [pool]
     // readout scratch
     int* blk_cnt;      // [ceil(v_loc/256)+1]
     float* occ_xyz;    // [v_loc*3] (allocated on first use)

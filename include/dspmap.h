@@ -388,6 +388,9 @@ int dspmap_get_observations(dspmap_t* m, float* obs_out_host /* [NP][100][5] */,
 int dspmap_set_expected_newborn(dspmap_t* m, float v);
 /* particles registered per pyramid by the last prediction (size of each pyramids_in_fov list, :124) */
 int dspmap_get_pyramid_counts(dspmap_t* m, int* count_out_host /* [NP] */);
+/* particles the last prediction tried to register per pyramid, before the cut to SAFE_PARTICLE_NUM_PYRAMID (this rank's
+ * share on a sharded map): list length + the particles turned away (-2, :1256-1259) */
+int dspmap_get_pyramid_candidates(dspmap_t* m, int* count_out_host /* [NP] */);
 
 /* ---- multi-GPU split-phase frame (Z-slab sharding; the single-process reference has no
  * counterpart).  One process per GPU owns the voxel layers [z_lo, z_hi) (dspmap_config).  Every

@@ -50,6 +50,7 @@ struct dsp_oracle {
     float* particles;  /* [V][slots][9] */
     float* results;    /* [V][rdim]     */
     int* pyr_lists;    /* [np][capp][3] */
+    int* pyr_cand;     /* [np] particles that asked for a place in the list this prediction, those turned away included (test infrastructure) */
     int* neighbors;    /* [np][nbs]     */
     int nn, nbs;       /* neighbourhood radius, table stride */
     float occl_margin;
@@ -286,6 +287,7 @@ dsp_oracle* dspo_create(const dspo_config* cfg) {
     o->particles = (float*)calloc((size_t)o->V * o->slots * PSTRIDE, sizeof(float));
     o->results = (float*)calloc((size_t)o->V * o->rdim, sizeof(float));
     o->pyr_lists = (int*)calloc((size_t)o->np * o->capp * 3, sizeof(int));
+    o->pyr_cand = (int*)calloc((size_t)o->np, sizeof(int));
     o->neighbors = (int*)calloc((size_t)o->np * o->nbs, sizeof(int));
     o->obs = (float*)calloc((size_t)o->np * DSPO_OBS_MAX_PER_PYRAMID * 5, sizeof(float));
     o->obs_count = (int*)calloc((size_t)o->np, sizeof(int));
@@ -294,7 +296,7 @@ dsp_oracle* dspo_create(const dspo_config* cfg) {
     o->bp_ori_v = (float*)calloc((size_t)(o->np_v + 1) * 3, sizeof(float));
     o->bp_h = (float*)calloc((size_t)(o->np_h + 1) * 3, sizeof(float));
     o->bp_v = (float*)calloc((size_t)(o->np_v + 1) * 3, sizeof(float));
-    if (!o->particles || !o->results || !o->pyr_lists || !o->neighbors || !o->obs) {
+    if (!o->particles || !o->results || !o->pyr_lists || !o->pyr_cand || !o->neighbors || !o->obs) {
         dspo_destroy(o);
         return NULL;
     }
@@ -326,7 +328,7 @@ dsp_oracle* dspo_create(const dspo_config* cfg) {
 
 void dspo_destroy(dsp_oracle* o) {
     if (!o) return;
-    free(o->particles); free(o->results); free(o->pyr_lists); free(o->neighbors);
+    free(o->particles); free(o->results); free(o->pyr_lists); free(o->pyr_cand); free(o->neighbors);
     free(o->obs); free(o->obs_count); free(o->obs_maxlen);
     free(o->bp_ori_h); free(o->bp_ori_v); free(o->bp_h); free(o->bp_v);
     free(o->cloud_view); free(o->birth); free(o->last_clusters);
@@ -360,6 +362,7 @@ void dspo_get_cursors(const dsp_oracle* o, int* p, int* v, int* r) {
 float* dspo_particles(dsp_oracle* o) { return o->particles; }
 float* dspo_results(dsp_oracle* o) { return o->results; }
 int* dspo_pyramid_lists(dsp_oracle* o) { return o->pyr_lists; }
+int* dspo_pyramid_candidates(dsp_oracle* o) { return o->pyr_cand; }
 float* dspo_obs(dsp_oracle* o) { return o->obs; }
 int* dspo_obs_count(dsp_oracle* o) { return o->obs_count; }
 float* dspo_obs_max_length(dsp_oracle* o) { return o->obs_maxlen; }
@@ -520,6 +523,7 @@ static int move_particle(dsp_oracle* o, int new_voxel, int cur_voxel, int cur_sl
         int v = dspo_pyramid_v(o, r[4], r[5], r[6]);
         int b = h * o->np_v + v;
         int ok = 0;
+        o->pyr_cand[b] += 1;
         for (int j = 0; j < o->capp; j++) {
             int* e = PYR(o, b, j);
             if (e[0] == 0) {
@@ -547,6 +551,7 @@ void dspo_map_prediction(dsp_oracle* o, float odx, float ody, float odz, float d
     o->update_time += dt; /* :634-635 */
     o->update_counter += 1;
     for (size_t i = 0, n = (size_t)o->np * o->capp; i < n; i++) o->pyr_lists[i * 3] &= 0; /* :638-642 */
+    memset(o->pyr_cand, 0, sizeof(int) * (size_t)o->np);
     for (int v = 0; v < o->V; ++v) {
         for (int p = 0; p < o->slots; p++) {
             float* r = PART(o, v, p);

@@ -144,6 +144,7 @@ int dspo_inject(dsp_oracle* o, int n, const float* px, const float* py, const fl
 float* dspo_particles(dsp_oracle* o);       /* [V][SLOTS][9]  voxels_with_particle :116 */
 float* dspo_results(dsp_oracle* o);         /* [V][4+T]       voxels_objects_number :120 */
 int* dspo_pyramid_lists(dsp_oracle* o);     /* [NP][CAPP][3]  pyramids_in_fov :124 */
+int* dspo_pyramid_candidates(dsp_oracle* o); /* [NP]          particles the last prediction tried to register per pyramid, before the cut */
 float* dspo_obs(dsp_oracle* o);             /* [NP][100][5]   point_cloud :498 */
 int* dspo_obs_count(dsp_oracle* o);         /* [NP]           observation_num_each_pyramid :501 */
 float* dspo_obs_max_length(dsp_oracle* o);  /* [NP]           point_cloud_max_length :515 */

@@ -97,6 +97,7 @@ def _load(fast=False):
         "dspo_add_random_particles": (None, [P, i, f]),
         "dspo_inject": (i, [P, i, P, P, P, P, P, P, P, P, f]),
         "dspo_particles": (fp, [P]), "dspo_results": (fp, [P]), "dspo_pyramid_lists": (ip, [P]),
+        "dspo_pyramid_candidates": (ip, [P]),
         "dspo_obs": (fp, [P]), "dspo_obs_count": (ip, [P]), "dspo_obs_max_length": (fp, [P]),
         "dspo_expected_newborn": (f, [P]), "dspo_set_expected_newborn": (None, [P, f]),
         "dspo_set_occlusion_margin": (None, [P, f]),
@@ -221,6 +222,11 @@ class Oracle:
     @property
     def pyramid_lists(self):
         return self._view(self.L.dspo_pyramid_lists(self.h), (self.NP, self.capp, 3), np.int32)
+
+    @property
+    def pyramid_candidates(self):
+        """particles the last prediction tried to register per pyramid: list length + the ones turned away (-2, :1256-1259)"""
+        return self._view(self.L.dspo_pyramid_candidates(self.h), (self.NP,), np.int32)
 
     @property
     def obs(self):

@@ -67,3 +67,27 @@ def sorted_records(voxel, rec, cols=(4, 5, 6, 1, 2, 7)):
     keys = [rec[:, c] for c in reversed(cols)] + [voxel]
     order = np.lexsort(keys)
     return voxel[order], rec[order]
+
+
+def uniform_per_voxel(cfg, per_voxel, seed, vmax=0.0, wlo=0.01, whi=0.05):
+    """per_voxel particles in EVERY voxel of the map, uniform inside the voxel (away from its faces), with velocities in
+    [-vmax, vmax] (vz = 0): px,py,pz,vx,vy,w like random_particles.  Enough of them in the field of view overfill the
+    pyramid lists far past what a list holds before its cut."""
+    rng = np.random.default_rng(seed)
+    r = float(cfg.voxel_resolution)
+    hx, hy, hz = half_extent(cfg)
+    ix, iy, iz = np.meshgrid(np.arange(cfg.nx), np.arange(cfg.ny), np.arange(cfg.nz), indexing="ij")
+    ix, iy, iz = (np.repeat(a.ravel(), per_voxel) for a in (ix, iy, iz))
+    n = len(ix)
+    px = (-hx + (ix + rng.uniform(0.05, 0.95, n)) * r).astype(np.float32)
+    py = (-hy + (iy + rng.uniform(0.05, 0.95, n)) * r).astype(np.float32)
+    pz = (-hz + (iz + rng.uniform(0.05, 0.95, n)) * r).astype(np.float32)
+    vx = rng.uniform(-vmax, vmax, n).astype(np.float32)
+    vy = rng.uniform(-vmax, vmax, n).astype(np.float32)
+    w = rng.uniform(wlo, whi, n).astype(np.float32)
+    return px, py, pz, vx, vy, w
+
+
+def capa(capp):
+    """entries a pyramid list of the HIP map accepts before its cut (MapDims::capa)"""
+    return 2 * capp + 64

@@ -444,7 +444,7 @@ def test_split_placement_changes_nothing(dsp, est, quat):
         if est:
             m.set_param(dsp.capi.P_VELOCITY_ESTIMATOR, est)
         maps.append(m)
-    for m in maps:   # (sparse enough that no pyramid list exceeds its hard capacity: beyond it, arrival order decides)
+    for m in maps:   # (sparse: the lists stay short -- test_gpu_list_capacity.py covers lists far past their capacity)
         m.seed_uniform(2, 0.01, 11, 0.0)
     rng = np.random.default_rng(3)
     ys, zs = np.meshgrid(np.linspace(-2.0, 2.0, 41), np.linspace(-0.9, 0.9, 19))

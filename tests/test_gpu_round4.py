@@ -449,6 +449,14 @@ def test_alternating_sweep_direction_changes_nothing(dsp):
     k_predict the other way again: each sweep starts on the tiles still in the Infinity Cache, DSPMAP_P_SWEEP_ALTERNATE).  Forced
     on / off on a small map, split placement on, a moving sensor and moving particles: every slot, every float, every counter
     and the future status equal after every frame -- no stage depends on the order in which the tiles are visited"""
+    # (8 per voxel: the fullest pyramid lists overflow their capacity CAPP = 422 -- the cut and the re-slotting run -- and stay
+    # below the CAPA = 2 CAPP + 64 entries a list holds before the cut; test_gpu_list_capacity.py seeds past CAPA, where the
+    # candidates beyond it go through the spill pool)
+    _alternating_sweep(dsp, 8)
+
+
+def _alternating_sweep(dsp, per_voxel):
+    """the body of test_alternating_sweep_direction_changes_nothing; returns the number of pyramid lists past CAPA per frame"""
     cfg = dict(nx=56, ny=88, nz=12, res=0.15, ppv=24)
     tables = common.tables(5)
     maps = []
@@ -459,20 +467,19 @@ def test_alternating_sweep_direction_changes_nothing(dsp):
         m.set_param(dsp.capi.P_VELOCITY_ESTIMATOR, 2)
         m.set_param(dsp.capi.P_SWEEP_ALTERNATE, alt)
         m.set_param(dsp.capi.P_RESAMPLE_WG_TILES, 0)          # the one-wave-per-tile resampler (the four-wave one has no direction)
-        # (8 per voxel: the fullest pyramid lists overflow their capacity CAPP = 422 -- the cut and the re-slotting run -- but stay
-        # below the CAPA = 2 CAPP + 64 entries a list accepts before the cut: beyond that entries are dropped in ARRIVAL order,
-        # the one documented place where the order of the tiles can show, DESIGN.md "Numerics" (3))
-        m.seed_uniform(8, 0.01, 6, 0.8)
+        m.seed_uniform(per_voxel, 0.01, 6, 0.8)
         maps.append(m)
     rng = np.random.default_rng(3)
     ys, zs = np.meshgrid(np.linspace(-2.0, 2.0, 41), np.linspace(-0.7, 0.7, 15))
     base = np.stack([np.full(ys.size, 2.3) + 0.2 * np.sin(2 * ys.ravel()), ys.ravel(), zs.ravel()], 1).astype(np.float32)
+    past = []
     for f in range(9):
         t = f / 30.0
         pts = torch.from_numpy(base + rng.normal(0, 0.004, base.shape).astype(np.float32)).cuda()
         pos = (0.9 * t, 0.5 * t, 0.1 * np.sin(5 * t))
         for m in maps:
             assert m.update_device(pts.data_ptr(), len(base), pos, t, (0.9659258, 0.0, 0.0, 0.258819)) == 1
+        past.append(int((maps[0].pyramid_candidates() > common.capa(maps[0].capp)).sum()))
         cs = [m.counters() for m in maps]
         for c in cs:
             c.pop("update_ms")
@@ -486,16 +493,17 @@ def test_alternating_sweep_direction_changes_nothing(dsp):
         assert np.array_equal(maps[0].results(), m.results())
     for m in maps:
         m.close()
+    return past
 
 
-def _sharded_overfull(dsp, world, exact):
+def _sharded_overfull(dsp, world, exact, nx=80, per_voxel=10):
     """a saturated map whose sensor looks INTO it (identity attitude: dozens of pyramid lists are overfull in every frame, the cut
     and the re-slotting run), every particle moving, the sensor advancing and climbing (particles change slab): slabs vs unsharded"""
     import os
     sharded = __import__("dsp-map_amd.sharded", fromlist=["CppGroup"])
     # 12 m long: a pyramid reaches 6 m into the map and holds ~60 voxels -> 500 - 700 of the 10 particles per voxel, its list
-    # takes CAPP = 368 (and accepts CAPA = 800 before the cut, beyond which entries would be dropped in arrival order)
-    cfg = dict(nx=80, ny=40, nz=16, res=0.15, ppv=24)
+    # takes CAPP = 368 (and holds CAPA = 800 before the cut; test_gpu_list_capacity.py runs a 24 m map past that)
+    cfg = dict(nx=nx, ny=40, nz=16, res=0.15, ppv=24)
     tables = common.tables(9)
     os.environ["DSPMAP_SHARDED_EXACT_LISTS"] = "1" if exact else "0"
     try:
@@ -507,8 +515,9 @@ def _sharded_overfull(dsp, world, exact):
     for x in grp.maps + [full]:
         x.set_tables(*tables)
         x.set_param(dsp.capi.P_VELOCITY_ESTIMATOR, 2)
-        x.seed_uniform(10, weight=0.01, seed=99, vmax=1.0)
+        x.seed_uniform(per_voxel, weight=0.01, seed=99, vmax=1.0)
     pts = common.wall_cloud(3, n_side=40, dist=4.2, half_w=1.8, half_h=0.6)
+    capa = common.capa(full.capp)
     d = torch.from_numpy(pts).cuda()
     stats = []
     same = True
@@ -519,7 +528,8 @@ def _sharded_overfull(dsp, world, exact):
         grp.sync()
         c = full.counters()
         stats.append((c["n_pyramid_full"], c["n_reslotted"], c["n_overflow_inexact"], c["n_moved"],
-                      sum(x.counters()["n_exported_up"] + x.counters()["n_exported_down"] for x in grp.maps)))
+                      sum(x.counters()["n_exported_up"] + x.counters()["n_exported_down"] for x in grp.maps),
+                      int((full.pyramid_candidates() > capa).sum()), max(int((x.pyramid_candidates() > capa).sum()) for x in grp.maps)))
         fut_s = np.concatenate([x.getFutureStatus() for x in grp.maps], 0)
         same = same and np.array_equal(fut_s, full.getFutureStatus())
         same = same and sum(x.counters()["n_pyramid_full"] for x in grp.maps) == c["n_pyramid_full"]

@@ -428,3 +428,33 @@ def test_strict_and_fastmath_builds_of_the_oracle_span_an_envelope(orc):
                 assert row["strict_vs_fast"]["mass_rel"] < 5e-3 and row["strict_vs_fast"]["jaccard"] >= 0.97, (scene, fr, row)
             b = envelope.bars(row, fr == checks[0])
             assert b["mass_rel"] >= envelope.STATED["mass"] and b["jaccard"] <= 0.999
+
+
+# the maps of tests/test_gpu_list_capacity.py (and of the round-4 helpers it runs past CAPA): (map, particles per voxel).  The
+# alternating-sweep map is seeded on the device; the same density uniform in every voxel stands for it here
+LIST_CAPACITY_MAPS = [
+    (dict(nx=160, ny=40, nz=16, res=0.15, ppv=24, angle=3), 12, (1, 0, 0, 0)),   # stages, whole frames, identical maps, sharded
+    (dict(nx=160, ny=40, nz=16, res=0.15, ppv=24, angle=1), 12, (1, 0, 0, 0)),   # stages: k_predict's batch_append registration
+    (dict(nx=56, ny=88, nz=12, res=0.15, ppv=24, angle=3), 20, (0.9659258, 0.0, 0.0, 0.258819)),   # alternating sweep directions
+]
+
+
+@pytest.mark.parametrize("k", range(len(LIST_CAPACITY_MAPS)))
+def test_list_capacity_maps_put_many_lists_past_capa(orc, k):
+    """the GPU tests of lists past CAPA = 2 CAPP + 64 (the entries a HIP list holds before its cut) must stay in that regime: with
+    nobody moving, the oracle's first prediction puts more than CAPA candidates into at least 20 lists, and the candidates it
+    counts are the list lengths plus the particles it turned away"""
+    cfg, per_voxel, quat = LIST_CAPACITY_MAPS[k]
+    o = orc.Oracle(orc.make_config(**cfg))
+    px, py, pz, vx, vy, w = common.uniform_per_voxel(o.cfg, per_voxel, 5)
+    z = np.zeros(len(px), np.float32)
+    assert o.inject(px, py, pz, z, z, z, w, 1.0) == len(px)
+    o.bin_points(np.zeros((0, 3), np.float32), quat)
+    live = o.L.dspo_count_live(o.h)
+    o.predict(0.0, 0.0, 0.0, 0.0)
+    cand = o.pyramid_candidates.copy()
+    lens = (o.pyramid_lists[:, :, 0] != 0).sum(1)
+    assert np.array_equal(lens, np.minimum(cand, o.capp))
+    assert live - o.L.dspo_count_live(o.h) == int(np.maximum(cand - o.capp, 0).sum())
+    assert (cand > common.capa(o.capp)).sum() >= 20, ((cand > common.capa(o.capp)).sum(), cand.max(), common.capa(o.capp))
+    o.close()
