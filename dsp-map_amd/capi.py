@@ -52,6 +52,9 @@ class Counters(C.Structure):
 
 VPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"),
                          ("nx", "f4"), ("ny", "f4"), ("nz", "f4"), ("intensity", "f4")])
+# dspmap_risk: one per trajectory (dspmap_trajectory_risk)
+RISK_DTYPE = np.dtype([("sum", "f4"), ("max", "f4"), ("first_over", "i4"), ("n_outside", "i4")])
+QUERY_WORLD = 1   # DSPMAP_QUERY_WORLD
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -65,6 +68,7 @@ SIGNATURES = {
     "dspmap_last_error": (C.c_char_p, [_P]),
     "dspmap_sync": (_i, [_P]),
     "dspmap_set_stream": (_i, [_P, _P]),
+    "dspmap_get_stream": (_P, [_P]),
     "dspmap_set_param": (_i, [_P, _i, _d]),
     "dspmap_get_param": (_d, [_P, _i]),
     "dspmap_set_gaussian_tables": (_i, [_P, _P, _P, _i]),
@@ -82,6 +86,10 @@ SIGNATURES = {
     "dspmap_get_results": (_i, [_P, _P]),
     "dspmap_results_device": (_P, [_P]),
     "dspmap_future_device": (_P, [_P]),
+    "dspmap_query_occupancy": (_i, [_P, _i, _P, _f, _i, _f, _P]),
+    "dspmap_query_occupancy_device": (_i, [_P, _i, _P, _f, _i, _f, _P]),
+    "dspmap_trajectory_risk": (_i, [_P, _i, _i, _P, _f, _i, _f, _f, _P]),
+    "dspmap_trajectory_risk_device": (_i, [_P, _i, _i, _P, _f, _i, _f, _f, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -395,6 +403,87 @@ class DSPMap:
         """[V_local, 4]: occupancy mass, mean vx, vy, vz (voxels_objects_number[v][0..3])."""
         out = np.zeros((self.V_local, 4), np.float32)
         self._chk(self.L.dspmap_get_results(self.h, _ptr(out)))
+        return out
+
+    # -- point / trajectory queries (extension; semantics in include/dspmap.h next to dspmap_query_occupancy)
+    @staticmethod
+    def _is_device_tensor(a):
+        return type(a).__module__.startswith("torch") and getattr(a, "is_cuda", False)
+
+    @staticmethod
+    def _device_samples(q, shape_tail, what):
+        import torch
+        if q.dtype != torch.float32 or tuple(q.shape[-len(shape_tail):]) != shape_tail:
+            raise ValueError("%s: a float32 tensor of shape %s" % (what, "[..., " + ", ".join(map(str, shape_tail)) + "]"))
+        return q.contiguous()
+
+    def _handle_stream_order(self, dev):
+        """(before, after) for a device call: when the handle queues on a stream other than torch's current one, `before` makes the
+        handle's stream wait for the work torch has queued so far (the samples), `after` makes torch's stream wait for the query.
+        So the result is ordered for torch's consumers, and the samples (also a temporary made by .contiguous()) and the output,
+        allocated on torch's stream, are not handed out again by the caching allocator before the handle has used them.  Both waits
+        are queued at once (no reference to the handle's stream outlives the call); no host synchronisation."""
+        import torch
+        cur = torch.cuda.current_stream(dev)
+        s = self.L.dspmap_get_stream(self.h) or 0
+        if s == cur.cuda_stream:
+            return (lambda: None), (lambda: None)
+        ext = torch.cuda.ExternalStream(s, device=dev)
+        return (lambda: ext.wait_stream(cur)), (lambda: cur.wait_stream(ext))
+
+    def query_occupancy(self, q, radius=0.0, world=False, outside=1.0):
+        """value of every sample {x, y, z, t} of q ([n, 4] float32): the maximum over the own voxel and the voxel centres within
+        `radius` of the current mass (t < 0) or of the future status at the first horizon >= t, `outside` for what lies outside
+        the map.  A numpy array goes through the host entry point (synchronous) and returns numpy; a torch tensor on the GPU goes
+        through the device entry point: the result is a tensor on the same device, enqueued on the handle's stream and ordered
+        with torch's current stream both ways (no host synchronisation; none needed when the handle is on torch's stream)."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(q):
+            import torch
+            q = self._device_samples(q, (4,), "query_occupancy")
+            n = q.numel() // 4
+            out = torch.empty(n, dtype=torch.float32, device=q.device)
+            self._chk(self.L.dspmap_init_device(self.h))   # (the handle's stream exists from here on)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_query_occupancy_device(self.h, n, q.data_ptr(), float(radius), flags, float(outside), out.data_ptr()))
+            after()
+            return out
+        q = np.ascontiguousarray(q, np.float32)
+        if q.shape[-1:] != (4,):
+            raise ValueError("query_occupancy: samples of shape [n, 4]")
+        n = q.size // 4
+        out = np.zeros(n, np.float32)
+        self._chk(self.L.dspmap_query_occupancy(self.h, n, _ptr(q), float(radius), flags, float(outside), _ptr(out)))
+        return out
+
+    def trajectory_risk(self, samples, radius=0.0, world=False, outside=1.0, threshold=0.5):
+        """per trajectory of samples ([K, S, 4] float32, trajectory-major): sequential fp32 sum, max, first sample > threshold (-1:
+        none) and the samples outside the map of the values query_occupancy gives.  numpy in -> structured numpy (RISK_DTYPE) out
+        (synchronous); a torch tensor on the GPU -> dict of tensors 'sum', 'max' (float32), 'first_over', 'n_outside' (int32) on the
+        same device, enqueued on the handle's stream."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(samples):
+            import torch
+            q = self._device_samples(samples, (4,), "trajectory_risk")
+            if q.dim() != 3:
+                raise ValueError("trajectory_risk: samples of shape [K, S, 4]")
+            k, s = int(q.shape[0]), int(q.shape[1])
+            raw = torch.empty((k, 4), dtype=torch.int32, device=q.device)
+            self._chk(self.L.dspmap_init_device(self.h))
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_trajectory_risk_device(self.h, k, s, q.data_ptr(), float(radius), flags, float(outside),
+                                                           float(threshold), raw.data_ptr()))
+            after()
+            return {"sum": raw[:, 0].view(torch.float32), "max": raw[:, 1].view(torch.float32),
+                    "first_over": raw[:, 2], "n_outside": raw[:, 3]}
+        q = np.ascontiguousarray(samples, np.float32)
+        if q.ndim != 3 or q.shape[2] != 4:
+            raise ValueError("trajectory_risk: samples of shape [K, S, 4]")
+        k, s = q.shape[0], q.shape[1]
+        out = np.zeros(k, RISK_DTYPE)
+        self._chk(self.L.dspmap_trajectory_risk(self.h, k, s, _ptr(q), float(radius), flags, float(outside), float(threshold), _ptr(out)))
         return out
 
     def getVoxelPositionFromIndexPublic(self, index):

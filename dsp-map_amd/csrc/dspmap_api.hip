@@ -226,6 +226,7 @@ static void free_dev(dspmap* m) {
                       m->ve.v_rot, m->ve.v_pyr, m->ve.v_fpar};
         for (void* q : vp) if (q) chk(hipFree(q), "hipFree");
     }
+    if (m->q_buf) { chk(hipFree(m->q_buf), "hipFree"); m->q_buf = nullptr; m->q_buf_bytes = 0; }
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
@@ -581,6 +582,7 @@ extern "C" int dspmap_set_stream(dspmap_t* m, void* hip_stream) {
     m->graph_epoch++;
     return DSPMAP_OK;
 }
+extern "C" void* dspmap_get_stream(const dspmap_t* m) { return m ? (void*)m->stream : nullptr; }
 
 // ------------------------------------------------------------------ setters
 extern "C" int dspmap_set_param(dspmap_t* m, int key, double v) {
@@ -1601,6 +1603,122 @@ extern "C" const float* dspmap_future_device(dspmap_t* m) {
     LaunchCtx c = dspmap_ctx_of(m);
     launch_future_combine(c);  // [V][T] view of the horizon-major accumulators + the static-particle mass
     return m->s.fut_out;
+}
+
+// --------------------------------------------------- point / trajectory queries (dspmap_query.hip; semantics in include/dspmap.h)
+static size_t q_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// the handle's query staging: at least `bytes`; grown only after the stream has drained (an earlier query may still use it)
+static int query_buf(dspmap* m, size_t bytes) {
+    if (bytes <= m->q_buf_bytes) return DSPMAP_OK;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    if (m->q_buf) { HIPCHK(m, hipFree(m->q_buf)); m->q_buf = nullptr; m->q_buf_bytes = 0; }
+    const size_t cap = bytes + bytes / 2;
+    HIPCHK(m, hipMalloc(&m->q_buf, cap));
+    m->q_buf_bytes = cap;
+    return DSPMAP_OK;
+}
+// argument checks of every query entry point: before READY, so that they hold without a device
+static int query_check(dspmap* m, long long n, const void* in, const void* out, float r, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "query: negative sample count %lld", n);
+    if (n > 0 && (!in || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "query: NULL sample or output array");
+    if (!(r >= 0.f && r <= 8.f * m->d.res)) return dspmap_fail(m, DSPMAP_E_ARG, "query: radius %g outside [0, 8 * voxel_resolution]", (double)r);
+    if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "query: unknown flags 0x%x", flags);
+    if (outside != outside) return dspmap_fail(m, DSPMAP_E_ARG, "query: outside_value is NaN");
+    return DSPMAP_OK;
+}
+static QueryArgs query_args(const dspmap* m, float r, int flags, float outside) {
+    const MapDims& d = m->d;
+    QueryArgs a;
+    a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a.ox = m->cur_pos[0]; a.oy = m->cur_pos[1]; a.oz = m->cur_pos[2];
+    a.r2 = r * r;
+    a.K = r > 0.f ? (int)ceilf(r / d.res) + 1 : 0;   // (a superset of the footprint: one lattice step of margin for the rounding)
+    a.outside = outside;
+    a.fut_zero = m->fut_clear_pending ? 1 : 0;       // read, never changed: the clear stays with the next frame / reader
+    a.cx = -d.half_x + d.res * 0.5f; a.cy = -d.half_y + d.res * 0.5f; a.cz = -d.half_z + d.res * 0.5f;   // dspmap_voxel_center
+    return a;
+}
+static int risk_check(dspmap* m, int n_traj, int n_samples, const void* in, const void* out, float r, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n_traj < 0) return dspmap_fail(m, DSPMAP_E_ARG, "trajectory risk: negative trajectory count %d", n_traj);
+    if (n_traj > 0 && n_samples <= 0) return dspmap_fail(m, DSPMAP_E_ARG, "trajectory risk: %d samples per trajectory", n_samples);
+    const long long n = (long long)n_traj * (n_traj > 0 ? n_samples : 0);
+    if (n > 0x7fffffffll) return dspmap_fail(m, DSPMAP_E_ARG, "trajectory risk: %d x %d samples exceed INT_MAX", n_traj, n_samples);
+    const int rc = query_check(m, n, in, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "trajectory risk: a slab handle holds part of the map; query every slab and merge with max");
+    return DSPMAP_OK;
+}
+
+extern "C" int dspmap_query_occupancy(dspmap_t* m, int n, const dspmap_query* q, float r, int flags, float outside, float* out) {
+    int rc = query_check(m, n, q, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n == 0) return DSPMAP_OK;
+    const size_t qb = q_align(sizeof(dspmap_query) * (size_t)n);
+    if ((rc = query_buf(m, qb + sizeof(float) * (size_t)n)) != DSPMAP_OK) return rc;
+    float4* dq = (float4*)m->q_buf;
+    float* dout = (float*)((char*)m->q_buf + qb);
+    HIPCHK(m, hipMemcpyAsync(dq, q, sizeof(dspmap_query) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    launch_query(dspmap_ctx_of(m), query_args(m, r, flags, outside), n, dq, dout, nullptr);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(out, dout, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_occupancy_device(dspmap_t* m, int n, const dspmap_query* q, float r, int flags, float outside, float* out) {
+    const int rc = query_check(m, n, q, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    launch_query(dspmap_ctx_of(m), query_args(m, r, flags, outside), n, (const float4*)q, out, nullptr);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+// values + flags of the n_traj x n_samples samples in the staging buffer at `vals`, then one dspmap_risk per trajectory into `out`
+static int risk_enqueue(dspmap* m, int n_traj, int n_samples, const float4* dq, float* vals, float r, int flags, float outside,
+                        float thr, dspmap_risk* out) {
+    const int n = n_traj * n_samples;
+    const LaunchCtx c = dspmap_ctx_of(m);
+    unsigned char* fl = (unsigned char*)((char*)vals + q_align(sizeof(float) * (size_t)n));
+    launch_query(c, query_args(m, r, flags, outside), n, dq, vals, fl);
+    launch_risk_reduce(c, n_traj, n_samples, vals, fl, thr, out);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+static size_t risk_scratch_bytes(long long n) { return q_align(sizeof(float) * (size_t)n) + q_align((size_t)n); }
+extern "C" int dspmap_trajectory_risk(dspmap_t* m, int n_traj, int n_samples, const dspmap_query* q, float r, int flags, float outside,
+                                      float thr, dspmap_risk* out) {
+    int rc = risk_check(m, n_traj, n_samples, q, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n_traj == 0) return DSPMAP_OK;
+    const int n = n_traj * n_samples;
+    const size_t qb = q_align(sizeof(dspmap_query) * (size_t)n), sb = risk_scratch_bytes(n);
+    if ((rc = query_buf(m, qb + sb + sizeof(dspmap_risk) * (size_t)n_traj)) != DSPMAP_OK) return rc;
+    float4* dq = (float4*)m->q_buf;
+    float* vals = (float*)((char*)m->q_buf + qb);
+    dspmap_risk* dout = (dspmap_risk*)((char*)m->q_buf + qb + sb);
+    HIPCHK(m, hipMemcpyAsync(dq, q, sizeof(dspmap_query) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    if ((rc = risk_enqueue(m, n_traj, n_samples, dq, vals, r, flags, outside, thr, dout)) != DSPMAP_OK) return rc;
+    HIPCHK(m, hipMemcpyAsync(out, dout, sizeof(dspmap_risk) * (size_t)n_traj, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_trajectory_risk_device(dspmap_t* m, int n_traj, int n_samples, const dspmap_query* q, float r, int flags,
+                                             float outside, float thr, dspmap_risk* out) {
+    int rc = risk_check(m, n_traj, n_samples, q, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n_traj == 0) return DSPMAP_OK;
+    const int n = n_traj * n_samples;
+    if ((rc = query_buf(m, risk_scratch_bytes(n))) != DSPMAP_OK) return rc;
+    return risk_enqueue(m, n_traj, n_samples, (const float4*)q, (float*)m->q_buf, r, flags, outside, thr, out);
 }
 
 extern "C" void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz) {  // :1556-1572

@@ -333,6 +333,11 @@ __device__ __forceinline__ float ck_from_fix(long long v) { return (float)((doub
 __device__ __forceinline__ u64 fut_quantum(float w) { return (u64)__float2ull_rn(w * FUT_FIX_SCALE); }   // (NaN / negative -> 0)
 __device__ __forceinline__ void fut_add(u64* cell, u64 q) { __hip_atomic_fetch_add(cell, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float fut_value(u64 q) { return (float)((double)q * FUT_FIX_INV); }
+// voxels_objects_number[v][4 + k] of storage voxel lv: what k_future_combine writes and what a query (dspmap_query.hip) reads in place --
+// ONE expression, so that the two can never differ by a bit
+__device__ __forceinline__ float fut_status_at(const MapDims& d, const DevState& s, int lv, int k) {
+    return fut_value(s.fut[(size_t)k * d.v_loc + lv]) + s.fut_stat[lv];
+}
 
 // entries of pyramid b's range-sorted particle list (what the pair kernels read): the list as registered, cut to the reference's
 // capacity -- on a sharded map in a frame with a global cut, what THIS rank keeps of it

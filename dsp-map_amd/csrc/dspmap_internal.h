@@ -171,6 +171,9 @@ struct dspmap {
     int* mgpu_count = nullptr;
     BirthSrc* mgpu_birth = nullptr;
     int last_exp[2] = {0, 0};   // particles exported down / up in the last frame
+    // point / trajectory queries (dspmap_query_occupancy*, dspmap_trajectory_risk*): device staging of the host variants' samples and
+    // results and of the risk's per-sample values; grown on demand (after the stream has drained), freed with the device state
+    void* q_buf = nullptr; size_t q_buf_bytes = 0;
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;

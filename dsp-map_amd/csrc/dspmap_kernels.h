@@ -131,6 +131,22 @@ void launch_occupied_compact(const LaunchCtx& c, float thr);
 void launch_clear_future(const LaunchCtx& c);
 void launch_future_combine(const LaunchCtx& c);  // fold the static-particle future mass into the [V][T] grid
 void launch_results_true(const LaunchCtx& c, float4* out);   // res4 (storage order) -> the reference's voxel order
+// point / trajectory queries (dspmap_query.hip; semantics in include/dspmap.h, dspmap_query_occupancy)
+struct QueryArgs {
+    float ox, oy, oz;    // subtracted from every sample when `world` is set: the sensor position of the last update (current_position :131)
+    int world;
+    float r2;            // fl(r * r)
+    int K;               // lattice steps either side of a sample's own lattice cell the candidate box spans; 0 = the own voxel only (r == 0)
+    float outside;       // what a lattice point outside the map, a point outside it or a NaN input contributes
+    int fut_zero;        // 1: a clear of the future accumulators is pending -- t >= 0 reads 0
+    float cx, cy, cz;    // -half + res / 2 per axis: the voxel centre of index i is fl(fl(i * res) + c) (dspmap_voxel_center)
+};
+struct dspmap_risk;
+// out[i] = the value of sample q[i]; out_flag (optional) = 1 where the point is outside the map or an input is NaN
+void launch_query(const LaunchCtx& c, const QueryArgs& a, int n, const float4* q, float* out, unsigned char* out_flag);
+// per trajectory of n_samples consecutive values: sequential fp32 sum, max, first value > threshold, flagged samples
+void launch_risk_reduce(const LaunchCtx& c, int n_traj, int n_samples, const float* v, const unsigned char* flag, float threshold,
+                        struct dspmap_risk* out);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

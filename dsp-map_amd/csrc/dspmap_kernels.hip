@@ -1815,8 +1815,7 @@ __global__ void k_future_combine(MapDims d, DevState s) {
     const int tv = blockIdx.x * blockDim.x + threadIdx.x;
     if (tv >= d.v_true) return;
     const int lv = lv_of_true(d, tv);
-    const float st = s.fut_stat[lv];
-    for (int t = 0; t < d.T; ++t) s.fut_out[(size_t)tv * d.T + t] = fut_value(s.fut[(size_t)t * d.v_loc + lv]) + st;
+    for (int t = 0; t < d.T; ++t) s.fut_out[(size_t)tv * d.T + t] = fut_status_at(d, s, lv, t);
 }
 void launch_future_combine(const LaunchCtx& c) {
     hipLaunchKernelGGL(k_future_combine, dim3((c.d.v_true + 255) / 256), dim3(256), 0, c.stream, c.d, c.s);

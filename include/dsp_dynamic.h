@@ -231,6 +231,18 @@ public:
     }
     /* north-star name: the V x T future occupancy masses (then cleared, like the getters above) */
     void getFutureStatus(float* future_status) { sync_params(); dspmap_get_future(h_, future_status + (size_t)dspmap_local_voxel_base(h_) * PREDICTION_TIMES); }
+    /* extensions: read-only point / trajectory queries on the device (dspmap_query_occupancy / dspmap_trajectory_risk in dspmap.h):
+     * values[i] = predicted occupancy around samples[i] = {x, y, z, t} within `radius` (t < 0: current mass, else the first
+     * horizon >= t); no whole-grid copy, nothing cleared.  Return DSPMAP_OK or a negative dspmap.h error code. */
+    int queryOccupancy(int n, const dspmap_query* samples, float* values, float radius = 0.f, bool world_frame = false,
+                       float outside_value = 1.f) {
+        return dspmap_query_occupancy(h_, n, samples, radius, world_frame ? DSPMAP_QUERY_WORLD : 0, outside_value, values);
+    }
+    int evaluateTrajectories(int n_traj, int n_samples, const dspmap_query* samples, dspmap_risk* risk, float radius = 0.f,
+                             bool world_frame = false, float outside_value = 1.f, const float threshold = 0.7) {
+        return dspmap_trajectory_risk(h_, n_traj, n_samples, samples, radius, world_frame ? DSPMAP_QUERY_WORLD : 0, outside_value,
+                                      threshold, risk);
+    }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

@@ -212,6 +212,8 @@ int dspmap_init_device(dspmap_t* m);                      /* allocate device sta
 const char* dspmap_last_error(const dspmap_t* m);
 int dspmap_sync(dspmap_t* m);                             /* wait for all queued work of this handle */
 int dspmap_set_stream(dspmap_t* m, void* hip_stream);     /* run on a caller-owned hipStream_t (e.g. torch's) */
+void* dspmap_get_stream(const dspmap_t* m);               /* the hipStream_t the handle queues on (NULL before its device state exists
+                                                             unless one was set): what a caller orders its own streams / allocator with */
 
 /* ---- setters: dsp_dynamic.h:355-382 ---- */
 int dspmap_set_param(dspmap_t* m, int key, double value);
@@ -268,6 +270,56 @@ int dspmap_get_results(dspmap_t* m, float* out_host);
 /* device-resident views for callers that keep the map on the GPU (no copy) */
 const float* dspmap_results_device(dspmap_t* m); /* [V_local][4] */
 const float* dspmap_future_device(dspmap_t* m);  /* [V_local][T] */
+
+/* ---- point and trajectory queries (no counterpart in the reference; a planner's question "what is predicted around these
+ * points at these times?" answered on the device without the whole-grid copy above).  READ-ONLY: a query never clears the future
+ * accumulators and never arms the clear that getOccupancyMap* leave behind (:397-400, :420-424); a later dspmap_get_future of the same
+ * frame returns the same grid, and no later frame computes anything differently.
+ *
+ * A sample is {x, y, z, t} (16 bytes).  Its value:
+ *  - frame: x, y, z are in the map frame (relative to the map centre, like dspmap_voxel_center and the occupancy cloud); with
+ *    flags & DSPMAP_QUERY_WORLD they are world coordinates and each axis is first reduced p = fl(q - cur_pos), cur_pos = the sensor
+ *    position of the last update (or dspmap_set_current_position).
+ *  - which value: t < 0 reads the current mass voxels_objects_number[v][0] (dspmap_get_results column 0); t >= 0 reads the future
+ *    status at horizon k(t) = the smallest k with prediction_future_time[k] >= t, clamped to T - 1: bit for bit the [v][k] entry of
+ *    dspmap_get_future -- or 0 while a clear is pending (after a consuming readout or dspmap_clear_future), as the reference's zeroed
+ *    cells would read.  A map with T == 0 reads the current mass for every t.
+ *  - footprint: the MAXIMUM of (a) the own voxel's value if the point is inside the map (dspmap_point_voxel_index's voxel), and
+ *    (b) the value of every voxel-centre lattice point (ix, iy, iz) with d2 <= fl(r * r), where the centre c is dspmap_voxel_center's
+ *    fl(fl((float)i * res) + (-half + res / 2)) per axis (extended to indices outside the map), d = fl(c - p) per axis and
+ *    d2 = fl(fl(fl(dx * dx) + fl(dy * dy)) + fl(dz * dz)).  A lattice point outside [0, nx) x [0, ny) x [0, nz) contributes
+ *    `outside_value`, and so does a point outside the map.  A sample with a NaN coordinate or t has the value `outside_value`.
+ *    r == 0: the own voxel, or `outside_value`.  0 <= r <= 8 * voxel_resolution, anything else is DSPMAP_E_ARG.
+ *  - sharded handles (slab [z_lo, z_hi)): only voxels of the handle's slab contribute a mass; the outside contributions apply on
+ *    every slab; a sample with no contribution on this slab reads -inf.  The elementwise max of all slabs' outputs is the unsharded
+ *    map's output.
+ * Arguments are checked before the device is touched: a NULL handle, n < 0, a NULL array with n > 0, a bad r, unknown flags or a
+ * NaN outside_value are DSPMAP_E_ARG; without a usable device a valid call is DSPMAP_E_DEVICE.  Work is queued on the handle's
+ * stream behind everything queued there before (the last frame included); the captured frame is not touched. */
+#define DSPMAP_QUERY_WORLD 1
+typedef struct dspmap_query {
+    float x, y, z, t;
+} dspmap_query;
+typedef struct dspmap_risk {
+    float sum;        /* fp32 sum of the trajectory's sample values, taken sequentially in sample order */
+    float max;        /* their maximum */
+    int first_over;   /* first sample whose value is > threshold (getOccupancyMap's comparison, :394), -1 if none */
+    int n_outside;    /* samples whose point is outside the map or that have a NaN coordinate or t */
+} dspmap_risk;
+/* out_host[i] = value of q_host[i]; synchronous */
+int dspmap_query_occupancy(dspmap_t* m, int n, const dspmap_query* q_host, float radius, int flags, float outside_value,
+                           float* out_host);
+/* the same on device arrays (q_dev: n x 16 B, out_dev: n floats); enqueued on the handle's stream, no synchronisation */
+int dspmap_query_occupancy_device(dspmap_t* m, int n, const dspmap_query* q_dev, float radius, int flags, float outside_value,
+                                  float* out_dev);
+/* n_traj trajectories of n_samples samples each, trajectory-major (q[t * n_samples + j]) -> one dspmap_risk per trajectory from the
+ * values above.  n_samples <= 0 with n_traj > 0, or more than INT_MAX samples in all, is DSPMAP_E_ARG; a sharded handle is
+ * DSPMAP_E_STATE (a trajectory's sum needs every slab).  Synchronous */
+int dspmap_trajectory_risk(dspmap_t* m, int n_traj, int n_samples, const dspmap_query* q_host, float radius, int flags,
+                           float outside_value, float threshold, dspmap_risk* out_host);
+/* the same on device arrays; enqueued on the handle's stream, no synchronisation */
+int dspmap_trajectory_risk_device(dspmap_t* m, int n_traj, int n_samples, const dspmap_query* q_dev, float radius, int flags,
+                                  float outside_value, float threshold, dspmap_risk* out_dev);
 
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
