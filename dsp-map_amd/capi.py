@@ -50,6 +50,31 @@ class Counters(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Camera(C.Structure):
+    """dspmap_camera: the depth image's layout, the pinhole intrinsics and which pixels are used (include/dspmap.h)"""
+    _fields_ = [
+        ("width", C.c_int), ("height", C.c_int),
+        ("row_stride_bytes", C.c_int),
+        ("format", C.c_int),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("depth_scale", C.c_float),
+        ("min_depth", C.c_float), ("max_depth", C.c_float),
+        ("pixel_step", C.c_int),
+    ]
+
+
+DEPTH_U16, DEPTH_F32 = 0, 1   # DSPMAP_DEPTH_*
+
+
+def make_camera(width, height, fx, fy, cx, cy, depth_scale=0.001, min_depth=0.0, max_depth=20.0, fmt=DEPTH_U16, row_stride_bytes=0,
+                pixel_step=1):
+    c = Camera()
+    c.width, c.height, c.row_stride_bytes, c.format = width, height, row_stride_bytes, fmt
+    c.fx, c.fy, c.cx, c.cy = fx, fy, cx, cy
+    c.depth_scale, c.min_depth, c.max_depth, c.pixel_step = depth_scale, min_depth, max_depth, pixel_step
+    return c
+
+
 VPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"),
                          ("nx", "f4"), ("ny", "f4"), ("nz", "f4"), ("intensity", "f4")])
 # dspmap_risk: one per trajectory (dspmap_trajectory_risk)
@@ -121,6 +146,9 @@ SIGNATURES = {
     "dspmap_save_checkpoint": (_i, [_P, C.c_char_p]),
     "dspmap_load_checkpoint": (_i, [_P, C.c_char_p]),
     "dspmap_preprocess_cloud": (_i, [_P, _i, _P, _i, _f, _i, _i, _P, _ip, _ip]),
+    "dspmap_preprocess_depth": (_i, [_P, C.POINTER(Camera), _P, _f, _i, _P, _ip, _ip, _ip]),
+    "dspmap_update_depth_device": (_i, [_P, C.POINTER(Camera), _P, _f, _i, _P, _d, _P]),
+    "dspmap_update_depth": (_i, [_P, C.POINTER(Camera), _P, _f, _i, _P, _d, _P]),
     "dspmap_add_random_particles": (_i, [_P, _i, _f]),
     "dspmap_seed_uniform_moving": (_i, [_P, _i, _f, C.c_uint, _f]),
     "dspmap_seed_uniform": (_i, [_P, _i, _f, C.c_uint]),
@@ -563,6 +591,72 @@ class DSPMap:
         self._chk(self.L.dspmap_preprocess_cloud(self.h, n, points_ptr, stride, leaf, 1 if swap_axes else 0, max_points,
                                                  out_ptr, C.byref(n_out), C.byref(n_leaves)))
         return n_out.value, n_leaves.value
+
+    # -- depth images (include/dspmap.h next to dspmap_preprocess_depth)
+    @staticmethod
+    def _host_image(cam, depth):
+        """a numpy image laid out as `cam` says: dtype from the format, rows cam.row_stride_bytes apart (0 = packed)"""
+        dt = np.uint16 if cam.format == DEPTH_U16 else np.float32
+        depth = np.asarray(depth)
+        if depth.dtype != dt:
+            raise ValueError("depth image: dtype %s for format %d" % (depth.dtype, cam.format))
+        if cam.row_stride_bytes == 0:
+            depth = np.ascontiguousarray(depth)
+            if depth.size != cam.width * cam.height:
+                raise ValueError("depth image: %d pixels for a %d x %d camera" % (depth.size, cam.width, cam.height))
+        else:
+            need = cam.row_stride_bytes * (cam.height - 1) + cam.width * depth.itemsize
+            if not depth.flags["C_CONTIGUOUS"] or depth.nbytes < need:
+                raise ValueError("depth image: a C-contiguous buffer of at least %d bytes for this row stride" % need)
+        return depth
+
+    def _device_image(self, cam, depth):
+        import torch
+        ok = (torch.int16, getattr(torch, "uint16", torch.int16)) if cam.format == DEPTH_U16 else (torch.float32,)
+        if depth.dtype not in ok:
+            raise ValueError("depth image: dtype %s for format %d" % (depth.dtype, cam.format))
+        depth = depth.contiguous()
+        row = cam.row_stride_bytes or cam.width * depth.element_size()
+        if depth.numel() * depth.element_size() < row * (cam.height - 1) + cam.width * depth.element_size():
+            raise ValueError("depth image: too few bytes for a %d x %d camera" % (cam.width, cam.height))
+        return depth
+
+    def preprocess_depth(self, cam, depth, max_points=5000, leaf=0.1):
+        """depth image (torch tensor on the GPU: uint16 / int16 bits for DEPTH_U16, float32 for DEPTH_F32) -> (filtered cloud as an
+        [n, 3] float32 tensor on the same device, occupied leaves touching the map box, pixels that passed the validity and range
+        test).  Back-projection, voxel-grid centroid filter, axis swap, crop and cap in one pass on the device; synchronous."""
+        import torch
+        if not self._is_device_tensor(depth):
+            raise ValueError("preprocess_depth: a torch tensor on the GPU (update_depth takes host images)")
+        depth = self._device_image(cam, depth)
+        out = torch.empty((max(int(max_points), 0), 3), dtype=torch.float32, device=depth.device)
+        n_out, n_leaves, n_valid = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.L.dspmap_init_device(self.h))
+        before, after = self._handle_stream_order(depth.device)
+        before()
+        self._chk(self.L.dspmap_preprocess_depth(self.h, C.byref(cam), depth.data_ptr(), float(leaf), int(max_points),
+                                                 out.data_ptr() if max_points > 0 else None, C.byref(n_out), C.byref(n_leaves),
+                                                 C.byref(n_valid)))
+        after()
+        return out[:n_out.value], n_leaves.value, n_valid.value
+
+    def update_depth(self, cam, depth, pos, stamp, quat, max_points=5000, leaf=0.1):
+        """the whole frame from one depth image: a numpy image goes through dspmap_update_depth (one copy of the IMAGE over the bus), a
+        torch tensor on the GPU through dspmap_update_depth_device.  Returns 1 (ok) / 0 (rejected)."""
+        pos_a = (C.c_float * 3)(*pos)
+        q_a = (C.c_float * 4)(*quat)
+        if self._is_device_tensor(depth):
+            depth = self._device_image(cam, depth)
+            self._chk(self.L.dspmap_init_device(self.h))
+            before, after = self._handle_stream_order(depth.device)
+            before()
+            rc = self._chk(self.L.dspmap_update_depth_device(self.h, C.byref(cam), depth.data_ptr(), float(leaf), int(max_points),
+                                                             C.cast(pos_a, C.c_void_p), float(stamp), C.cast(q_a, C.c_void_p)))
+            after()
+            return rc
+        depth = self._host_image(cam, depth)
+        return self._chk(self.L.dspmap_update_depth(self.h, C.byref(cam), _ptr(depth), float(leaf), int(max_points),
+                                                    C.cast(pos_a, C.c_void_p), float(stamp), C.cast(q_a, C.c_void_p)))
 
     def seed_uniform(self, per_voxel, weight=0.01, seed=99, vmax=0.0):
         self._chk(self.L.dspmap_seed_uniform_moving(self.h, per_voxel, weight, seed, vmax))

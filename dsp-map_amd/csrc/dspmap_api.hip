@@ -230,6 +230,13 @@ static void free_dev(dspmap* m) {
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
+    {
+        void* dp[] = {m->dp_sum, m->dp_cnt, m->dp_blk, m->dp_tot, m->dp_out, m->dp_img};
+        for (void* p : dp) if (p) chk(hipFree(p), "hipFree");
+        if (m->dp_img_pin) chk(hipHostFree(m->dp_img_pin), "hipHostFree");
+        m->dp_sum = nullptr; m->dp_cnt = nullptr; m->dp_blk = nullptr; m->dp_tot = nullptr; m->dp_out = nullptr; m->dp_img = nullptr; m->dp_img_pin = nullptr;
+        m->dp_cells_cap = 0; m->dp_out_cap = 0; m->dp_img_bytes = 0; m->dp_img_pin_bytes = 0;
+    }
     for (int k = 0; k < DSPMAP_PTS_RING; ++k) {
         if (m->pts_ring[k]) chk(hipHostFree(m->pts_ring[k]), "hipHostFree");
         if (m->pts_ring_ev[k]) chk(hipEventDestroy(m->pts_ring_ev[k]), "hipEventDestroy");
@@ -1409,6 +1416,10 @@ extern "C" int dspmap_update_device(dspmap_t* m, int n_points, const float* poin
     { const int rq = dspmap_check_estimator_queue(m); if (rq != DSPMAP_OK) return rq; }
     float dp[3], dt;
     if (!dspmap_gate_and_delta(m, pos, stamp, q, dp, &dt)) return DSPMAP_REJECTED;
+    return device_frame(m, n_points, points_dev, n_birth, birth_dev, dp, dt, q);
+}
+int dspmap_device_frame(dspmap* m, int n_points, const float* points_dev, int n_birth, const dspmap_vpoint* birth_dev, const float dp[3],
+                        float dt, const float q[4]) {
     return device_frame(m, n_points, points_dev, n_birth, birth_dev, dp, dt, q);
 }
 

@@ -179,6 +179,18 @@ struct dspmap {
     void* pp_acc = nullptr;
     int* pp_blk = nullptr;
     size_t pp_cells_cap = 0;
+    // depth-image ingest (dspmap_depth.hip): per-leaf fixed-point sums {x, y, z} (int64, units of 2^-20 m) and point counts over the same
+    // leaf lattice as pp_acc.  Zeroed when allocated; the emit kernel zeroes every leaf it reads, so a frame costs no clear of the grid.
+    // dp_dirty: a call did not reach its end (the grid may hold sums): the next one clears all of it first
+    long long* dp_sum = nullptr;
+    int* dp_cnt = nullptr;
+    int* dp_blk = nullptr;
+    int* dp_tot = nullptr;           // {points kept by the crop, occupied leaves, valid pixels}
+    size_t dp_cells_cap = 0;
+    bool dp_dirty = false;
+    float* dp_out = nullptr; int dp_out_cap = 0;         // the filtered cloud of dspmap_update_depth* (the frame reads it)
+    void* dp_img = nullptr; size_t dp_img_bytes = 0;     // device copy of a host image (dspmap_update_depth)
+    void* dp_img_pin = nullptr; size_t dp_img_pin_bytes = 0;   // its pinned staging
     // per-stage profiling
     bool prof = false;
     hipEvent_t pev[DSPMAP_N_STAGES + 1] = {};
@@ -195,6 +207,9 @@ LaunchCtx dspmap_ctx_of(dspmap* m);
 void dspmap_mgpu_birth_early(dspmap* m, const LaunchCtx& c);   // the newborn children of a split-phase frame, on the stream the estimator ran on
 void dspmap_resample(dspmap* m, const LaunchCtx& c);   // launch_resample + bookkeeping of the variant it ran
 int dspmap_gate_and_delta(dspmap* m, const float pos[3], double stamp, const float q[4], float dp[3], float* dt);
+// the device-resident frame behind dspmap_update_device, after the gate (dp, dt from dspmap_gate_and_delta)
+int dspmap_device_frame(dspmap* m, int n_points, const float* points_dev, int n_birth, const dspmap_vpoint* birth_dev, const float dp[3],
+                        float dt, const float q[4]);
 int dspmap_check_estimator_queue(dspmap* m);   // first thing in every frame entry point: fails once if an earlier frame's cross-queue wait gave up
 void dspmap_freeze_birth_statics(dspmap* m);
 int dspmap_ensure_point_cap(dspmap* m, int n);

@@ -196,16 +196,31 @@ public:
                                      sensor_quaternion_y, sensor_quaternion_z);
 #endif
         if (rc < 0) { cerr << "DSPMap::update failed: " << dspmap_last_error(h_) << endl; return 0; }
-        if (rc == 1 && record_flag_) {  // :326-350: every frame when the flag is negative, else once after record_time
-            const float update_time = (float)dspmap_get_param(h_, DSPMAP_P_UPDATE_TIME);
-            if (record_flag_ < 0 || (update_time > record_time_ && !recorded_once_)) {
-                recorded_once_ = 1;
-                const int update_counter = (int)dspmap_get_param(h_, DSPMAP_P_UPDATE_COUNTER);
-                writeParticleCsv(particle_save_folder + "/particles_update_t_" + to_string(update_counter) + "_" +
-                                 to_string((int)(update_time * 1000)) + ".csv");
-            }
-        }
+        record_hook(rc);
         return rc;
+    }
+
+    /* No counterpart in the reference: the whole frame from one depth image in host memory (16UC1 / 32FC1, described by `cam`) --
+       back-projection, the voxel-grid centroid filter (leaf), axis swap, crop and cap (max_points) run on the device
+       (dspmap_update_depth, include/dspmap.h), so the node's cloudCallback pre-processing (src/map_sim_example.cpp:309-336) and its
+       point-cloud copy go away.  Returns 1, 0 (rejected) like update(); a negative code on an error (text on cerr).  Sharded
+       builds (-DDSPMAP_WORLD) keep the cloud entry point: DSPMAP_E_STATE. */
+    int updateDepth(const dspmap_camera& cam, const void* depth_host, float sensor_px, float sensor_py, float sensor_pz,
+                    double time_stamp_second, float sensor_quaternion_w, float sensor_quaternion_x, float sensor_quaternion_y,
+                    float sensor_quaternion_z, float leaf = 0.1f, int max_points = 5000) {
+#ifdef DSPMAP_WORLD
+        (void)cam; (void)depth_host; (void)sensor_px; (void)sensor_py; (void)sensor_pz; (void)time_stamp_second;
+        (void)sensor_quaternion_w; (void)sensor_quaternion_x; (void)sensor_quaternion_y; (void)sensor_quaternion_z; (void)leaf; (void)max_points;
+        return DSPMAP_E_STATE;
+#else
+        lazy_prefill();
+        const float pos[3] = {sensor_px, sensor_py, sensor_pz};
+        const float quat[4] = {sensor_quaternion_w, sensor_quaternion_x, sensor_quaternion_y, sensor_quaternion_z};
+        const int rc = dspmap_update_depth(h_, &cam, depth_host, leaf, max_points, pos, time_stamp_second, quat);
+        if (rc < 0) { cerr << "DSPMap::updateDepth failed: " << dspmap_last_error(h_) << endl; return rc; }
+        record_hook(rc);
+        return rc;
+#endif
     }
 
     void setPredictionVariance(float p_stddev, float v_stddev) {  // :355-360 (regenerates the Gaussian tables)
@@ -295,6 +310,16 @@ public:
 private:
     static float& voxel_filter_res() { static float r = 0.15f; return r; }  // :132
     void sync_params() { dspmap_set_param(h_, DSPMAP_P_VOXEL_FILTER_RES, voxel_filter_res()); }
+    void record_hook(int rc) {   // :326-350: every frame when the flag is negative, else once after record_time
+        if (rc != 1 || !record_flag_) return;
+        const float update_time = (float)dspmap_get_param(h_, DSPMAP_P_UPDATE_TIME);
+        if (record_flag_ < 0 || (update_time > record_time_ && !recorded_once_)) {
+            recorded_once_ = 1;
+            const int update_counter = (int)dspmap_get_param(h_, DSPMAP_P_UPDATE_COUNTER);
+            writeParticleCsv(particle_save_folder + "/particles_update_t_" + to_string(update_counter) + "_" +
+                             to_string((int)(update_time * 1000)) + ".csv");
+        }
+    }
     void lazy_prefill() {
         sync_params();
         if (init_particles_ > 0) { dspmap_add_random_particles(h_, init_particles_, init_weight_); init_particles_ = 0; }

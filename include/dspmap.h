@@ -416,6 +416,47 @@ int dspmap_load_checkpoint(dspmap_t* m, const char* path);
 int dspmap_preprocess_cloud(dspmap_t* m, int n, const float* points_dev, int stride_floats, float leaf, int swap_axes,
                             int max_points, float* out_dev, int* n_out, int* n_leaves_out);
 
+/* ---- depth images straight to the map (what a node with a depth topic owns is a 16UC1 / 32FC1 image, not a cloud).
+ * One kernel reads the image, back-projects every kept pixel in registers and accumulates the voxel-grid filter's leaf sums; the 12 B per
+ * pixel cloud never exists in memory.  Per kept pixel (u = column, v = row), every operation rounded to fp32 on its own:
+ *     d = fl((float)raw * depth_scale)                                   (DSPMAP_DEPTH_F32: raw is the float itself)
+ *     X = fl(fl(fl((float)u - cx) * d) / fx)   Y = fl(fl(fl((float)v - cy) * d) / fy)   Z = d        camera optical frame
+ * A pixel is kept iff it is a return (format) and min_depth <= d <= max_depth.  Leaf membership, the leaf lattice over the map box, the
+ * output order, the axis swap x = Z, y = -X, z = -Y, the open-box crop and the cap are those of dspmap_preprocess_cloud(swap_axes = 1)
+ * applied to (X, Y, Z) (a pixel whose X, Y or Z is not finite is ignored like a non-finite point).  Only the CENTROID differs: each
+ * coordinate is accumulated per leaf as the 64-bit integer llrint((double)p * 2^20) (ties to even) and the centroid is
+ * (float)(((double)S / (double)count) * 2^-20).  Integer sums do not depend on the order of the additions: the filtered cloud is the same
+ * bits on every run, launch shape and pixel order.
+ * Arguments are checked before the device is touched: a NULL handle / camera / image, width, height or pixel_step < 1 (or a side above
+ * 2^24 pixels), a row stride smaller than a row or not a multiple of the element size, an unknown format, non-finite or non-positive fx,
+ * fy, depth_scale, non-finite cx, cy, min_depth > max_depth or a NaN among them, leaf <= 0, max_points < 0 (or NULL outputs / pose) are
+ * DSPMAP_E_ARG with a text; without a usable device a valid call is DSPMAP_E_DEVICE. */
+#define DSPMAP_DEPTH_U16 0   /* raw units, value 0 = no return (RealSense / ROS 16UC1) */
+#define DSPMAP_DEPTH_F32 1   /* raw floats; NaN, +-inf and values <= 0 = no return (ROS 32FC1) */
+typedef struct dspmap_camera {
+    int width, height;
+    int row_stride_bytes;       /* 0 = packed */
+    int format;                 /* DSPMAP_DEPTH_* */
+    float fx, fy, cx, cy;       /* pinhole intrinsics, pixels */
+    float depth_scale;          /* metres per raw unit (0.001 for millimetres, 1 for 32FC1) */
+    float min_depth, max_depth; /* metres; a pixel is kept iff min_depth <= d <= max_depth */
+    int pixel_step;             /* use rows and columns 0, step, 2*step, ...; 1 = every pixel */
+} dspmap_camera;
+/* depth image in device memory -> filtered cloud in device memory; same outputs and the same synchronous contract as
+ * dspmap_preprocess_cloud(swap_axes = 1); *n_valid_out (optional) = pixels that passed the validity and range test */
+int dspmap_preprocess_depth(dspmap_t* m, const dspmap_camera* cam, const void* depth_dev, float leaf, int max_points,
+                            float* out_dev, int* n_out, int* n_leaves_out, int* n_valid_out);
+/* the whole frame from one image: ingest as above into a buffer the handle owns, then exactly dspmap_update_device(n_out, that
+ * buffer, 0, NULL, ...).  1 / 0 / negative like dspmap_update; a rejected frame (0) leaves the map state untouched: the gate of
+ * dspmap_update (quaternion, |dp| > 10 m, dt outside [0, 10] s) is evaluated before any ingest work is queued.  The frame itself is
+ * asynchronous like dspmap_update_device; the call waits for the ingest (one 12-byte read of the point count, which the frame's
+ * parameter block takes from the host). */
+int dspmap_update_depth_device(dspmap_t* m, const dspmap_camera* cam, const void* depth_dev, float leaf, int max_points,
+                               const float sensor_pos[3], double time_stamp_second, const float quat_wxyz[4]);
+/* the same with the image in host memory (one pinned staging copy + H2D of the IMAGE, not of a cloud) */
+int dspmap_update_depth(dspmap_t* m, const dspmap_camera* cam, const void* depth_host, float leaf, int max_points,
+                        const float sensor_pos[3], double time_stamp_second, const float quat_wxyz[4]);
+
 /* addRandomParticles :594-624 (constructor pre-fill); uses the rand table */
 int dspmap_add_random_particles(dspmap_t* m, int n, float weight);
 /* benchmark fill: every voxel gets `per_voxel` zero-velocity particles,
