@@ -131,6 +131,7 @@ SIGNATURES = {
     "dspmap_debug_sweep_probe": (_i, [_P, _i, _i, _i, _i, _fp, C.POINTER(C.c_longlong)]),
     "dspmap_debug_tile_view": (_i, [_P, C.POINTER(C.c_int), _i]),
     "dspmap_debug_rollout_paths": (_i, [_P, C.POINTER(C.c_longlong)]),
+    "dspmap_debug_rollout_plan": (_i, [_P, _ip, _ip]),
     "dspmap_debug_estimator_queue": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_frame_branches": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_resample_split_frames": (C.c_longlong, [_P]),
@@ -300,6 +301,13 @@ class DSPMap:
         out = (C.c_longlong * 3)()
         self._chk(self.L.dspmap_debug_rollout_paths(self.h, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def rollout_plan(self):
+        """(halo rows per horizon of k_rollout's LDS windows, LDS cells of all windows) for this handle; all halos 0 = the collapsed plan"""
+        halo = (C.c_int * MAX_PRED)()
+        cells = C.c_int()
+        n = self._chk(self.L.dspmap_debug_rollout_plan(self.h, halo, C.byref(cells)))
+        return [int(halo[t]) for t in range(n)], cells.value
 
     def estimator_queue(self):
         """(frames whose estimator ran on a queue of its own, hand-over word 0, hand-over word 1, give-ups, frames whose first birth kernel

@@ -1883,7 +1883,6 @@ extern "C" int dspmap_add_random_particles(dspmap_t* m, int n, float weight) {
     if (rc != DSPMAP_OK) return rc;
     rc = dspmap_mark_nb_dirty(m);
     if (rc != DSPMAP_OK) return rc;
-    if ((long long)m->d.v_loc >= (1ll << 24)) return dspmap_fail(m, DSPMAP_E_ARG, "constructor pre-fill supports up to 2^24 voxels per handle");
     LaunchCtx c = dspmap_ctx_of(m);
     int* slot_of = nullptr;
     HIPCHK(m, dalloc(&slot_of, (size_t)(n > 0 ? n : 1)));
@@ -2117,6 +2116,13 @@ extern "C" int dspmap_debug_rollout_paths(dspmap_t* m, long long out[3]) {
         for (size_t g = 0; g < ng; ++g) { out[1] += st[2 * g]; out[2] += st[2 * g + 1]; }
     }
     return DSPMAP_OK;
+}
+extern "C" int dspmap_debug_rollout_plan(dspmap_t* m, int halo_out[DSPMAP_MAX_PRED_TIMES], int* lds_cells_out) {
+    if (!m || !halo_out) return DSPMAP_E_ARG;   // (host state only: no device needed)
+    for (int t = 0; t < DSPMAP_MAX_PRED_TIMES; ++t) halo_out[t] = -1;
+    const int cells = rollout_plan_halos(m->d, halo_out);
+    if (lds_cells_out) *lds_cells_out = cells;
+    return m->d.T;
 }
 extern "C" int dspmap_debug_frame_branches(dspmap_t* m, long long out[5]) {
     READY(m);

@@ -123,6 +123,7 @@ void launch_birth_materialize(const LaunchCtx& c, BirthSrc* out, int cap, int* n
 // mapOccupancyCalculationAndResample (:924-1057)
 void launch_resample(const LaunchCtx& c, int cls = 0, bool with_rollout = true, int part = 0);   // + the future rollout of the moving particles (k_rollout)
 int rollout_groups(const MapDims& d, int ntiles);   // workgroup groups of k_rollout (KernelScratch::ro_stat holds 2 ints per workgroup: x 4 with cube storage and windows)
+int rollout_plan_halos(const MapDims& d, int* halo_out);   // k_rollout's window plan for this map: halo rows per horizon -> halo_out[T]; returns the LDS cells of all windows
 void launch_rollout(const LaunchCtx& c);    // the rollout alone (a two-branch frame: once, behind both branches' resampling)
 int resample_variant(const LaunchCtx& c);   // bit 0: k_resample_wg; bits 1-2: rollout 0 inline, 1 k_rollout light, 2 k_rollout windows, 3 none
 void kernels_init_device();                 // function attributes of the current device (dynamic LDS of k_rollout)

@@ -2085,13 +2085,24 @@ __device__ __forceinline__ SeedDraw seed_draw(const MapDims& d, const DevState& 
     if (voxel_of_lv(d, r.px, r.py, r.pz, gv, lv)) r.lv = lv;   // (-1: another rank's slab)
     return r;
 }
+// A voxel's bucket ends up holding the SEED_BUCKET_CAP LOWEST particle indices drawn into it, ascending, whatever the order the threads
+// arrive in: every entry starts as SEED_EMPTY, a thread walks the bucket with atomicMin and carries the larger of the two values on.
+// Entry p sees every index except the p smaller ones that came to rest before it, so it ends as the (p + 1)-th smallest.  (Keeping the
+// first SEED_BUCKET_CAP ARRIVALS, as this did, placed other particles than the sequential reference from 129 candidates per voxel on:
+// half of the voxels of a 128-slot map pre-filled with one particle per slot.)
+#define SEED_EMPTY 0x7f7f7f7f   // (hipMemsetAsync's byte pattern; above every particle index a pre-fill can have)
 __global__ void k_add_random_bucket(MapDims d, DevState s, FilterParams fp, int n, int* __restrict__ vb_cnt, int* __restrict__ vb_idx) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || i >= SEED_EMPTY) return;
     const SeedDraw r = seed_draw(d, s, fp, i);
     if (r.lv < 0) return;
-    const int pos = atomicAdd(&vb_cnt[r.lv], 1);
-    if (pos < SEED_BUCKET_CAP) vb_idx[(size_t)r.lv * SEED_BUCKET_CAP + pos] = i;
+    atomicAdd(&vb_cnt[r.lv], 1);
+    int* b = vb_idx + (size_t)r.lv * SEED_BUCKET_CAP;
+    int cur = i;
+    for (int p = 0; p < SEED_BUCKET_CAP && cur != SEED_EMPTY; ++p) {
+        const int prev = atomicMin(&b[p], cur);
+        if (prev > cur) cur = prev;
+    }
 }
 __global__ void k_add_random_place(MapDims d, DevState s, FilterParams fp, int n, float weight, const int* __restrict__ vb_cnt,
                                    const int* __restrict__ vb_idx, int* __restrict__ slot_of) {
@@ -2124,12 +2135,12 @@ __global__ void k_add_random_place(MapDims d, DevState s, FilterParams fp, int n
     st_pos(s, idx, r.px, r.py, r.pz); st_vel(s, idx, r.vx, r.vy); s.w[idx] = weight;
     note_speed(s, r.vx, r.vy);
     if (s.vz0) s.vz0[idx] = r.vz;
-    slot_of[i] = (r.lv << 7) | sl;
+    slot_of[i] = r.lv * d.slots + sl;   // the cell index (31-bit by dspmap_create's bound; (lv << 7) | sl overflowed from 2^24 voxels on)
 }
 __global__ void k_add_random_commit(MapDims d, DevState s, int n, const int* __restrict__ slot_of) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || slot_of[i] < 0) return;
-    const int lv = slot_of[i] >> 7, sl = slot_of[i] & 127;
+    const int lv = slot_of[i] / d.slots, sl = slot_of[i] - lv * d.slots;
     atomicOr(&s.nbmask[(size_t)lv * d.mw + (sl >> 6)], 1ull << (sl & 63));   // flag 15
 }
 __global__ void k_zero_ints(int* __restrict__ p, int n) {
@@ -2481,31 +2492,40 @@ void launch_resample(const LaunchCtx& c, int cls, bool with_rollout, int part) {
 int rollout_groups(const MapDims& d, int ntiles) {   // groups of k_rollout: runs of RO_G tiles; cube storage: inside one row of cubes
     return d.tiling ? d.ncz * ((d.ncy + RO_GC - 1) / RO_GC) * ((d.ncx + RO_GC - 1) / RO_GC) : (ntiles + RO_G - 1) / RO_G;
 }
+static void rollout_plan(const MapDims& d, RolloutPlan& pl) {
+    // windows: the rows a particle reaches at a design speed (1.5 m/s, a brisk pedestrian), lowered until all T windows fit the LDS
+    float vdes = 1.5f;
+    for (;;) {
+        int tot = 0;
+        for (int t = 0; t < d.T; ++t) {
+            pl.halo[t] = (int)ceilf(vdes * fabsf(d.pred_t[t]) / d.res) + 1;
+            pl.woff[t] = tot;
+            // index-order storage: the group's 512 voxel indices and halo rows of the grid either side; cubes: the rectangle of voxels
+            // around the group's 32 x 4 in one layer (one workgroup per layer)
+            tot += d.tiling ? (RO_GC * 4 + 2 * pl.halo[t]) * (RO_GC * 4 + 2 * pl.halo[t]) : RO_G * 64 + 2 * pl.halo[t] * d.nx;
+        }
+        pl.woff[d.T] = tot;
+        if (tot <= RO_LDS_CELLS || vdes < 0.02f) break;
+        vdes *= 0.8f;
+    }
+    if (pl.woff[d.T] > RO_LDS_CELLS) {   // (a grid too wide even for one-row halos: every window collapses to the group itself)
+        int tot = 0;
+        for (int t = 0; t < d.T; ++t) { pl.halo[t] = 0; pl.woff[t] = tot; tot += d.tiling ? RO_GC * 4 * RO_GC * 4 : RO_G * 64; }
+        pl.woff[d.T] = tot;
+    }
+}
+int rollout_plan_halos(const MapDims& d, int* halo_out) {   // the plan k_rollout gets for this map: halo rows per horizon; returns its LDS cells
+    RolloutPlan pl;
+    rollout_plan(d, pl);
+    for (int t = 0; t < d.T; ++t) halo_out[t] = pl.halo[t];
+    return pl.woff[d.T];
+}
 void launch_rollout(const LaunchCtx& c) {
     const KernelScratch* k = &c.k;
     const int ro = resample_variant(c) >> 1;
     if (ro == 1 || ro == 2) {
-        // windows: the rows a particle reaches at a design speed (1.5 m/s, a brisk pedestrian), lowered until all T windows fit the LDS
         RolloutPlan pl;
-        float vdes = 1.5f;
-        for (;;) {
-            int tot = 0;
-            for (int t = 0; t < c.d.T; ++t) {
-                pl.halo[t] = (int)ceilf(vdes * fabsf(c.d.pred_t[t]) / c.d.res) + 1;
-                pl.woff[t] = tot;
-                // index-order storage: the group's 512 voxel indices and halo rows of the grid either side; cubes: the rectangle of voxels
-                // around the group's 32 x 4 in one layer (one workgroup per layer)
-                tot += c.d.tiling ? (RO_GC * 4 + 2 * pl.halo[t]) * (RO_GC * 4 + 2 * pl.halo[t]) : RO_G * 64 + 2 * pl.halo[t] * c.d.nx;
-            }
-            pl.woff[c.d.T] = tot;
-            if (tot <= RO_LDS_CELLS || vdes < 0.02f) break;
-            vdes *= 0.8f;
-        }
-        if (pl.woff[c.d.T] > RO_LDS_CELLS) {   // (a grid too wide even for one-row halos: every window collapses to the group itself)
-            int tot = 0;
-            for (int t = 0; t < c.d.T; ++t) { pl.halo[t] = 0; pl.woff[t] = tot; tot += c.d.tiling ? RO_GC * 4 * RO_GC * 4 : RO_G * 64; }
-            pl.woff[c.d.T] = tot;
-        }
+        rollout_plan(c.d, pl);
         const unsigned ngrp = (unsigned)rollout_groups(c.d, k->ntiles);
         if (ro == 1) hipLaunchKernelGGL((k_rollout<256, true>), dim3(ngrp), dim3(256), 0, c.stream, c.d, c.s, k->ro_rec, k->ro_cnt,
                                         k->ntiles, pl, k->ro_stat, k->ro_sub);
@@ -2538,6 +2558,7 @@ void launch_add_random(const LaunchCtx& c, int n, float weight, int* slot_of_tmp
     if (n <= 0) return;
     mark_all_live(c);
     const dim3 g((n + 255) / 256), b(256);
+    (void)hipMemsetAsync(c.k.vb_idx, SEED_EMPTY & 0xff, sizeof(int) * (size_t)c.d.v_loc * SEED_BUCKET_CAP, c.stream);   // (k_add_random_bucket)
     hipLaunchKernelGGL(k_add_random_bucket, g, b, 0, c.stream, c.d, c.s, c.fp, n, c.k.vb_cnt, c.k.vb_idx);
     hipLaunchKernelGGL(k_add_random_place, g, b, 0, c.stream, c.d, c.s, c.fp, n, weight, c.k.vb_cnt, c.k.vb_idx, slot_of_tmp);
     hipLaunchKernelGGL(k_add_random_commit, g, b, 0, c.stream, c.d, c.s, n, slot_of_tmp);

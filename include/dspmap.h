@@ -369,6 +369,11 @@ int dspmap_debug_tile_moving(dspmap_t* m, int* out, int cap);
  * out[0] = bit 0: four-waves-per-tile resampler; bits 1-2: rollout 0 inside the resampler, 1 k_rollout without LDS windows,
  * 2 k_rollout with LDS windows, 3 none; out[1] / out[2] = contributions k_rollout sent through its windows / as single atomics */
 int dspmap_debug_rollout_paths(dspmap_t* m, long long out[3]);
+/* diagnostics: the window plan k_rollout gets on this handle (a function of the configuration and the storage order alone; no device
+ * needed): halo_out[t] = rows of the grid horizon t's LDS window reaches beyond its group of tiles, either side (-1 past the last
+ * horizon), *lds_cells_out = 32-bit cells of all windows together (may be NULL).  All halos 0 = the collapsed plan of a grid too wide
+ * for one-row halos: every window is the group itself.  Returns the number of horizons or an error */
+int dspmap_debug_rollout_plan(dspmap_t* m, int halo_out[DSPMAP_MAX_PRED_TIMES], int* lds_cells_out);
 /* diagnostics of DSPMAP_P_ESTIMATOR_QUEUE: out[0] = frames of this handle whose velocity estimator ran on a queue of its own, out[1] / out[2] = the
  * two hand-over words (ring position + 1 of the last frame whose birth stage has ended / whose birth cloud the estimator has finished),
  * out[3] = nonzero if a cross-queue wait ever gave up, out[4] = frames whose first birth kernel found the birth cloud unfinished (its workgroup 0

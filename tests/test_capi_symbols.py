@@ -67,6 +67,17 @@ def test_create_rejects_bad_config(dsp):
     assert not L.dspmap_create(C.byref(bad))
     bad = dsp.make_config(z_lo=30, z_hi=50)
     assert not L.dspmap_create(C.byref(bad))
+    # the immediate neighbours outside the configuration space (tests/config_edges.py): 65 particles per voxel, 129 slots, 17 horizons,
+    # 130 / 98 pyramids per axis at 1 degree, 2^31 cells -- and the nearest configuration inside is accepted
+    from tests import config_edges as E
+    assert sorted(E.OUTSIDE) == ["cells_2p31", "fov_h65", "fov_v49", "ppv65", "slots129", "t17"]
+    for name in E.OUTSIDE:
+        assert not L.dspmap_create(C.byref(E.outside_config(dsp.make_config, name))), name
+    for kw in (dict(ppv=64), dict(ppv=32, safe_factor=4), dict(pred_times=E.T16), dict(angle=1, half_fov_h=64, half_fov_v=48),
+               dict(nx=1024, ny=1024, nz=1023, ppv=1)):
+        h = L.dspmap_create(C.byref(dsp.make_config(**dict(E.SMALL, **kw))))
+        assert h, kw
+        L.dspmap_destroy(h)
 
 
 def test_compute_fails_loudly_without_gpu(dsp):
