@@ -80,6 +80,7 @@ VPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"),
 # dspmap_risk: one per trajectory (dspmap_trajectory_risk)
 RISK_DTYPE = np.dtype([("sum", "f4"), ("max", "f4"), ("first_over", "i4"), ("n_outside", "i4")])
 QUERY_WORLD = 1   # DSPMAP_QUERY_WORLD
+DIST_OUTSIDE_OCCUPIED = 1   # DSPMAP_DIST_OUTSIDE_OCCUPIED
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -115,6 +116,11 @@ SIGNATURES = {
     "dspmap_query_occupancy_device": (_i, [_P, _i, _P, _f, _i, _f, _P]),
     "dspmap_trajectory_risk": (_i, [_P, _i, _i, _P, _f, _i, _f, _f, _P]),
     "dspmap_trajectory_risk_device": (_i, [_P, _i, _i, _P, _f, _i, _f, _f, _P]),
+    "dspmap_build_distance_field": (_i, [_P, _f, _i, _i]),
+    "dspmap_distance_field_device": (_P, [_P]),
+    "dspmap_get_distance_field": (_i, [_P, _i, _P]),
+    "dspmap_query_distance": (_i, [_P, _i, _P, _i, _f, _P, _P]),
+    "dspmap_query_distance_device": (_i, [_P, _i, _P, _i, _f, _P, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -521,6 +527,54 @@ class DSPMap:
         out = np.zeros(k, RISK_DTYPE)
         self._chk(self.L.dspmap_trajectory_risk(self.h, k, s, _ptr(q), float(radius), flags, float(outside), float(threshold), _ptr(out)))
         return out
+
+    # -- distance fields (extension; semantics in include/dspmap.h next to dspmap_build_distance_field)
+    def build_distance_field(self, threshold, max_voxels, outside_occupied=False):
+        """enqueue the truncated Euclidean distance fields of all T + 1 layers (0: current mass, 1 + k: horizon k) on the handle's stream:
+        metres to the nearest voxel with mass > threshold, at most max_voxels voxels; outside_occupied counts the lattice just outside
+        the map as occupied.  Read-only towards the map; the field is a snapshot and goes stale with the next frame."""
+        self._chk(self.L.dspmap_build_distance_field(self.h, float(threshold), int(max_voxels), DIST_OUTSIDE_OCCUPIED if outside_occupied else 0))
+
+    def distance_field(self, layer=None):
+        """the field of one layer as numpy [nz, ny, nx], or of all layers [L, nz, ny, nx] (synchronous host copies)"""
+        shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
+        layers = range(self.T + 1) if layer is None else [int(layer)]
+        out = np.zeros((len(layers),) + shape, np.float32)
+        for j, l in enumerate(layers):
+            self._chk(self.L.dspmap_get_distance_field(self.h, l, _ptr(out[j])))
+        return out if layer is None else out[0]
+
+    def distance_field_ptr(self):
+        """device address of the [L][V] float32 field, or None when there is none / it is stale"""
+        return self.L.dspmap_distance_field_device(self.h) or None
+
+    def query_distance(self, q, world=False, outside=0.0, grad=True):
+        """distance (and gradient [n, 3] unless grad is False) of every sample {x, y, z, t} of q ([n, 4] float32) in the layer its t
+        selects (t < 0: current, else the first horizon >= t): the field at the point's own voxel and its central / one-sided
+        differences; `outside` and a zero gradient for what lies outside the map.  numpy in -> numpy out (synchronous); a torch tensor
+        on the GPU -> tensors on the same device, enqueued on the handle's stream and ordered with torch's current stream like
+        query_occupancy.  Returns (dist, grad) or dist."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(q):
+            import torch
+            q = self._device_samples(q, (4,), "query_distance")
+            n = q.numel() // 4
+            dist = torch.empty(n, dtype=torch.float32, device=q.device)
+            g = torch.empty((n, 3), dtype=torch.float32, device=q.device) if grad else None
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_query_distance_device(self.h, n, q.data_ptr(), flags, float(outside), dist.data_ptr(),
+                                                          g.data_ptr() if grad else None))
+            after()
+            return (dist, g) if grad else dist
+        q = np.ascontiguousarray(q, np.float32)
+        if q.shape[-1:] != (4,):
+            raise ValueError("query_distance: samples of shape [n, 4]")
+        n = q.size // 4
+        dist = np.zeros(n, np.float32)
+        g = np.zeros((n, 3), np.float32) if grad else None
+        self._chk(self.L.dspmap_query_distance(self.h, n, _ptr(q), flags, float(outside), _ptr(dist), _ptr(g)))
+        return (dist, g) if grad else dist
 
     def getVoxelPositionFromIndexPublic(self, index):
         x, y, z = C.c_float(), C.c_float(), C.c_float()

@@ -227,6 +227,8 @@ static void free_dev(dspmap* m) {
         for (void* q : vp) if (q) chk(hipFree(q), "hipFree");
     }
     if (m->q_buf) { chk(hipFree(m->q_buf), "hipFree"); m->q_buf = nullptr; m->q_buf_bytes = 0; }
+    for (void* q : {(void*)m->df_field, (void*)m->df_g8, (void*)m->df_h16}) if (q) chk(hipFree(q), "hipFree");
+    m->df_field = nullptr; m->df_g8 = nullptr; m->df_h16 = nullptr; m->df_valid = false;
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
@@ -821,6 +823,7 @@ int dspmap_gate_and_delta(dspmap* m, const float pos[3], double stamp, const flo
     m->last_stamp = stamp;
     m->dt_last = *dt;
     m->update_time += *dt; m->update_counter += 1;   // mapPrediction :634-635
+    m->df_valid = false;   // a new frame: a distance field is a snapshot of the one before
     for (int i = 0; i < 4; i++) m->quat[i] = q[i];
     return 1;
 }
@@ -1732,6 +1735,93 @@ extern "C" int dspmap_trajectory_risk_device(dspmap_t* m, int n_traj, int n_samp
     return risk_enqueue(m, n_traj, n_samples, (const float4*)q, (float*)m->q_buf, r, flags, outside, thr, out);
 }
 
+// --------------------------------------------------- distance fields (dspmap_distance.hip; semantics in include/dspmap.h)
+extern "C" int dspmap_build_distance_field(dspmap_t* m, float thr, int max_voxels, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (thr != thr) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: threshold is NaN");
+    if (max_voxels < 1 || max_voxels > 64) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: max_voxels %d outside [1, 64]", max_voxels);
+    if (flags & ~DSPMAP_DIST_OUTSIDE_OCCUPIED) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: unknown flags 0x%x", flags);
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "distance field: a slab handle holds part of the map; distances cross slabs");
+    READY(m);
+    BENIGN(m);
+    const MapDims& d = m->d;
+    const size_t cells = (size_t)(d.T + 1) * d.v_glob;
+    m->df_valid = false;
+    if (!m->df_field) {
+        HIPCHK(m, hipMalloc(&m->df_field, sizeof(float) * cells));
+        HIPCHK(m, hipMalloc(&m->df_g8, cells));
+        HIPCHK(m, hipMalloc(&m->df_h16, sizeof(unsigned short) * cells));
+    }
+    DistArgs a;
+    a.thr = thr; a.R = max_voxels; a.outside_occ = (flags & DSPMAP_DIST_OUTSIDE_OCCUPIED) ? 1 : 0;
+    a.fut_zero = m->fut_clear_pending ? 1 : 0;   // read, never changed (as the queries)
+    a.L = d.T + 1;
+    a.g8 = m->df_g8; a.h16 = m->df_h16; a.field = m->df_field;
+    launch_distance_field(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    m->df_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" const float* dspmap_distance_field_device(dspmap_t* m) { return (m && m->df_valid) ? m->df_field : nullptr; }
+static int dist_field_ready(dspmap* m, const char* what) {
+    if (!m->df_valid)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no distance field, or the map has changed since it was built (dspmap_build_distance_field)", what);
+    if (m->device >= 0) (void)hipSetDevice(m->device);
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_distance_field(dspmap_t* m, int layer, float* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: NULL output array");
+    if (layer < 0 || layer > m->d.T) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: layer %d outside [0, %d)", layer, m->d.T + 1);
+    const int rc = dist_field_ready(m, "dspmap_get_distance_field");
+    if (rc != DSPMAP_OK) return rc;
+    const size_t V = (size_t)m->d.v_glob;
+    HIPCHK(m, hipMemcpyAsync(out, m->df_field + V * layer, sizeof(float) * V, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+static int dist_query_check(dspmap* m, int n, const void* in, const void* out, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "distance query: negative sample count %d", n);
+    if (n > 0 && (!in || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "distance query: NULL sample or output array");
+    if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "distance query: unknown flags 0x%x", flags);
+    if (outside != outside) return dspmap_fail(m, DSPMAP_E_ARG, "distance query: outside_value is NaN");
+    return dist_field_ready(m, "dspmap_query_distance");
+}
+static DistQueryArgs dist_query_args(const dspmap* m, int flags, float outside) {
+    DistQueryArgs a;
+    a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a.ox = m->cur_pos[0]; a.oy = m->cur_pos[1]; a.oz = m->cur_pos[2];
+    a.outside = outside;
+    a.field = m->df_field;
+    return a;
+}
+extern "C" int dspmap_query_distance(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, float* dist, float* grad) {
+    int rc = dist_query_check(m, n, q, dist, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    const size_t qb = q_align(sizeof(dspmap_query) * (size_t)n), db = q_align(sizeof(float) * (size_t)n);
+    if ((rc = query_buf(m, qb + db + (grad ? sizeof(float) * 3 * (size_t)n : 0))) != DSPMAP_OK) return rc;
+    float4* dq = (float4*)m->q_buf;
+    float* dd = (float*)((char*)m->q_buf + qb);
+    float* dg = grad ? (float*)((char*)m->q_buf + qb + db) : nullptr;
+    HIPCHK(m, hipMemcpyAsync(dq, q, sizeof(dspmap_query) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    launch_distance_query(dspmap_ctx_of(m), dist_query_args(m, flags, outside), n, dq, dd, dg);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(dist, dd, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (grad) HIPCHK(m, hipMemcpyAsync(grad, dg, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_distance_device(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, float* dist, float* grad) {
+    const int rc = dist_query_check(m, n, q, dist, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    launch_distance_query(dspmap_ctx_of(m), dist_query_args(m, flags, outside), n, (const float4*)q, dist, grad);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+
 extern "C" void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz) {  // :1556-1572
     const MapDims& d = m->d;
     const int zc = d.ny * d.nx;
@@ -1800,6 +1890,7 @@ int dspmap_mark_nb_dirty(dspmap* m) {
 
 extern "C" int dspmap_clear_state(dspmap_t* m) {
     READY(m);
+    m->df_valid = false;
     m->state_epoch++;
     const MapDims& d = m->d;
     const size_t W = (size_t)d.v_loc * d.mw;
@@ -1822,6 +1913,7 @@ extern "C" int dspmap_clear_state(dspmap_t* m) {
 
 extern "C" int dspmap_import_state(dspmap_t* m, int n, const int* voxel, const int* slot, const float* rec8) {
     READY(m);
+    m->df_valid = false;
     m->state_epoch++;
     if (n < 0 || (n > 0 && (!voxel || !rec8))) return DSPMAP_E_ARG;
     if (n == 0) return DSPMAP_OK;
@@ -1877,6 +1969,7 @@ extern "C" int dspmap_export_state(dspmap_t* m, int cap, int* voxel, int* slot, 
 
 extern "C" int dspmap_add_random_particles(dspmap_t* m, int n, float weight) {
     READY(m);
+    m->df_valid = false;
     m->state_epoch++;
     if (n < 0) return DSPMAP_E_ARG;
     int rc = ensure_vz(m);
@@ -1895,6 +1988,7 @@ extern "C" int dspmap_add_random_particles(dspmap_t* m, int n, float weight) {
 
 extern "C" int dspmap_seed_uniform_moving(dspmap_t* m, int per_voxel, float weight, unsigned seed, float vmax) {
     READY(m);
+    m->df_valid = false;
     m->state_epoch++;
     if (per_voxel < 0 || per_voxel > m->d.slots) return dspmap_fail(m, DSPMAP_E_ARG, "per_voxel must be in [0, %d]", m->d.slots);
     if (!(vmax >= 0.f)) return dspmap_fail(m, DSPMAP_E_ARG, "vmax must be >= 0");
@@ -1936,6 +2030,7 @@ extern "C" int dspmap_set_current_position(dspmap_t* m, float x, float y, float 
 }
 extern "C" int dspmap_stage_predict(dspmap_t* m, float dx, float dy, float dz, float dt) {
     READY(m);
+    m->df_valid = false;
     m->frame_parity ^= 1u;
     LaunchCtx c = dspmap_ctx_of(m);
     if (m->vz_frames <= 0) c.s.vz0 = nullptr;
@@ -1955,6 +2050,7 @@ extern "C" int dspmap_stage_predict(dspmap_t* m, float dx, float dy, float dz, f
 }
 extern "C" int dspmap_stage_update(dspmap_t* m) {
     READY(m);
+    m->df_valid = false;
     LaunchCtx c = dspmap_ctx_of(m);
     launch_ck_partial(c);
     launch_weight_update(c);
@@ -1964,6 +2060,7 @@ extern "C" int dspmap_stage_update(dspmap_t* m) {
 }
 extern "C" int dspmap_stage_birth(dspmap_t* m) {
     READY(m);
+    m->df_valid = false;
     dspmap_freeze_birth_statics(m);
     int nb = m->last_n_birth;
     if (m->h_birth_valid) {
@@ -1985,6 +2082,7 @@ extern "C" int dspmap_stage_birth(dspmap_t* m) {
 }
 extern "C" int dspmap_stage_resample(dspmap_t* m) {
     READY(m);
+    m->df_valid = false;
     dspmap_flush_future_clear(m);   // a pending clear must not wipe what this stage accumulates
     LaunchCtx c = dspmap_ctx_of(m);
     if (m->vz_frames <= 0) c.s.vz0 = nullptr;
@@ -2279,6 +2377,7 @@ extern "C" int dspmap_save_checkpoint(dspmap_t* m, const char* path) {
 
 extern "C" int dspmap_load_checkpoint(dspmap_t* m, const char* path) {
     READY(m);
+    m->df_valid = false;
     if (!path) return DSPMAP_E_ARG;
     FILE* f = fopen(path, "rb");
     if (!f) return dspmap_fail(m, DSPMAP_E_ARG, "cannot open %s", path);

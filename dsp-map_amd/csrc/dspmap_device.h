@@ -339,6 +339,17 @@ __device__ __forceinline__ float fut_status_at(const MapDims& d, const DevState&
     return fut_value(s.fut[(size_t)k * d.v_loc + lv]) + s.fut_stat[lv];
 }
 
+// the horizon a query sample reads (dspmap_query.hip, dspmap_distance.hip): -1 = the current mass (t < 0, or a map without horizons);
+// else the smallest k with prediction_future_time[k] >= t, clamped to T - 1.  (t is not NaN here.)
+__device__ __forceinline__ int q_horizon(const MapDims& d, float t) {
+    if (!(t >= 0.f) || d.T == 0) return -1;
+    int k = d.T - 1;
+#pragma unroll
+    for (int j = DSP_MAX_PRED - 1; j >= 0; --j)
+        if (j < d.T && d.pred_t[j] >= t) k = j;
+    return k;
+}
+
 // entries of pyramid b's range-sorted particle list (what the pair kernels read): the list as registered, cut to the reference's
 // capacity -- on a sharded map in a frame with a global cut, what THIS rank keeps of it
 __device__ __forceinline__ int pyr_len(const MapDims& d, const DevState& s, int b) {

@@ -174,6 +174,10 @@ struct dspmap {
     // point / trajectory queries (dspmap_query_occupancy*, dspmap_trajectory_risk*): device staging of the host variants' samples and
     // results and of the risk's per-sample values; grown on demand (after the stream has drained), freed with the device state
     void* q_buf = nullptr; size_t q_buf_bytes = 0;
+    // distance fields (dspmap_build_distance_field): the field [L][V] and the two passes' scratch, allocated by the first build, freed with the
+    // device state.  df_valid: the field is a snapshot of the map as it is -- cleared by everything that computes a frame or replaces state
+    float* df_field = nullptr; unsigned char* df_g8 = nullptr; unsigned short* df_h16 = nullptr;
+    bool df_valid = false;
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;

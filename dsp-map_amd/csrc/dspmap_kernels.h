@@ -148,6 +148,27 @@ void launch_query(const LaunchCtx& c, const QueryArgs& a, int n, const float4* q
 // per trajectory of n_samples consecutive values: sequential fp32 sum, max, first value > threshold, flagged samples
 void launch_risk_reduce(const LaunchCtx& c, int n_traj, int n_samples, const float* v, const unsigned char* flag, float threshold,
                         struct dspmap_risk* out);
+// truncated Euclidean distance fields of the current and the predicted occupancy (dspmap_distance.hip; semantics in include/dspmap.h,
+// dspmap_build_distance_field).  Three separable passes over all L = T + 1 layers at once; the grids are in the reference's voxel order
+struct DistArgs {
+    float thr;           // a voxel is occupied iff its mass > thr (getOccupancyMap's comparison, :394)
+    int R;               // truncation radius in voxels, 1 .. 64
+    int outside_occ;     // DSPMAP_DIST_OUTSIDE_OCCUPIED: the lattice just outside the map counts as occupied
+    int fut_zero;        // 1: a clear of the future accumulators is pending -- the layers >= 1 are empty
+    int L;               // layers: T + 1
+    unsigned char* g8;   // [L][V] pass 1: distance along x to the row's nearest occupied voxel, clamped to R + 1
+    unsigned short* h16; // [L][V] pass 2: squared distance within the z plane, clamped to R^2
+    float* field;        // [L][V] pass 3: the field
+};
+void launch_distance_field(const LaunchCtx& c, const DistArgs& a);
+struct DistQueryArgs {
+    float ox, oy, oz;    // as QueryArgs
+    int world;
+    float outside;       // what a point outside the map or a NaN sample reads
+    const float* field;  // [L][V]
+};
+// dist[i] = the field at sample q[i]'s own voxel in the layer its t selects, grad[3 i ..] (optional) = its central / one-sided differences
+void launch_distance_query(const LaunchCtx& c, const DistQueryArgs& a, int n, const float4* q, float* dist, float* grad);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

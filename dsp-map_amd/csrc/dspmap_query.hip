@@ -22,16 +22,7 @@
 
 #define Q_TPB 256
 
-// the horizon a sample reads: -1 = the current mass (t < 0, or a map without horizons); else the smallest k with
-// prediction_future_time[k] >= t, clamped to T - 1.  (t is not NaN here.)
-__device__ __forceinline__ int q_horizon(const MapDims& d, float t) {
-    if (!(t >= 0.f) || d.T == 0) return -1;
-    int k = d.T - 1;
-#pragma unroll
-    for (int j = DSP_MAX_PRED - 1; j >= 0; --j)
-        if (j < d.T && d.pred_t[j] >= t) k = j;
-    return k;
-}
+// (q_horizon, the horizon k(t) a sample reads, lives in dspmap_device.h: dspmap_distance.hip picks its layer with it too)
 __device__ __forceinline__ float q_mass(const MapDims& d, const DevState& s, int lv, int k, int fut_zero) {
     if (k < 0) return s.res4[lv].x;
     return fut_zero ? 0.f : fut_status_at(d, s, lv, k);

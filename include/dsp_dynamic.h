@@ -258,6 +258,17 @@ public:
         return dspmap_trajectory_risk(h_, n_traj, n_samples, samples, radius, world_frame ? DSPMAP_QUERY_WORLD : 0, outside_value,
                                       threshold, risk);
     }
+    /* extensions: truncated Euclidean distance fields of the current (layer 0) and the predicted (layer 1 + k) occupancy, built and kept on
+     * the device (dspmap_build_distance_field in dspmap.h): metres to the nearest voxel with mass > threshold, at most max_voxels voxels.
+     * Read-only towards the map; a field is a snapshot and goes stale with the next update().  Return DSPMAP_OK or a negative error code. */
+    int buildDistanceField(const float threshold = 0.7, int max_voxels = 20, bool outside_occupied = false) {
+        return dspmap_build_distance_field(h_, threshold, max_voxels, outside_occupied ? DSPMAP_DIST_OUTSIDE_OCCUPIED : 0);
+    }
+    int getDistanceField(int layer, float* field) { return dspmap_get_distance_field(h_, layer, field); }
+    int queryDistance(int n, const dspmap_query* samples, float* distances, float* gradients = nullptr, bool world_frame = false,
+                      float outside_value = 0.f) {
+        return dspmap_query_distance(h_, n, samples, world_frame ? DSPMAP_QUERY_WORLD : 0, outside_value, distances, gradients);
+    }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

@@ -321,6 +321,49 @@ int dspmap_trajectory_risk(dspmap_t* m, int n_traj, int n_samples, const dspmap_
 int dspmap_trajectory_risk_device(dspmap_t* m, int n_traj, int n_samples, const dspmap_query* q_dev, float radius, int flags,
                                   float outside_value, float threshold, dspmap_risk* out_dev);
 
+/* ---- truncated Euclidean distance fields of the current and the predicted occupancy (no counterpart in the reference; the clearance a
+ * gradient-based planner, an MPC cost term or a corridor generator needs right after the map, computed where the map lives instead of by
+ * T + 1 whole-grid copies and CPU distance transforms).
+ *
+ * Layers: L = T + 1.  Layer 0 is the current mass, layer 1 + k is horizon k; a map with T == 0 has one layer.  Each layer is a dense
+ * [nz][ny][nx] grid in the reference's global voxel index order (:1081), whatever DSPMAP_P_TILING stores internally.
+ *  - occupied: layer 0: voxels_objects_number[v][0] > threshold (getOccupancyMap's comparison, :394; dspmap_get_results column 0);
+ *    layer 1 + k: future[v][k] > threshold with future bit for bit what dspmap_get_future would return -- 0 everywhere while a clear is
+ *    pending (after a consuming readout or dspmap_clear_future), as the queries above read it.
+ *  - value: with integer voxel indices, D2(i) = min over the occupied voxels u of (ix - ux)^2 + (iy - uy)^2 + (iz - uz)^2, +inf for a layer
+ *    without an occupied voxel.  With DSPMAP_DIST_OUTSIDE_OCCUPIED also the minimum over the three axes of min(i_a + 1, n_a - i_a)^2: the
+ *    lattice just outside the map counts as occupied, which pushes a planner away from the edge of the local map.
+ *    d2c = min(D2, R^2) with R = max_voxels, and the value is fl(fl(sqrtf((float)d2c)) * voxel_resolution), sqrt correctly rounded.  All
+ *    integers involved are <= 4096: everything up to the sqrt is exact and the field is defined bit for bit.
+ *  - arguments, checked before the device is touched: a NULL handle, a NaN threshold, max_voxels outside 1 .. 64 or unknown flags are
+ *    DSPMAP_E_ARG; a sharded handle (slab) is DSPMAP_E_STATE (distances cross slabs); without a usable device a valid call is
+ *    DSPMAP_E_DEVICE.
+ *  - snapshot: the build is enqueued on the handle's stream behind everything queued there before (the last frame included) and does not
+ *    synchronise.  It writes into a buffer the handle owns (the buffer and two scratch grids of 1 and 2 bytes per cell are allocated by
+ *    the first build; a handle that never builds a field allocates nothing).  READ-ONLY towards the map: no accumulator is cleared, the
+ *    pending clear is neither armed nor carried out, the captured frame and its parameter ring are not touched.  The field stays valid
+ *    through readouts and dspmap_clear_future (it is a snapshot of the frame it was built from) and becomes STALE with every call that
+ *    computes a new frame or replaces state: dspmap_update*, dspmap_update_depth*, dspmap_mgpu_*, dspmap_stage_predict / update / birth /
+ *    resample, dspmap_import_state, dspmap_clear_state, dspmap_load_checkpoint, dspmap_add_random_particles, dspmap_seed_uniform*.  On a
+ *    stale or never-built field dspmap_distance_field_device returns NULL, dspmap_get_distance_field and dspmap_query_distance* return
+ *    DSPMAP_E_STATE with a text.  A `layer` outside [0, L) is DSPMAP_E_ARG.
+ * dspmap_query_distance*: samples, frame convention, DSPMAP_QUERY_WORLD and the NaN rule are those of dspmap_query_occupancy.
+ *  - layer: t < 0 or T == 0 selects layer 0, otherwise layer 1 + k(t) with the k(t) of dspmap_query_occupancy.
+ *  - a point outside the map, or a sample with a NaN, reads `outside_value` and the gradient (0, 0, 0); otherwise the distance is the
+ *    field at the point's own voxel (dspmap_point_voxel_index's voxel), and the gradient per axis, with index i of n along it:
+ *    lo = max(i - 1, 0), hi = min(i + 1, n - 1), g = fl(fl(F[hi] - F[lo]) / fl((float)(hi - lo) * voxel_resolution)); g = 0 if n == 1.
+ *  - a NULL handle, n < 0, a NULL sample or distance array with n > 0, unknown flags or a NaN outside_value are DSPMAP_E_ARG. */
+#define DSPMAP_DIST_OUTSIDE_OCCUPIED 1
+int dspmap_build_distance_field(dspmap_t* m, float threshold, int max_voxels, int flags);
+const float* dspmap_distance_field_device(dspmap_t* m);            /* [L][V] device memory, NULL if none / stale */
+int dspmap_get_distance_field(dspmap_t* m, int layer, float* out_host);   /* V floats; synchronous */
+/* dist_out_host[i], grad_out_host[3 i .. 3 i + 2] (n x 3, may be NULL) of q_host[i]; synchronous */
+int dspmap_query_distance(dspmap_t* m, int n, const dspmap_query* q_host, int flags, float outside_value, float* dist_out_host,
+                          float* grad_out_host);
+/* the same on device arrays; enqueued on the handle's stream, no synchronisation */
+int dspmap_query_distance_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, float outside_value, float* dist_out_dev,
+                                 float* grad_out_dev);
+
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
 int dspmap_point_voxel_index(const dspmap_t* m, float px, float py, float pz, int* index);
