@@ -1,4 +1,4 @@
-// dspmap_internal.h -- the handle behind dspmap_t and helpers shared by dspmap_api.hip / dspmap_mgpu.hip
+// dspmap_internal.h -- the handle behind dspmap_t and helpers shared by dspmap_api.hip / dspmap_frame.hip / dspmap_mgpu.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -208,6 +208,7 @@ int dspmap_fail(dspmap* m, int code, const char* fmt, ...);
 void dspmap_prof_mark(dspmap* m, int i);
 void dspmap_prof_collect(dspmap* m);
 LaunchCtx dspmap_ctx_of(dspmap* m);
+LaunchCtx dspmap_frame_ctx(dspmap* m);   // ... of a frame or stage: the velocity noise of constructor-seeded particles (vz0) only while m->vz_frames lasts
 void dspmap_mgpu_birth_early(dspmap* m, const LaunchCtx& c);   // the newborn children of a split-phase frame, on the stream the estimator ran on
 void dspmap_resample(dspmap* m, const LaunchCtx& c);   // launch_resample + bookkeeping of the variant it ran
 int dspmap_gate_and_delta(dspmap* m, const float pos[3], double stamp, const float q[4], float dp[3], float* dt);
@@ -216,13 +217,18 @@ int dspmap_device_frame(dspmap* m, int n_points, const float* points_dev, int n_
                         float dt, const float q[4]);
 int dspmap_check_estimator_queue(dspmap* m);   // first thing in every frame entry point: fails once if an earlier frame's cross-queue wait gave up
 void dspmap_freeze_birth_statics(dspmap* m);
+void dspmap_fill_pose(dspmap* m, const float dp[3], float dt);   // sensor pose, displacement, dt and the estimator's / classifier's constants -> m->hp
+int dspmap_cloud_to_host(dspmap* m, int n, const float* points_dev);   // the frame's cloud -> a pinned staging slot (m->pts_pin), async copy
+void dspmap_run_host_estimator(dspmap* m, int n, const float q[4], float dt);   // the host velocity estimator on m->pts_pin -> m->h_birth
+void dspmap_frame_cloud_queued(dspmap* m, int n_points, int n_birth, bool birth_static);   // bookkeeping once prediction and cloud are queued ...
+int dspmap_frame_done(dspmap* m, bool timed);   // ... and once the resampling is: the frame is complete (timed: closes update_ms)
 int dspmap_ensure_point_cap(dspmap* m, int n);
 int dspmap_push_frame_params(dspmap* m);
 void dspmap_flush_future_clear(dspmap* m);   // m->hp -> device
 int dspmap_mark_nb_dirty(dspmap* m);
 void dspmap_dist_free(dspmap* m);
-const FrameParams* dspmap_ring_push(dspmap* m);   // the frame's parameter block into the pinned ring (direct launches); nullptr: no ring
-void dspmap_ring_pushed(dspmap* m);               // after the launches that read the slot were queued
+int dspmap_ring_push(dspmap* m);     // m->hp into its slot of the pinned parameter ring (m->ring_host must exist); the launches take m->ring_dev
+int dspmap_ring_pushed(dspmap* m);   // after the launches that read the slot were queued
 int dspmap_pts_slot_acquire(dspmap* m, int n);   // next pinned staging slot (waits for the copy that last used it) -> m->pts_pin
 int dspmap_pts_slot_release(dspmap* m);          // after queueing the copy that reads / writes m->pts_pin
 int dspmap_stage_points(dspmap* m, int n, int stride, const float* pts);   // host cloud -> m->pts_dev (pinned staging, async copy)

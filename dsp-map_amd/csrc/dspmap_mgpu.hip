@@ -1,8 +1,6 @@
 // dspmap_mgpu.hip -- split-phase frame for Z-slab sharding across GPUs (include/dspmap.h,
 // "multi-GPU split-phase frame").  One process per GPU; the collectives between the phases are
 // issued by the caller through torch.distributed / RCCL on buffers it owns and binds here.
-#include <vector>
-
 #include "dspmap_internal.h"
 
 extern "C" int dspmap_mgpu_bind(dspmap_t* m, long long* ck_dev, int* nstatic_dev, int nstatic_cap) {
@@ -50,20 +48,13 @@ extern "C" int dspmap_mgpu_begin(dspmap_t* m, int n_points, const float* points_
     if (est_host && n_points > 0) {
         // DSPMAP_P_VELOCITY_ESTIMATOR = 1, or a cloud beyond the device estimator's capacity: every rank runs the HOST stage on the
         // replicated cloud (deterministic: the same tagged cloud everywhere), like the unsharded map falls back to it
-        // (dspmap_api.hip: device_frame).  One D2H copy of the cloud and a host synchronisation in such a frame.
-        int rc = dspmap_pts_slot_acquire(m, n_points);
-        if (rc != DSPMAP_OK) return rc;
-        HIPCHK(m, hipMemcpyAsync(m->pts_pin, points_dev, sizeof(float) * 3 * (size_t)n_points, hipMemcpyDeviceToHost, m->stream));
-        rc = dspmap_pts_slot_release(m);
+        // (dspmap_frame.hip: dspmap_device_frame).  One D2H copy of the cloud and a host synchronisation in such a frame.
+        int rc = dspmap_cloud_to_host(m, n_points, points_dev);
         if (rc != DSPMAP_OK) return rc;
         rc = dspmap_ve_state_to_host(m);   // (synchronises the stream: the copy has landed)
         if (rc != DSPMAP_OK) return rc;
         HIPCHK(m, hipStreamSynchronize(m->stream));
-        std::vector<float> view;
-        view.reserve((size_t)n_points * 3);
-        m->vel.rotate_and_filter(m->pts_pin, n_points, q, view);
-        m->vel.run(view, m->cur_pos, dt, m->voxel_filter_res, m->h_birth);
-        m->ve_last_at = 1;
+        dspmap_run_host_estimator(m, n_points, q, dt);
         rc = dspmap_upload_birth(m, m->h_birth.data(), (int)m->h_birth.size());
         if (rc != DSPMAP_OK) return rc;
         birth_dev = reinterpret_cast<const dspmap_vpoint*>(m->s.birth);
@@ -77,15 +68,11 @@ extern "C" int dspmap_mgpu_begin(dspmap_t* m, int n_points, const float* points_
     if (nb_own > m->mgpu_nstatic_cap) return dspmap_fail(m, DSPMAP_E_ARG, "more birth sources than the bound capacity");
     dspmap_freeze_birth_statics(m);
     m->frame_parity ^= 1u;
-    LaunchCtx c = dspmap_ctx_of(m);
-    if (m->vz_frames <= 0) c.s.vz0 = nullptr;
+    LaunchCtx c = dspmap_frame_ctx(m);
     const int mode = birth_dev ? 0 : (want_est ? 2 : 1);
     const bool static_birth = mode != 0;     // the cloud lives on the device (synthesised or estimated)
     m->mgpu_birth = static_birth ? nullptr : (BirthSrc*)birth_dev;
-    for (int i = 0; i < 4; i++) m->hp.quat[i] = m->quat[i];
-    for (int i = 0; i < 3; i++) { m->hp.cur_pos[i] = m->cur_pos[i]; m->hp.od[i] = -dp[i]; }
-    m->hp.dt = dt;
-    m->hp.res_filter = m->voxel_filter_res;
+    dspmap_fill_pose(m, dp, dt);
     m->hp.n_pts = n_points; m->hp.n_birth = nb_own; m->hp.static_birth = mode;
     const int nb_grid = dspmap_begin_cloud(m, n_points, static_birth);
     const int nb = static_birth ? nb_grid : nb_own;   // grid bound of the birth launches
@@ -93,8 +80,8 @@ extern "C" int dspmap_mgpu_begin(dspmap_t* m, int n_points, const float* points_
     m->hp.birth = static_birth ? m->s.birth : m->mgpu_birth;
     // the parameter block travels through the pinned ring (the frame's first kernel fetches it over the bus): a pageable H2D copy
     // makes the host wait for the stream to drain, and every kernel of the frame is then launched into an empty queue
-    const FrameParams* ring = dspmap_ring_push(m);
-    if (!ring) { int rcp = dspmap_push_frame_params(m); if (rcp != DSPMAP_OK) return rcp; }
+    const FrameParams* ring = m->ring_host ? m->ring_dev : nullptr;
+    { const int rcp = ring ? dspmap_ring_push(m) : dspmap_push_frame_params(m); if (rcp != DSPMAP_OK) return rcp; }
     dspmap_prof_collect(m);
     HIPCHK(m, hipEventRecord(m->ev0, m->stream));
     launch_setup_and_bin(c, n_points, false, ring, DSPMAP_RING - 1);
@@ -104,7 +91,7 @@ extern "C" int dspmap_mgpu_begin(dspmap_t* m, int n_points, const float* points_
     if (est_side) HIPCHK(m, hipEventRecord(m->ev_fork, m->stream));
     // + gather + (static tags) the birth rank; k_place follows the exchange: imported movers take part in the sweep-order placement
     launch_predict_only(c, true, nb > 0 && mode != 2);
-    if (ring) dspmap_ring_pushed(m);
+    if (ring) { const int rcp = dspmap_ring_pushed(m); if (rcp != DSPMAP_OK) return rcp; }
     m->mgpu_est_side = false;
     if (mode == 2 && nb > 0) {   // ... with the estimator the rank rides on k_ve_clusters
         if (est_side) {
@@ -122,10 +109,7 @@ extern "C" int dspmap_mgpu_begin(dspmap_t* m, int n_points, const float* points_
     m->mgpu_interior_done = false;
     m->mgpu_birth_early = false;
     m->vz_frames_at_begin = m->vz_frames;
-    if (m->vz_frames > 0) --m->vz_frames;
-    m->last_n_points = n_points;
-    m->last_n_birth = nb;
-    m->last_birth_static = static_birth;
+    dspmap_frame_cloud_queued(m, n_points, nb, static_birth);   // (the resampling, and dspmap_frame_done, follow in dspmap_mgpu_finish)
     HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;
 }
@@ -220,7 +204,7 @@ int dspmap_mgpu_place_phase(dspmap* m) {
     if (m->vz_frames_at_begin <= 0) c.s.vz0 = nullptr;
     // a large slab: only the arrivals of tiles that can see the field of view are registered in pyramids, so only their
     // placement has to precede the weight update -- the others get their slots on the side stream, beside the pair kernels
-    // AND the Ck all-reduce that follows this phase (the same split as the unsharded frame, dspmap_api.hip: enqueue_frame)
+    // AND the Ck all-reduce that follows this phase (the same split as the unsharded frame, dspmap_frame.hip: enqueue_frame)
     m->mgpu_split = !m->mgpu_interior_done && c.k.ntiles >= m->place_split_tiles;
     if (m->mgpu_interior_done) launch_claim(c, 0, 2, m->mgpu_tile_lo, m->mgpu_tile_hi);
     else launch_claim(c, 0, 0, 0, 0, m->mgpu_split ? 1 : -1);
@@ -284,16 +268,11 @@ extern "C" int dspmap_mgpu_weights_and_split(dspmap_t* m) {
 extern "C" int dspmap_mgpu_finish(dspmap_t* m) {
     READY(m);
     m->df_valid = false;
-    LaunchCtx c = dspmap_ctx_of(m);
-    if (m->vz_frames <= 0) c.s.vz0 = nullptr;
+    LaunchCtx c = dspmap_frame_ctx(m);
     if (m->mgpu_side_pending) { HIPCHK(m, hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->mgpu_side_pending = false; }   // (a caller that skipped the weight phase)
     if (!m->mgpu_birth_early) launch_birth_early(c, m->last_n_birth, false);   // caller used the per-direction exports
     launch_birth_finish(c, m->last_n_birth, m->mgpu_all_static);
     m->mgpu_birth_early = false;
     dspmap_resample(m, c);
-    if (m->nb_dirty) { m->nb_dirty = false; m->graph_epoch++; }
-    HIPCHK(m, hipEventRecord(m->ev1, m->stream));
-    m->ev_valid = true;
-    HIPCHK(m, hipGetLastError());
-    return DSPMAP_OK;
+    return dspmap_frame_done(m, true);
 }
