@@ -81,6 +81,11 @@ VPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"),
 RISK_DTYPE = np.dtype([("sum", "f4"), ("max", "f4"), ("first_over", "i4"), ("n_outside", "i4")])
 QUERY_WORLD = 1   # DSPMAP_QUERY_WORLD
 DIST_OUTSIDE_OCCUPIED = 1   # DSPMAP_DIST_OUTSIDE_OCCUPIED
+# dspmap_segment / dspmap_cast_hit (dspmap_cast_segments) and the DSPMAP_CAST_* statuses
+SEGMENT_DTYPE = np.dtype([("ax", "f4"), ("ay", "f4"), ("az", "f4"), ("ta", "f4"), ("bx", "f4"), ("by", "f4"), ("bz", "f4"), ("tb", "f4")])
+HIT_DTYPE = np.dtype([("s", "f4"), ("voxel", "i4"), ("layer", "i4"), ("status", "i4")])
+CAST_FREE, CAST_HIT, CAST_LEFT_MAP, CAST_START_OUTSIDE, CAST_INVALID = range(5)
+CAST_MAX_INFLATE = 8   # DSPMAP_CAST_MAX_INFLATE
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -121,6 +126,11 @@ SIGNATURES = {
     "dspmap_get_distance_field": (_i, [_P, _i, _P]),
     "dspmap_query_distance": (_i, [_P, _i, _P, _i, _f, _P, _P]),
     "dspmap_query_distance_device": (_i, [_P, _i, _P, _i, _f, _P, _P]),
+    "dspmap_build_cast_grid": (_i, [_P, _f, _i, _i]),
+    "dspmap_cast_grid_device": (_P, [_P]),
+    "dspmap_get_cast_grid": (_i, [_P, _i, _P]),
+    "dspmap_cast_segments": (_i, [_P, _i, _P, _i, _P]),
+    "dspmap_cast_segments_device": (_i, [_P, _i, _P, _i, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -575,6 +585,52 @@ class DSPMap:
         g = np.zeros((n, 3), np.float32) if grad else None
         self._chk(self.L.dspmap_query_distance(self.h, n, _ptr(q), flags, float(outside), _ptr(dist), _ptr(g)))
         return (dist, g) if grad else dist
+
+    # -- segment casts (extension; semantics in include/dspmap.h next to dspmap_build_cast_grid)
+    def build_cast_grid(self, threshold, inflate_voxels=0):
+        """enqueue the bit grids of all T + 1 layers (0: current mass, 1 + k: horizon k) on the handle's stream: a voxel's bit is set iff
+        some voxel within inflate_voxels (Chebyshev, 0 .. 8) has mass > threshold.  Read-only towards the map; the grid is a snapshot and
+        goes stale with the next frame."""
+        self._chk(self.L.dspmap_build_cast_grid(self.h, float(threshold), int(inflate_voxels), 0))
+
+    def cast_grid(self, layer=None):
+        """the grid of one layer as numpy uint64 [nz, ny, W], W = ceil(nx / 64), bit (x & 63) of word (x >> 6) = voxel x of the row; or
+        of all layers [L, nz, ny, W] (synchronous host copies)"""
+        shape = (self.cfg.nz, self.cfg.ny, (self.cfg.nx + 63) // 64)
+        layers = range(self.T + 1) if layer is None else [int(layer)]
+        out = np.zeros((len(layers),) + shape, np.uint64)
+        for j, l in enumerate(layers):
+            self._chk(self.L.dspmap_get_cast_grid(self.h, l, _ptr(out[j])))
+        return out if layer is None else out[0]
+
+    def cast_grid_ptr(self):
+        """device address of the [L][nz][ny][W] uint64 grid, or None when there is none / it is stale"""
+        return self.L.dspmap_cast_grid_device(self.h) or None
+
+    def cast_segments(self, seg, world=False):
+        """first blocked cell of every segment {ax, ay, az, ta, bx, by, bz, tb} of seg ([n, 8] float32) through the cast grid: the cell
+        entered at parameter s is tested in the layer of the time ta + s (tb - ta) (ta < 0: the current layer).  numpy in ->
+        structured numpy (HIT_DTYPE: s, voxel, layer, status = CAST_*) out, synchronous; a torch tensor on the GPU -> dict of tensors
+        's' (float32), 'voxel', 'layer', 'status' (int32) on the same device, enqueued on the handle's stream and ordered with torch's
+        current stream like query_occupancy."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(seg):
+            import torch
+            q = self._device_samples(seg, (8,), "cast_segments")
+            n = q.numel() // 8
+            raw = torch.empty((n, 4), dtype=torch.int32, device=q.device)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_cast_segments_device(self.h, n, q.data_ptr(), flags, raw.data_ptr()))
+            after()
+            return {"s": raw[:, 0].view(torch.float32), "voxel": raw[:, 1], "layer": raw[:, 2], "status": raw[:, 3]}
+        q = np.ascontiguousarray(seg, np.float32)
+        if q.shape[-1:] != (8,):
+            raise ValueError("cast_segments: segments of shape [n, 8]")
+        n = q.size // 8
+        out = np.zeros(n, HIT_DTYPE)
+        self._chk(self.L.dspmap_cast_segments(self.h, n, _ptr(q), flags, _ptr(out)))
+        return out
 
     def getVoxelPositionFromIndexPublic(self, index):
         x, y, z = C.c_float(), C.c_float(), C.c_float()

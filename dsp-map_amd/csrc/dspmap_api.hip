@@ -227,6 +227,8 @@ static void free_dev(dspmap* m) {
     if (m->q_buf) { chk(hipFree(m->q_buf), "hipFree"); m->q_buf = nullptr; m->q_buf_bytes = 0; }
     for (void* q : {(void*)m->df_field, (void*)m->df_g8, (void*)m->df_h16}) if (q) chk(hipFree(q), "hipFree");
     m->df_field = nullptr; m->df_g8 = nullptr; m->df_h16 = nullptr; m->df_valid = false;
+    for (void* q : {(void*)m->cg_bits, (void*)m->cg_tmp}) if (q) chk(hipFree(q), "hipFree");
+    m->cg_bits = nullptr; m->cg_tmp = nullptr; m->cg_valid = false;
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
@@ -1012,6 +1014,91 @@ extern "C" int dspmap_query_distance_device(dspmap_t* m, int n, const dspmap_que
     return DSPMAP_OK;
 }
 
+// --------------------------------------------------- segment casts (dspmap_cast.hip; semantics in include/dspmap.h)
+static size_t cast_layer_words(const MapDims& d) { return (size_t)d.nz * d.ny * (size_t)((d.nx + 63) >> 6); }
+extern "C" int dspmap_build_cast_grid(dspmap_t* m, float thr, int inflate_voxels, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (thr != thr) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: threshold is NaN");
+    if (inflate_voxels < 0 || inflate_voxels > DSPMAP_CAST_MAX_INFLATE)
+        return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: inflate_voxels %d outside [0, %d]", inflate_voxels, DSPMAP_CAST_MAX_INFLATE);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: unknown flags 0x%x", flags);
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "cast grid: a slab handle holds part of the map; casts cross slabs");
+    const MapDims& d = m->d;
+    const size_t words = (size_t)(d.T + 1) * cast_layer_words(d);
+    if (words > 0x7fffffffull) return dspmap_fail(m, DSPMAP_E_STATE, "cast grid: %zu words exceed INT_MAX", words);
+    READY(m);
+    BENIGN(m);
+    m->cg_valid = false;
+    if (!m->cg_bits) {
+        HIPCHK(m, hipMalloc(&m->cg_bits, sizeof(u64) * words));
+        HIPCHK(m, hipMalloc(&m->cg_tmp, sizeof(u64) * words));
+    }
+    CastGridArgs a;
+    a.thr = thr; a.r = inflate_voxels;
+    a.fut_zero = m->fut_clear_pending ? 1 : 0;   // read, never changed (as the queries)
+    a.L = d.T + 1;
+    a.bits = m->cg_bits; a.tmp = m->cg_tmp;
+    launch_cast_grid(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    m->cg_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" const unsigned long long* dspmap_cast_grid_device(dspmap_t* m) { return (m && m->cg_valid) ? m->cg_bits : nullptr; }
+static int cast_grid_ready(dspmap* m, const char* what) {
+    if (!m->cg_valid)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no cast grid, or the map has changed since it was built (dspmap_build_cast_grid)", what);
+    if (m->device >= 0) (void)hipSetDevice(m->device);
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_cast_grid(dspmap_t* m, int layer, unsigned long long* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: NULL output array");
+    if (layer < 0 || layer > m->d.T) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: layer %d outside [0, %d)", layer, m->d.T + 1);
+    const int rc = cast_grid_ready(m, "dspmap_get_cast_grid");
+    if (rc != DSPMAP_OK) return rc;
+    const size_t lw = cast_layer_words(m->d);
+    HIPCHK(m, hipMemcpyAsync(out, m->cg_bits + lw * layer, sizeof(u64) * lw, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+static int cast_check(dspmap* m, int n, const void* in, const void* out, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "cast: negative segment count %d", n);
+    if (n > 0 && (!in || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "cast: NULL segment or output array");
+    if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "cast: unknown flags 0x%x", flags);
+    return cast_grid_ready(m, "dspmap_cast_segments");
+}
+static CastArgs cast_args(const dspmap* m, int flags) {
+    CastArgs a;
+    a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a.ox = m->cur_pos[0]; a.oy = m->cur_pos[1]; a.oz = m->cur_pos[2];
+    a.bits = m->cg_bits;
+    return a;
+}
+extern "C" int dspmap_cast_segments(dspmap_t* m, int n, const dspmap_segment* seg, int flags, dspmap_cast_hit* out) {
+    int rc = cast_check(m, n, seg, out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    const size_t sb = q_align(sizeof(dspmap_segment) * (size_t)n);
+    if ((rc = query_buf(m, sb + sizeof(dspmap_cast_hit) * (size_t)n)) != DSPMAP_OK) return rc;
+    dspmap_segment* ds = (dspmap_segment*)m->q_buf;
+    dspmap_cast_hit* dh = (dspmap_cast_hit*)((char*)m->q_buf + sb);
+    HIPCHK(m, hipMemcpyAsync(ds, seg, sizeof(dspmap_segment) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    launch_cast(dspmap_ctx_of(m), cast_args(m, flags), n, ds, dh);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(out, dh, sizeof(dspmap_cast_hit) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_cast_segments_device(dspmap_t* m, int n, const dspmap_segment* seg, int flags, dspmap_cast_hit* out) {
+    const int rc = cast_check(m, n, seg, out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    launch_cast(dspmap_ctx_of(m), cast_args(m, flags), n, seg, out);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+
 extern "C" void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz) {  // :1556-1572
     const MapDims& d = m->d;
     const int zc = d.ny * d.nx;
@@ -1080,7 +1167,7 @@ int dspmap_mark_nb_dirty(dspmap* m) {
 
 extern "C" int dspmap_clear_state(dspmap_t* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     m->state_epoch++;
     const MapDims& d = m->d;
     const size_t W = (size_t)d.v_loc * d.mw;
@@ -1103,7 +1190,7 @@ extern "C" int dspmap_clear_state(dspmap_t* m) {
 
 extern "C" int dspmap_import_state(dspmap_t* m, int n, const int* voxel, const int* slot, const float* rec8) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     m->state_epoch++;
     if (n < 0 || (n > 0 && (!voxel || !rec8))) return DSPMAP_E_ARG;
     if (n == 0) return DSPMAP_OK;
@@ -1158,7 +1245,7 @@ extern "C" int dspmap_export_state(dspmap_t* m, int cap, int* voxel, int* slot, 
 
 extern "C" int dspmap_add_random_particles(dspmap_t* m, int n, float weight) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     m->state_epoch++;
     if (n < 0) return DSPMAP_E_ARG;
     int rc = ensure_vz(m);
@@ -1177,7 +1264,7 @@ extern "C" int dspmap_add_random_particles(dspmap_t* m, int n, float weight) {
 
 extern "C" int dspmap_seed_uniform_moving(dspmap_t* m, int per_voxel, float weight, unsigned seed, float vmax) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     m->state_epoch++;
     if (per_voxel < 0 || per_voxel > m->d.slots) return dspmap_fail(m, DSPMAP_E_ARG, "per_voxel must be in [0, %d]", m->d.slots);
     if (!(vmax >= 0.f)) return dspmap_fail(m, DSPMAP_E_ARG, "vmax must be >= 0");
@@ -1475,7 +1562,7 @@ extern "C" int dspmap_save_checkpoint(dspmap_t* m, const char* path) {
 
 extern "C" int dspmap_load_checkpoint(dspmap_t* m, const char* path) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     if (!path) return DSPMAP_E_ARG;
     FILE* f = fopen(path, "rb");
     if (!f) return dspmap_fail(m, DSPMAP_E_ARG, "cannot open %s", path);

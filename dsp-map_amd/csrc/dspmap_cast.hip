@@ -1,0 +1,174 @@
+// dspmap_cast.hip -- segment casts through a bit grid of the current and the predicted occupancy (dspmap_build_cast_grid,
+// dspmap_cast_segments*; semantics next to them in include/dspmap.h).  The reference has no counterpart: a planner that asks "is the
+// straight segment a -> b free, and where is it blocked first?" copies the whole grid out (getOccupancyMapWithFutureStatus :405-426)
+// and walks it on the host.
+//
+// The grid: one bit per voxel and layer (0: current mass, 1 + k: horizon k) in the reference's voxel order, [L][nz][ny][W] 64-bit words.
+//   k_cast_pack        one wave per (row, layer): the masses are read in place and in storage order and balloted into words
+//                      (df_row_word, the ballot k_dist_x of dspmap_distance.hip takes its distances from).
+//   k_cast_inflate_xy  (r > 0) one lane per word, lanes along the words of a row: OR of the 2r + 1 rows y - r .. y + r of the word and its
+//                      two neighbours, then the x dilation as shifts by 1 .. r both ways with the carries out of the neighbouring words
+//                      (OR commutes with shifts: one dilation after the ORs).  The pad bits of a row's last word are masked off again.
+//   k_cast_inflate_z   (r > 0) one lane per word: OR over the 2r + 1 planes z - r .. z + r.  Nothing is transposed; rows outside the map
+//                      contribute nothing, which is the Chebyshev ball clipped at the faces.
+//
+// The cast: ONE LANE PER SEGMENT, a plain Amanatides-Woo loop per lane -- two 16-byte loads in, one 16-byte store out.  A lane keeps the
+// 64-bit word of its current (layer, row, x >> 6) in registers and loads again only when that key changes: steps along x inside a word
+// cost no memory access.  The layer of the time a cell is LEFT is carried over as the layer of the time the next one is ENTERED (the two
+// are the same fp32 expression of the same parameter), so a space-time cast evaluates k(t) once per cell.
+// Divergence of the trip counts between the lanes of a wave is the cost that remains, and the plain loop is the answer chosen here.
+// A coarse any-bit-per-4x4x4 grid or a word-level skip along x would have to advance the IDENTICAL fp32 DDA state (tMax += tDelta per
+// crossed face, in the same order) through the skipped cells to leave s and the LEFT_MAP cell bit-exact, so a skip saves loads, not
+// steps -- and the loads are already rare: the grids are 0.3 MB (66 x 66 x 40, 7 layers) to a few MB and sit in L2, the register word
+// covers the x steps, and segments of a planner's batch that start near each other share lines.  What a skip structure adds is a
+// second snapshot to build per layer and a second test per step in every lane.  A segment of 3 m at 0.15 m crosses ~20 - 35 cells;
+// 131 072 of them are 2 048 waves, eight per CU, whose long lanes overlap other waves' loads.
+#include "dspmap_device.h"
+#include "dspmap_internal.h"
+
+#define CAST_TPB 256
+#define CAST_WAVES (CAST_TPB / 64)
+
+__global__ void __launch_bounds__(CAST_TPB) k_cast_pack(MapDims d, DevState s, CastGridArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * CAST_WAVES + (threadIdx.x >> 6);   // y + ny * z
+    const int layer = blockIdx.y;
+    if (row >= d.ny * d.nz) return;   // (wave-uniform: the ballots below see whole waves)
+    const int z = row / d.ny, y = row - z * d.ny;
+    const int nw = (d.nx + 63) >> 6;
+    u64* out = a.bits + ((size_t)layer * d.ny * d.nz + row) * nw;
+    for (int w = 0; w < nw; ++w) {
+        const u64 word = df_row_word(d, s, a.thr, a.fut_zero, layer, w * 64 + lane, y, z);
+        if (lane == 0) out[w] = word;
+    }
+}
+
+// bits -> tmp: OR over the rows y - r .. y + r of the same plane, dilated by r along x
+__global__ void __launch_bounds__(CAST_TPB) k_cast_inflate_xy(MapDims d, CastGridArgs a, unsigned n_words) {
+    const unsigned t = blockIdx.x * CAST_TPB + threadIdx.x;
+    if (t >= n_words) return;
+    const unsigned nw = (unsigned)(d.nx + 63) >> 6;
+    const unsigned w = t % nw, row = t / nw;          // row = y + ny * (z + nz * layer)
+    const int y = (int)(row % (unsigned)d.ny);
+    const int y0 = max(y - a.r, 0), y1 = min(y + a.r, d.ny - 1);
+    u64 c = 0, p = 0, q = 0;                          // the word, the one below it along x, the one above
+    for (int yy = y0; yy <= y1; ++yy) {
+        const u64* in = a.bits + ((size_t)row - y + yy) * nw + w;
+        c |= in[0];
+        if (w > 0) p |= in[-1];
+        if (w + 1 < nw) q |= in[1];
+    }
+    u64 o = c;
+    for (int sft = 1; sft <= a.r; ++sft) o |= (c << sft) | (c >> sft) | (p >> (64 - sft)) | (q << (64 - sft));
+    if (w + 1 == nw && (d.nx & 63)) o &= ~0ull >> (64 - (d.nx & 63));   // bits at x >= nx stay 0
+    a.tmp[t] = o;
+}
+
+// tmp -> bits: OR over the planes z - r .. z + r of the same layer
+__global__ void __launch_bounds__(CAST_TPB) k_cast_inflate_z(MapDims d, CastGridArgs a, unsigned n_words) {
+    const unsigned t = blockIdx.x * CAST_TPB + threadIdx.x;
+    if (t >= n_words) return;
+    const unsigned plane = (unsigned)d.ny * ((unsigned)(d.nx + 63) >> 6);
+    const int z = (int)((t / plane) % (unsigned)d.nz);
+    const int z0 = max(z - a.r, 0), z1 = min(z + a.r, d.nz - 1);
+    u64 o = 0;
+    for (int zz = z0; zz <= z1; ++zz) o |= a.tmp[(long long)t + (long long)(zz - z) * (long long)plane];
+    a.bits[t] = o;
+}
+
+// one axis of the DDA set-up (include/dspmap.h, steps 2 and 3); pa is inside the map along this axis
+__device__ __forceinline__ void cast_axis(float pa, float pb, float half, float res, int& i, int& st, float& tmax, float& tdelta) {
+    const float ua = __fdiv_rn(__fadd_rn(pa, half), res), ub = __fdiv_rn(__fadd_rn(pb, half), res);
+    i = (int)ua;
+    const float dd = __fsub_rn(ub, ua);
+    st = dd > 0.f ? 1 : (dd < 0.f ? -1 : 0);
+    tmax = INFINITY;
+    tdelta = 0.f;
+    if (st != 0) {
+        const float bnd = (float)(i + (st > 0 ? 1 : 0));
+        tmax = __fdiv_rn(__fsub_rn(bnd, ua), dd);
+        tdelta = __fdiv_rn(1.0f, fabsf(dd));
+    }
+}
+__device__ __forceinline__ bool cast_finite(float v) { return fabsf(v) < INFINITY; }   // (false for NaN)
+
+__global__ void __launch_bounds__(CAST_TPB) k_cast(MapDims d, CastArgs a, int n, const float4* __restrict__ seg, int4* __restrict__ out) {
+    const unsigned i = blockIdx.x * CAST_TPB + threadIdx.x;   // (unsigned: n may come within a block of INT_MAX)
+    if (i >= (unsigned)n) return;
+    const float4 A = seg[2 * (size_t)i], B = seg[2 * (size_t)i + 1];   // {ax, ay, az, ta}, {bx, by, bz, tb}
+    float s = 0.f;
+    int voxel = -1, layer = -1, status = DSPMAP_CAST_INVALID;
+    const bool valid = cast_finite(A.x) && cast_finite(A.y) && cast_finite(A.z) && cast_finite(B.x) && cast_finite(B.y) && cast_finite(B.z) &&
+                       A.w == A.w && B.w == B.w;
+    if (valid) {
+        float ax = A.x, ay = A.y, az = A.z, bx = B.x, by = B.y, bz = B.z;
+        if (a.world) {
+            ax = __fsub_rn(ax, a.ox); ay = __fsub_rn(ay, a.oy); az = __fsub_rn(az, a.oz);
+            bx = __fsub_rn(bx, a.ox); by = __fsub_rn(by, a.oy); bz = __fsub_rn(bz, a.oz);
+        }
+        int ix = 0, iy = 0, iz = 0, sx = 0, sy = 0, sz = 0;
+        float tmx = INFINITY, tmy = INFINITY, tmz = INFINITY, tdx = 0.f, tdy = 0.f, tdz = 0.f;
+        bool inside = !(fabsf(ax) >= d.half_x || fabsf(ay) >= d.half_y || fabsf(az) >= d.half_z);   // dspmap_point_voxel_index's test
+        if (inside) {
+            cast_axis(ax, bx, d.half_x, d.res, ix, sx, tmx, tdx);
+            cast_axis(ay, by, d.half_y, d.res, iy, sy, tmy, tdy);
+            cast_axis(az, bz, d.half_z, d.res, iz, sz, tmz, tdz);
+            inside = ix < d.nx && iy < d.ny && iz < d.nz;   // (all >= 0: p > -half)
+        }
+        status = DSPMAP_CAST_START_OUTSIDE;
+        if (inside) {
+            const bool timed = !(A.w < 0.f) && d.T > 0;
+            const float dt = __fsub_rn(B.w, A.w);
+            const size_t nw = (size_t)(d.nx + 63) >> 6, rows = (size_t)d.ny * d.nz;
+            int l_in = timed ? q_horizon(d, __fadd_rn(A.w, __fmul_rn(0.f, dt))) + 1 : 0;
+            size_t key = ~(size_t)0;
+            u64 word = 0;
+            float s_in = 0.f;
+            status = DSPMAP_CAST_INVALID;   // (never left standing: the loop below ends within nx + ny + nz steps)
+            const int max_steps = d.nx + d.ny + d.nz;
+            for (int it = 0; it <= max_steps; ++it) {
+                const bool mx = tmx <= tmy && tmx <= tmz;
+                const bool my = !mx && tmy <= tmz;
+                const float tm = mx ? tmx : (my ? tmy : tmz);
+                int l_out = 0;
+                if (timed) l_out = q_horizon(d, __fadd_rn(A.w, __fmul_rn(fminf(tm, 1.f), dt))) + 1;
+                const int l0 = min(l_in, l_out), l1 = max(l_in, l_out);
+                const size_t cell = ((size_t)iz * d.ny + iy) * nw + ((unsigned)ix >> 6);
+                int l = l0;
+                for (; l <= l1; ++l) {
+                    const size_t k = (size_t)l * rows * nw + cell;
+                    if (k != key) { word = a.bits[k]; key = k; }
+                    if ((word >> (ix & 63)) & 1ull) break;
+                }
+                const int here = (iz * d.ny + iy) * d.nx + ix;
+                if (l <= l1) { s = s_in; voxel = here; layer = l; status = DSPMAP_CAST_HIT; break; }
+                if (!(tm <= 1.f)) { s = 1.f; status = DSPMAP_CAST_FREE; break; }
+                s_in = tm;
+                l_in = l_out;   // t_in of the next cell is t_out of this one: the same expression of the same parameter (tm <= 1)
+                bool left;
+                if (mx) { ix += sx; tmx = __fadd_rn(tm, tdx); left = (unsigned)ix >= (unsigned)d.nx; }
+                else if (my) { iy += sy; tmy = __fadd_rn(tm, tdy); left = (unsigned)iy >= (unsigned)d.ny; }
+                else { iz += sz; tmz = __fadd_rn(tm, tdz); left = (unsigned)iz >= (unsigned)d.nz; }
+                if (left) { s = s_in; voxel = here; status = DSPMAP_CAST_LEFT_MAP; break; }
+            }
+        }
+    }
+    out[i] = make_int4(__float_as_int(s), voxel, layer, status);
+}
+
+void launch_cast_grid(const LaunchCtx& c, const CastGridArgs& a) {
+    const MapDims& d = c.d;
+    const int rows = d.ny * d.nz;
+    hipLaunchKernelGGL(k_cast_pack, dim3((rows + CAST_WAVES - 1) / CAST_WAVES, a.L), dim3(CAST_TPB), 0, c.stream, d, c.s, a);
+    if (a.r <= 0) return;
+    const unsigned n_words = (unsigned)((size_t)a.L * rows * ((d.nx + 63) >> 6));   // (< 2^31: dspmap_build_cast_grid refuses more)
+    const dim3 g((n_words + CAST_TPB - 1) / CAST_TPB);
+    hipLaunchKernelGGL(k_cast_inflate_xy, g, dim3(CAST_TPB), 0, c.stream, d, a, n_words);
+    hipLaunchKernelGGL(k_cast_inflate_z, g, dim3(CAST_TPB), 0, c.stream, d, a, n_words);
+}
+
+void launch_cast(const LaunchCtx& c, const CastArgs& a, int n, const dspmap_segment* seg, dspmap_cast_hit* out) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_cast, dim3((unsigned)(((long long)n + CAST_TPB - 1) / CAST_TPB)), dim3(CAST_TPB), 0, c.stream, c.d, a, n,
+                       (const float4*)seg, (int4*)out);
+}

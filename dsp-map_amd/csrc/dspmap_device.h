@@ -350,6 +350,19 @@ __device__ __forceinline__ int q_horizon(const MapDims& d, float t) {
     return k;
 }
 
+// occupancy word of 64 cells of a row of layer `layer` (0: the current mass, 1 + k: horizon k), balloted by one whole wave: bit l = voxel
+// (x0 + l, y, z) has mass > thr.  The masses are read in place and in storage order (what dspmap_query.hip reads); fut_zero: a clear of the
+// future accumulators is pending, the layers >= 1 read 0.  Cells at x >= nx give 0 bits.  (dspmap_distance.hip, dspmap_cast.hip)
+__device__ __forceinline__ u64 df_row_word(const MapDims& d, const DevState& s, float thr, int fut_zero, int layer, int x, int y, int z) {
+    bool occ = false;
+    if (x < d.nx) {
+        const int lv = lv_of_xyz(d, x, y, z);   // (unsharded: z_lo == 0)
+        const float mass = layer == 0 ? s.res4[lv].x : (fut_zero ? 0.f : fut_status_at(d, s, lv, layer - 1));
+        occ = mass > thr;
+    }
+    return __builtin_amdgcn_ballot_w64(occ);
+}
+
 // entries of pyramid b's range-sorted particle list (what the pair kernels read): the list as registered, cut to the reference's
 // capacity -- on a sharded map in a frame with a global cut, what THIS rank keeps of it
 __device__ __forceinline__ int pyr_len(const MapDims& d, const DevState& s, int b) {

@@ -25,17 +25,7 @@
 #define DF_TS 32      // output rows of the scanned axis per workgroup (passes 2 and 3)
 #define DF_RMAX 64    // largest truncation radius (dspmap_build_distance_field refuses more)
 
-// occupancy word of 64 cells of a row: bit l = voxel (w * 64 + l, y, z) of the layer is occupied
-__device__ __forceinline__ u64 df_row_word(const MapDims& d, const DevState& s, const DistArgs& a, int layer, int x, int y, int z) {
-    bool occ = false;
-    if (x < d.nx) {
-        const int lv = lv_of_xyz(d, x, y, z);   // (unsharded: z_lo == 0)
-        const float mass = layer == 0 ? s.res4[lv].x : (a.fut_zero ? 0.f : fut_status_at(d, s, lv, layer - 1));
-        occ = mass > a.thr;
-    }
-    return __builtin_amdgcn_ballot_w64(occ);
-}
-
+// (df_row_word, the occupancy word of 64 cells of a row, lives in dspmap_device.h: dspmap_cast.hip packs its grid with it too)
 __global__ void __launch_bounds__(DF_TPB) k_dist_x(MapDims d, DevState s, DistArgs a) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * DF_WAVES + (threadIdx.x >> 6);   // y + ny * z
@@ -45,9 +35,9 @@ __global__ void __launch_bounds__(DF_TPB) k_dist_x(MapDims d, DevState s, DistAr
     const int nw = (d.nx + 63) >> 6;
     const int cap = a.R + 1;
     unsigned char* out = a.g8 + ((size_t)layer * d.v_glob + (size_t)row * d.nx);
-    u64 prev = 0, cur = df_row_word(d, s, a, layer, lane, y, z);
+    u64 prev = 0, cur = df_row_word(d, s, a.thr, a.fut_zero, layer, lane, y, z);
     for (int w = 0; w < nw; ++w) {
-        const u64 next = w + 1 < nw ? df_row_word(d, s, a, layer, (w + 1) * 64 + lane, y, z) : 0;
+        const u64 next = w + 1 < nw ? df_row_word(d, s, a.thr, a.fut_zero, layer, (w + 1) * 64 + lane, y, z) : 0;
         // nearest set bit at or below the lane: in its own word, else the top one of the word before (anything further is > 64 cells away)
         const u64 ml = cur & (~0ull >> (63 - lane));
         const int dl = ml ? lane - (63 - __builtin_clzll(ml)) : (prev ? lane + 1 + __builtin_clzll(prev) : cap);

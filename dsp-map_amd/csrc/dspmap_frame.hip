@@ -101,7 +101,7 @@ int dspmap_gate_and_delta(dspmap* m, const float pos[3], double stamp, const flo
     m->last_stamp = stamp;
     m->dt_last = *dt;
     m->update_time += *dt; m->update_counter += 1;   // mapPrediction :634-635
-    m->df_valid = false;   // a new frame: a distance field is a snapshot of the one before
+    dspmap_snapshots_stale(m);   // a new frame: a distance field / cast grid is a snapshot of the one before
     for (int i = 0; i < 4; i++) m->quat[i] = q[i];
     return 1;
 }
@@ -807,7 +807,7 @@ extern "C" int dspmap_set_current_position(dspmap_t* m, float x, float y, float 
 }
 extern "C" int dspmap_stage_predict(dspmap_t* m, float dx, float dy, float dz, float dt) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     m->frame_parity ^= 1u;
     LaunchCtx c = dspmap_frame_ctx(m);
     fill_sensor(m);   // (not dspmap_fill_pose: the stage leaves res_filter and birth_reach as they are)
@@ -825,7 +825,7 @@ extern "C" int dspmap_stage_predict(dspmap_t* m, float dx, float dy, float dz, f
 }
 extern "C" int dspmap_stage_update(dspmap_t* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     LaunchCtx c = dspmap_ctx_of(m);
     launch_ck_partial(c);
     launch_weight_update(c);
@@ -835,7 +835,7 @@ extern "C" int dspmap_stage_update(dspmap_t* m) {
 }
 extern "C" int dspmap_stage_birth(dspmap_t* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     dspmap_freeze_birth_statics(m);
     int nb = m->last_n_birth;
     if (m->h_birth_valid) {
@@ -856,7 +856,7 @@ extern "C" int dspmap_stage_birth(dspmap_t* m) {
 }
 extern "C" int dspmap_stage_resample(dspmap_t* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     dspmap_flush_future_clear(m);   // a pending clear must not wipe what this stage accumulates
     LaunchCtx c = dspmap_frame_ctx(m);
     dspmap_resample(m, c);

@@ -178,6 +178,10 @@ struct dspmap {
     // device state.  df_valid: the field is a snapshot of the map as it is -- cleared by everything that computes a frame or replaces state
     float* df_field = nullptr; unsigned char* df_g8 = nullptr; unsigned short* df_h16 = nullptr;
     bool df_valid = false;
+    // cast grid (dspmap_build_cast_grid): one bit per voxel, [L][nz][ny][W] words, and the inflation's scratch grid of the same size; allocated
+    // by the first build, freed with the device state.  cg_valid: the life cycle of df_valid (dspmap_snapshots_stale)
+    u64* cg_bits = nullptr; u64* cg_tmp = nullptr;
+    bool cg_valid = false;
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;
@@ -204,6 +208,8 @@ struct dspmap {
     float event_overhead_ms = 0.f;   // calibrated by dspmap_set_profiling(1): what an event bracket adds to the one kernel inside it
 };
 
+// everything that computes a frame or replaces state calls this: the distance field and the cast grid are snapshots of the map before it
+inline void dspmap_snapshots_stale(dspmap* m) { m->df_valid = false; m->cg_valid = false; }
 int dspmap_fail(dspmap* m, int code, const char* fmt, ...);
 void dspmap_prof_mark(dspmap* m, int i);
 void dspmap_prof_collect(dspmap* m);

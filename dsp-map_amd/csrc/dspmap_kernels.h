@@ -169,6 +169,25 @@ struct DistQueryArgs {
 };
 // dist[i] = the field at sample q[i]'s own voxel in the layer its t selects, grad[3 i ..] (optional) = its central / one-sided differences
 void launch_distance_query(const LaunchCtx& c, const DistQueryArgs& a, int n, const float4* q, float* dist, float* grad);
+// segment casts through a bit grid of the current and the predicted occupancy (dspmap_cast.hip; semantics in include/dspmap.h,
+// dspmap_build_cast_grid).  The grid is in the reference's voxel order: [L][nz][ny][W] words, W = ceil(nx / 64)
+struct CastGridArgs {
+    float thr;           // a voxel is occupied iff its mass > thr (as DistArgs)
+    int r;               // Chebyshev inflation radius in voxels, 0 .. DSPMAP_CAST_MAX_INFLATE
+    int fut_zero;        // 1: a clear of the future accumulators is pending -- the layers >= 1 are empty
+    int L;               // layers: T + 1
+    u64* bits;           // [L][nz][ny][W] the grid
+    u64* tmp;            // the same size: the grid after the x and y passes of the inflation
+};
+void launch_cast_grid(const LaunchCtx& c, const CastGridArgs& a);
+struct CastArgs {
+    float ox, oy, oz;    // as QueryArgs
+    int world;
+    const u64* bits;     // [L][nz][ny][W]
+};
+struct dspmap_segment;
+struct dspmap_cast_hit;
+void launch_cast(const LaunchCtx& c, const CastArgs& a, int n, const struct dspmap_segment* seg, struct dspmap_cast_hit* out);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

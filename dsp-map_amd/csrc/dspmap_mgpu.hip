@@ -150,7 +150,7 @@ extern "C" int dspmap_mgpu_export_both(dspmap_t* m, float* up_dev_out, float* do
 // tiles.  Gives the GPU work for the time the driver spends synchronising with the host to size the exchange.
 extern "C" int dspmap_mgpu_place_interior(dspmap_t* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     if (!m->mgpu_place_pending || m->mgpu_interior_done) return DSPMAP_OK;
     if (m->vz_frames_at_begin > 0) return DSPMAP_OK;   // constructor-seeded particles still carry vz: no bound on the layer change
     const MapDims& d = m->d;
@@ -176,7 +176,7 @@ extern "C" int dspmap_mgpu_set_export_counts(dspmap_t* m, int n_up, int n_down) 
 
 extern "C" int dspmap_mgpu_import(dspmap_t* m, int n, const float* rec_dev) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     if (n < 0 || (n > 0 && !rec_dev)) return DSPMAP_E_ARG;
     LaunchCtx c = dspmap_ctx_of(m);
     launch_import_movers(c, n, rec_dev);
@@ -198,7 +198,7 @@ void dspmap_mgpu_birth_early(dspmap* m, const LaunchCtx& c) {
 // the phase in two halves, so that the C++ driver (dspmap_dist.hip) can select the pyramid lists' GLOBAL cut between them
 int dspmap_mgpu_place_phase(dspmap* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     if (!m->mgpu_place_pending) return DSPMAP_OK;
     LaunchCtx c = dspmap_ctx_of(m);
     if (m->vz_frames_at_begin <= 0) c.s.vz0 = nullptr;
@@ -216,7 +216,7 @@ int dspmap_mgpu_place_phase(dspmap* m) {
 }
 int dspmap_mgpu_ck_phase(dspmap* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     LaunchCtx c = dspmap_ctx_of(m);   // (carries DevState::pyr_kstar when the driver selected a global cut for this frame)
     if (m->mgpu_placed) {
         m->mgpu_placed = false;
@@ -255,7 +255,7 @@ extern "C" int dspmap_mgpu_ck_partial(dspmap_t* m) {
 
 extern "C" int dspmap_mgpu_weights_and_split(dspmap_t* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     LaunchCtx c = dspmap_ctx_of(m);
     launch_weight_update(c);
     if (m->mgpu_side_pending) { HIPCHK(m, hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->mgpu_side_pending = false; }   // the side placement
@@ -267,7 +267,7 @@ extern "C" int dspmap_mgpu_weights_and_split(dspmap_t* m) {
 
 extern "C" int dspmap_mgpu_finish(dspmap_t* m) {
     READY(m);
-    m->df_valid = false;
+    dspmap_snapshots_stale(m);
     LaunchCtx c = dspmap_frame_ctx(m);
     if (m->mgpu_side_pending) { HIPCHK(m, hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->mgpu_side_pending = false; }   // (a caller that skipped the weight phase)
     if (!m->mgpu_birth_early) launch_birth_early(c, m->last_n_birth, false);   // caller used the per-direction exports

@@ -269,6 +269,14 @@ public:
                       float outside_value = 0.f) {
         return dspmap_query_distance(h_, n, samples, world_frame ? DSPMAP_QUERY_WORLD : 0, outside_value, distances, gradients);
     }
+    /* extensions: segment casts through bit grids of the current (layer 0) and the predicted (layer 1 + k) occupancy, built and kept on the
+     * device (dspmap_build_cast_grid in dspmap.h): hits[i] = the first cell of segs[i] = {a, ta, b, tb} whose bit is set, tested in the
+     * horizon of the time the segment enters it.  Read-only towards the map; a grid is a snapshot and goes stale with the next update().
+     * Return DSPMAP_OK or a negative error code. */
+    int buildCastGrid(float thr = 0.2f, int inflate = 0) { return dspmap_build_cast_grid(h_, thr, inflate, 0); }
+    int castSegments(int n, const dspmap_segment* segs, dspmap_cast_hit* hits, bool world = false) {
+        return dspmap_cast_segments(h_, n, segs, world ? DSPMAP_QUERY_WORLD : 0, hits);
+    }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

@@ -364,6 +364,66 @@ int dspmap_query_distance(dspmap_t* m, int n, const dspmap_query* q_host, int fl
 int dspmap_query_distance_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, float outside_value, float* dist_out_dev,
                                  float* grad_out_dev);
 
+/* ---- segment casts through the current and the predicted occupancy (no counterpart in the reference; a planner's edge check, a
+ * line-of-sight test or a first hit along a ray, answered where the map lives instead of by sampling dspmap_trajectory_risk every half
+ * voxel -- which misses voxels a segment only clips -- or by copying the whole grid out and walking it on the host).
+ *
+ * Cast grid (dspmap_build_cast_grid): a snapshot with the life cycle of the distance field.  L = T + 1 layers, layer 0 the current mass,
+ * layer 1 + k horizon k; each layer one bit per voxel in the reference's index order (:1081), whatever DSPMAP_P_TILING stores internally:
+ * W = ceil(nx / 64) 64-bit words per row, bit (x & 63) of word (x >> 6) of row (z, y) belongs to voxel (x, y, z); bits at x >= nx are 0.
+ *  - raw occupancy: the distance field's rule.  Layer 0: voxels_objects_number[v][0] > threshold (:394); layer 1 + k: future[v][k] >
+ *    threshold with future bit for bit what dspmap_get_future returns -- 0 everywhere while a clear is pending.
+ *  - inflation by r = inflate_voxels (0 .. DSPMAP_CAST_MAX_INFLATE), the Chebyshev ball: bit i is set iff some voxel u INSIDE the map with
+ *    max over the axes of |i_a - u_a| <= r is raw-occupied.  The outside of the map contributes nothing.
+ *  - arguments, checked before the device is touched: a NULL handle, a NaN threshold, inflate_voxels outside 0 .. 8 or flags != 0 are
+ *    DSPMAP_E_ARG; then a sharded handle (slab) is DSPMAP_E_STATE (casts cross slabs); without a usable device a valid call is
+ *    DSPMAP_E_DEVICE.
+ *  - snapshot: enqueued on the handle's stream behind everything queued there before, no synchronisation.  The grid and one scratch grid
+ *    of the same size (L * nz * ny * W words each) are allocated by the first build; a handle that never builds one allocates nothing.
+ *    READ-ONLY towards the map in every sense listed for the distance field: no accumulator is cleared, the pending clear is neither armed
+ *    nor carried out, the captured frame and its parameter ring are not touched.  The grid stays valid through readouts and
+ *    dspmap_clear_future and becomes STALE with exactly the calls that make a distance field stale (dspmap_build_distance_field above).  On
+ *    a stale or never-built grid dspmap_cast_grid_device returns NULL, dspmap_get_cast_grid and dspmap_cast_segments* return
+ *    DSPMAP_E_STATE with a text naming dspmap_build_cast_grid.  A `layer` outside [0, L) or a NULL output is DSPMAP_E_ARG.
+ *
+ * A cast (dspmap_cast_segments*) walks the segment a -> b, parameter s in [0, 1], through the grid cell by cell (Amanatides-Woo) and
+ * reports the first cell whose bit is set.  ta, tb are the times at which a and b are reached: the cell entered at parameter s is tested
+ * in the horizon of the time the segment is there.  Every named operation below is rounded to fp32 on its own.
+ *  1. validity, frame: a non-finite ax .. bz or a NaN ta or tb gives {0, -1, -1, DSPMAP_CAST_INVALID}.  With DSPMAP_QUERY_WORLD both end
+ *     points are reduced p = fl(q - cur_pos) per axis, as in the queries.
+ *  2. voxel coordinates, per axis: u_a = fl(fl(a + half) / res), u_b = fl(fl(b + half) / res) (dspmap_point_voxel_index's expression).  If
+ *     dspmap_point_voxel_index calls a outside, or trunc(u_a) >= n on some axis, the result is {0, -1, -1, DSPMAP_CAST_START_OUTSIDE}.
+ *     b may lie anywhere.  The start cell is i = trunc(u_a).
+ *  3. set-up, per axis: d = fl(u_b - u_a), step = sign(d).  d == 0: tMax = +inf.  Otherwise bnd = (float)(i + (step > 0 ? 1 : 0)),
+ *     tMax = fl(fl(bnd - u_a) / d), tDelta = fl(1.0f / fabsf(d)).  s_in = 0 for the start cell.
+ *  4. per cell: the axis m with the smallest tMax leaves first, ties to x, then y, then z (tMax_x <= tMax_y && tMax_x <= tMax_z, then
+ *     tMax_y <= tMax_z).  s_out = fminf(tMax_m, 1).  Layers tested: ta < 0 or T == 0: layer 0 only.  Otherwise dt = fl(tb - ta),
+ *     t_in = fl(ta + fl(s_in * dt)), t_out = fl(ta + fl(s_out * dt)), and the layers 1 + k(t_in), 1 + k(t_out) (the k(t) of
+ *     dspmap_query_occupancy; a t that is negative or NaN selects layer 0) and every layer between them, in ascending order.  The first
+ *     tested layer whose bit is set ends the cast with {s_in, global voxel index, that layer, DSPMAP_CAST_HIT}.  If none is set:
+ *     !(tMax_m <= 1) ends it with {1, -1, -1, DSPMAP_CAST_FREE}; otherwise s_in = tMax_m, i_m += step_m, tMax_m = fl(tMax_m + tDelta_m), and
+ *     if i_m has left [0, n_m) the cast ends with {s_in, index of the last cell inside the map, -1, DSPMAP_CAST_LEFT_MAP}.
+ *     A cast takes at most nx + ny + nz steps: each step moves one index monotonically.
+ *  - arguments: a NULL handle, n < 0, a NULL array with n > 0 or flags other than DSPMAP_QUERY_WORLD are DSPMAP_E_ARG. */
+#define DSPMAP_CAST_MAX_INFLATE 8
+typedef struct dspmap_segment {
+    float ax, ay, az, ta, bx, by, bz, tb;
+} dspmap_segment; /* 32 bytes */
+typedef struct dspmap_cast_hit {
+    float s;      /* parameter at which the reported cell is entered (HIT, LEFT_MAP: at which the map is left), 1 for FREE, 0 otherwise */
+    int voxel;    /* global voxel index of the cell (HIT: the occupied one, LEFT_MAP: the last one inside the map), else -1 */
+    int layer;    /* HIT: the layer whose bit was set, else -1 */
+    int status;   /* DSPMAP_CAST_* */
+} dspmap_cast_hit; /* 16 bytes */
+enum { DSPMAP_CAST_FREE = 0, DSPMAP_CAST_HIT = 1, DSPMAP_CAST_LEFT_MAP = 2, DSPMAP_CAST_START_OUTSIDE = 3, DSPMAP_CAST_INVALID = 4 };
+int dspmap_build_cast_grid(dspmap_t* m, float threshold, int inflate_voxels, int flags /* must be 0 */);
+const unsigned long long* dspmap_cast_grid_device(dspmap_t* m);          /* [L][nz][ny][W] words, NULL if none / stale */
+int dspmap_get_cast_grid(dspmap_t* m, int layer, unsigned long long* out_host);   /* nz * ny * W words; synchronous */
+/* out_host[i] = the cast of seg_host[i]; synchronous */
+int dspmap_cast_segments(dspmap_t* m, int n, const dspmap_segment* seg_host, int flags, dspmap_cast_hit* out_host);
+/* the same on device arrays (seg_dev: n x 32 B, out_dev: n x 16 B); enqueued on the handle's stream, no synchronisation */
+int dspmap_cast_segments_device(dspmap_t* m, int n, const dspmap_segment* seg_dev, int flags, dspmap_cast_hit* out_dev);
+
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
 int dspmap_point_voxel_index(const dspmap_t* m, float px, float py, float pz, int* index);
