@@ -86,6 +86,12 @@ SEGMENT_DTYPE = np.dtype([("ax", "f4"), ("ay", "f4"), ("az", "f4"), ("ta", "f4")
 HIT_DTYPE = np.dtype([("s", "f4"), ("voxel", "i4"), ("layer", "i4"), ("status", "i4")])
 CAST_FREE, CAST_HIT, CAST_LEFT_MAP, CAST_START_OUTSIDE, CAST_INVALID = range(5)
 CAST_MAX_INFLATE = 8   # DSPMAP_CAST_MAX_INFLATE
+# dspmap_box (dspmap_grow_boxes), the DSPMAP_BOX_* statuses and the DSPMAP_BOX_STOP_* causes (2 bits per face -x, +x, -y, +y, -z, +z in `stop`)
+BOX_DTYPE = np.dtype([("lo", "i4", (3,)), ("hi", "i4", (3,)), ("status", "i4"), ("stop", "u4")])
+BOX_OK, BOX_SEED_BLOCKED, BOX_SEED_OUTSIDE, BOX_INVALID = 0, 1, 3, 4
+BOX_STOP_OBSTACLE, BOX_STOP_EDGE, BOX_STOP_LIMIT = 1, 2, 3
+BOX_MAX_GROW = 64        # DSPMAP_BOX_MAX_GROW
+BOX_WITH_CURRENT = 2     # DSPMAP_BOX_WITH_CURRENT
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -131,6 +137,8 @@ SIGNATURES = {
     "dspmap_get_cast_grid": (_i, [_P, _i, _P]),
     "dspmap_cast_segments": (_i, [_P, _i, _P, _i, _P]),
     "dspmap_cast_segments_device": (_i, [_P, _i, _P, _i, _P]),
+    "dspmap_grow_boxes": (_i, [_P, _i, _P, _P, _i, _P]),
+    "dspmap_grow_boxes_device": (_i, [_P, _i, _P, _P, _i, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -631,6 +639,51 @@ class DSPMap:
         out = np.zeros(n, HIT_DTYPE)
         self._chk(self.L.dspmap_cast_segments(self.h, n, _ptr(q), flags, _ptr(out)))
         return out
+
+    # -- free boxes in the cast grid (extension; semantics in include/dspmap.h next to dspmap_grow_boxes)
+    def grow_boxes(self, seeds, max_grow, world=False, with_current=False):
+        """the axis-aligned box of free voxels grown around every seed {ax, ay, az, ta, bx, by, bz, tb} of seeds ([n, 8] float32, the
+        segments cast_segments takes) in the cast grid: at most max_grow = (gx, gy, gz) voxels (0 .. 64 each) beyond the seed's own cells
+        per side, tested in the layers of the times ta .. tb (ta < 0: the current layer; with_current adds it to the others).  numpy in ->
+        structured numpy (BOX_DTYPE: lo[3], hi[3] inclusive voxel indices, status = BOX_*, stop = 2 bits BOX_STOP_* per face) out,
+        synchronous; a torch tensor on the GPU -> dict of tensors 'lo', 'hi' ([n, 3] int32), 'status', 'stop' (int32) on the same device,
+        enqueued on the handle's stream and ordered with torch's current stream like query_occupancy."""
+        flags = (QUERY_WORLD if world else 0) | (BOX_WITH_CURRENT if with_current else 0)
+        g = (C.c_int * 3)(*[int(v) for v in max_grow])
+        if self._is_device_tensor(seeds):
+            import torch
+            q = self._device_samples(seeds, (8,), "grow_boxes")
+            n = q.numel() // 8
+            raw = torch.empty((n, 8), dtype=torch.int32, device=q.device)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_grow_boxes_device(self.h, n, q.data_ptr(), C.cast(g, C.c_void_p), flags, raw.data_ptr()))
+            after()
+            return {"lo": raw[:, 0:3], "hi": raw[:, 3:6], "status": raw[:, 6], "stop": raw[:, 7]}
+        q = np.ascontiguousarray(seeds, np.float32)
+        if q.shape[-1:] != (8,):
+            raise ValueError("grow_boxes: seeds of shape [n, 8]")
+        n = q.size // 8
+        out = np.zeros(n, BOX_DTYPE)
+        self._chk(self.L.dspmap_grow_boxes(self.h, n, _ptr(q), C.cast(g, C.c_void_p), flags, _ptr(out)))
+        return out
+
+    def box_bounds(self, boxes):
+        """metric corners (lo_m, hi_m), float32 [n, 3] each, of boxes (BOX_DTYPE, or the dict grow_boxes returns for device input) in the
+        map frame: lo_m = fl(fl((float)lo * res) + (-half)), hi_m = fl(fl((float)(hi + 1) * res) + (-half)) per axis, the faces of the
+        voxels lo and hi that bound the box; NaN for boxes without indices (BOX_SEED_OUTSIDE, BOX_INVALID).  Host arithmetic."""
+        if isinstance(boxes, dict):
+            lo, hi = (np.asarray(boxes[k].cpu().numpy() if hasattr(boxes[k], "cpu") else boxes[k], np.int64) for k in ("lo", "hi"))
+        else:
+            lo, hi = np.asarray(boxes["lo"], np.int64), np.asarray(boxes["hi"], np.int64)
+        f = np.float32
+        res = f(self.cfg.voxel_resolution)
+        half = np.array([f(f(res * f(k)) * f(0.5)) for k in (self.cfg.nx, self.cfg.ny, self.cfg.nz)], f)   # (res * n) * 0.5 (:528-530)
+        lo_m = ((lo.astype(f) * res).astype(f) + (-half)).astype(f)
+        hi_m = (((hi + 1).astype(f) * res).astype(f) + (-half)).astype(f)
+        none = (lo < 0).any(-1)
+        lo_m[none], hi_m[none] = np.nan, np.nan
+        return lo_m, hi_m
 
     def getVoxelPositionFromIndexPublic(self, index):
         x, y, z = C.c_float(), C.c_float(), C.c_float()

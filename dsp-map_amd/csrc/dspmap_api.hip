@@ -1099,6 +1099,52 @@ extern "C" int dspmap_cast_segments_device(dspmap_t* m, int n, const dspmap_segm
     return DSPMAP_OK;
 }
 
+// --------------------------------------------------- free boxes in the cast grid (dspmap_corridor.hip; semantics in include/dspmap.h)
+static int box_check(dspmap* m, int n, const void* in, const int* max_grow, int flags, const void* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "grow boxes: negative seed count %d", n);
+    if (n > 0 && (!in || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "grow boxes: NULL seed or output array");
+    if (!max_grow) return dspmap_fail(m, DSPMAP_E_ARG, "grow boxes: NULL max_grow");
+    for (int k = 0; k < 3; ++k)
+        if (max_grow[k] < 0 || max_grow[k] > DSPMAP_BOX_MAX_GROW)
+            return dspmap_fail(m, DSPMAP_E_ARG, "grow boxes: max_grow[%d] = %d outside [0, %d]", k, max_grow[k], DSPMAP_BOX_MAX_GROW);
+    if (flags & ~(DSPMAP_QUERY_WORLD | DSPMAP_BOX_WITH_CURRENT)) return dspmap_fail(m, DSPMAP_E_ARG, "grow boxes: unknown flags 0x%x", flags);
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "grow boxes: a slab handle holds part of the map; boxes cross slabs");
+    return cast_grid_ready(m, "dspmap_grow_boxes");
+}
+static BoxArgs box_args(const dspmap* m, const int* max_grow, int flags) {
+    BoxArgs a;
+    a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a.with_current = (flags & DSPMAP_BOX_WITH_CURRENT) ? 1 : 0;
+    a.ox = m->cur_pos[0]; a.oy = m->cur_pos[1]; a.oz = m->cur_pos[2];
+    for (int k = 0; k < 3; ++k) a.grow[k] = max_grow[k];
+    a.bits = m->cg_bits;
+    return a;
+}
+extern "C" int dspmap_grow_boxes(dspmap_t* m, int n, const dspmap_segment* seed, const int max_grow[3], int flags, dspmap_box* out) {
+    int rc = box_check(m, n, seed, max_grow, flags, out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    const size_t sb = q_align(sizeof(dspmap_segment) * (size_t)n);
+    if ((rc = query_buf(m, sb + sizeof(dspmap_box) * (size_t)n)) != DSPMAP_OK) return rc;
+    dspmap_segment* ds = (dspmap_segment*)m->q_buf;
+    dspmap_box* db = (dspmap_box*)((char*)m->q_buf + sb);
+    HIPCHK(m, hipMemcpyAsync(ds, seed, sizeof(dspmap_segment) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    launch_grow_boxes(dspmap_ctx_of(m), box_args(m, max_grow, flags), n, ds, db);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(out, db, sizeof(dspmap_box) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_grow_boxes_device(dspmap_t* m, int n, const dspmap_segment* seed, const int max_grow[3], int flags, dspmap_box* out) {
+    const int rc = box_check(m, n, seed, max_grow, flags, out);
+    if (rc != DSPMAP_OK) return rc;
+    launch_grow_boxes(dspmap_ctx_of(m), box_args(m, max_grow, flags), n, seed, out);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+
 extern "C" void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz) {  // :1556-1572
     const MapDims& d = m->d;
     const int zc = d.ny * d.nx;

@@ -188,6 +188,16 @@ struct CastArgs {
 struct dspmap_segment;
 struct dspmap_cast_hit;
 void launch_cast(const LaunchCtx& c, const CastArgs& a, int n, const struct dspmap_segment* seg, struct dspmap_cast_hit* out);
+// axis-aligned free boxes grown in the cast grid, one wave per seed (dspmap_corridor.hip; semantics in include/dspmap.h, dspmap_grow_boxes)
+struct BoxArgs {
+    float ox, oy, oz;    // as QueryArgs
+    int world;
+    int with_current;    // DSPMAP_BOX_WITH_CURRENT: layer 0 is tested in addition
+    int grow[3];         // max_grow per axis, 0 .. DSPMAP_BOX_MAX_GROW
+    const u64* bits;     // [L][nz][ny][W]
+};
+struct dspmap_box;
+void launch_grow_boxes(const LaunchCtx& c, const BoxArgs& a, int n, const struct dspmap_segment* seed, struct dspmap_box* out);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

@@ -277,6 +277,12 @@ public:
     int castSegments(int n, const dspmap_segment* segs, dspmap_cast_hit* hits, bool world = false) {
         return dspmap_cast_segments(h_, n, segs, world ? DSPMAP_QUERY_WORLD : 0, hits);
     }
+    /* extension: axis-aligned free boxes (safe corridors) grown in the cast grid around the pieces seeds[i] = {a, ta, b, tb} of a path
+     * (dspmap_grow_boxes in dspmap.h): boxes[i] = inclusive voxel bounds, a status and the cause that stopped each face.  Needs a grid
+     * built by buildCastGrid() since the last update(); read-only.  Return DSPMAP_OK or a negative error code. */
+    int growBoxes(int n, const dspmap_segment* seeds, const int max_grow[3], dspmap_box* boxes, bool world = false, bool with_current = false) {
+        return dspmap_grow_boxes(h_, n, seeds, max_grow, (world ? DSPMAP_QUERY_WORLD : 0) | (with_current ? DSPMAP_BOX_WITH_CURRENT : 0), boxes);
+    }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

@@ -424,6 +424,54 @@ int dspmap_cast_segments(dspmap_t* m, int n, const dspmap_segment* seg_host, int
 /* the same on device arrays (seg_dev: n x 32 B, out_dev: n x 16 B); enqueued on the handle's stream, no synchronisation */
 int dspmap_cast_segments_device(dspmap_t* m, int n, const dspmap_segment* seg_dev, int flags, dspmap_cast_hit* out_dev);
 
+/* ---- axis-aligned free boxes in the cast grid: safe corridors (no counterpart in the reference; the step a corridor planner takes right
+ * after the map -- around every piece of a candidate path the largest box of free voxels, which becomes the constraint set of its
+ * optimiser -- answered where the map lives instead of by a grid copy per frame and a host loop per box).
+ *
+ * A seed is a dspmap_segment: the piece a -> b of a path, reached at the times ta, tb -- what dspmap_cast_segments takes, so that an edge
+ * check and its corridor box come from one grid and one batch.  The box is grown in the grid of the last dspmap_build_cast_grid, pure
+ * integer work on its bits:
+ *  1. validity, frame: the rules of dspmap_cast_segments step 1 unchanged.  A non-finite ax .. bz or a NaN ta or tb gives
+ *     {-1 x 6, DSPMAP_BOX_INVALID, 0}; with DSPMAP_QUERY_WORLD both end points are reduced p = fl(q - cur_pos) per axis.
+ *  2. seed box: per axis i_a = trunc(u_a), i_b = trunc(u_b) with the u_a, u_b of cast step 2.  BOTH end points must lie inside the map: if
+ *     dspmap_point_voxel_index calls a or b outside, or trunc(u) >= n on some axis for either, the result is
+ *     {-1 x 6, DSPMAP_BOX_SEED_OUTSIDE, 0}.  The seed box is lo = min(i_a, i_b), hi = max(i_a, i_b) per axis.
+ *  3. layers tested: the rule of cast step 4 with t_in = ta and t_out = tb.  ta < 0 or T == 0: layer 0 only.  Otherwise the layers
+ *     1 + k(ta), 1 + k(tb) (the k(t) of dspmap_query_occupancy; a negative tb selects layer 0) and every layer between them.  With
+ *     DSPMAP_BOX_WITH_CURRENT layer 0 is tested in addition.  A cell is BLOCKED iff its bit is set in some tested layer.
+ *  4. seed test: if a cell of the seed box is blocked the result is {seed box, DSPMAP_BOX_SEED_BLOCKED, 0}.
+ *  5. growth: all six faces f = 0 .. 5 (-x, +x, -y, +y, -z, +z) start active; rounds are repeated until none is.  A round visits the
+ *     faces in the order f = 0 .. 5 and skips the inactive ones.  For an active face on axis a, c = lo_a - 1 or hi_a + 1, tested in this
+ *     order: (i) c outside [0, n_a) stops the face with cause DSPMAP_BOX_STOP_EDGE; (ii) c farther than max_grow[a] from the SEED box's
+ *     bound on that side (seed lo_a - c, or c - seed hi_a, > max_grow[a]) stops it with DSPMAP_BOX_STOP_LIMIT; (iii) a blocked cell in the
+ *     slab {index c on axis a} x the current [lo, hi] on the other two axes -- extensions made earlier in the same round included --
+ *     stops it with DSPMAP_BOX_STOP_OBSTACLE; otherwise the box is extended to c.  A stopped face is inactive for good and its cause is
+ *     recorded in `stop`.  That is exact, not a heuristic: the slab of a stopped face only grows afterwards, so its obstacle stays in it.
+ *     The result is {box, DSPMAP_BOX_OK, stop}; no cell of the box is blocked.  At most 6 * (DSPMAP_BOX_MAX_GROW + 1) face tests per seed.
+ *  - inflation is whatever the grid was built with: a box grown in a grid inflated by r keeps a Chebyshev distance greater than r voxels
+ *    from every raw-occupied voxel of the tested layers.
+ *  - arguments, checked before the device is touched: a NULL handle, n < 0, a NULL array with n > 0, a NULL max_grow, a max_grow[a] outside
+ *    0 .. DSPMAP_BOX_MAX_GROW or flags outside DSPMAP_QUERY_WORLD | DSPMAP_BOX_WITH_CURRENT are DSPMAP_E_ARG.  Then, as for
+ *    dspmap_cast_segments: a sharded handle (slab) is DSPMAP_E_STATE; a stale or never-built grid is DSPMAP_E_STATE with a text naming
+ *    dspmap_build_cast_grid (without a usable device there is no grid: dspmap_build_cast_grid is the call that reports DSPMAP_E_DEVICE);
+ *    a device call that fails is DSPMAP_E_DEVICE.
+ *  - state: READ-ONLY towards the map and the grid; what makes the grid stale is unchanged and a call does not make it so.  Enqueued on
+ *    the handle's stream behind the build and the frame. */
+#define DSPMAP_BOX_MAX_GROW 64
+#define DSPMAP_BOX_WITH_CURRENT 2          /* flag; DSPMAP_QUERY_WORLD (1) is the other one */
+typedef struct dspmap_box {
+    int lo[3], hi[3];   /* inclusive voxel indices x, y, z; -1 everywhere for SEED_OUTSIDE / INVALID */
+    int status;         /* DSPMAP_BOX_* */
+    unsigned stop;      /* 2 bits per face f = 0..5 (-x, +x, -y, +y, -z, +z) at bits 2f, 2f+1: why growth ended there */
+} dspmap_box;           /* 32 bytes */
+enum { DSPMAP_BOX_OK = 0, DSPMAP_BOX_SEED_BLOCKED = 1, DSPMAP_BOX_SEED_OUTSIDE = 3, DSPMAP_BOX_INVALID = 4 };
+enum { DSPMAP_BOX_STOP_OBSTACLE = 1, DSPMAP_BOX_STOP_EDGE = 2, DSPMAP_BOX_STOP_LIMIT = 3 };
+/* out_host[i] = the box of seed_host[i]; synchronous */
+int dspmap_grow_boxes(dspmap_t* m, int n, const dspmap_segment* seed_host, const int max_grow[3], int flags, dspmap_box* out_host);
+/* the same on device arrays (seed_dev: n x 32 B, out_dev: n x 32 B; max_grow is host memory); enqueued on the handle's stream, no
+ * synchronisation */
+int dspmap_grow_boxes_device(dspmap_t* m, int n, const dspmap_segment* seed_dev, const int max_grow[3], int flags, dspmap_box* out_dev);
+
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
 int dspmap_point_voxel_index(const dspmap_t* m, float px, float py, float pz, int* index);
