@@ -410,6 +410,10 @@ class DSPMap:
         self._chk(self.L.dspmap_get_cursors(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def set_cursors(self, p_cursor=-1, v_cursor=-1, r_cursor=-1):
+        """move the cursors of the position / velocity / rand() tables; a negative value leaves that cursor where it is"""
+        self._chk(self.L.dspmap_set_cursors(self.h, int(p_cursor), int(v_cursor), int(r_cursor)))
+
     # -- the frame (dsp_dynamic.h:181)
     def update(self, pts, pos, stamp, quat):
         """pts: (n,3) float32 host array, sensor frame.  Returns 1 (ok) / 0 (rejected)."""

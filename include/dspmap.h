@@ -166,7 +166,16 @@ enum dspmap_param {
                                        this runtime (tools/micro/fork_join.hip).  Every wait is for work submitted earlier and is bounded (200 ms): a wait
                                        that gives up calls the frame's birth stage off, the next call fails once and the handle goes on with 0.  The stream
                                        is tested not to share the main stream's hardware queue; if none is found the handle keeps 0's path
-                                       (dspmap_debug_estimator_path).  0 = a forked branch of the captured graph (rounds 2-5).  Same result either way */
+                                       (dspmap_debug_estimator_path).  0 = a forked branch of the captured graph (rounds 2-5).  Same result either way.
+                                       WHAT THE WAIT CANNOT COVER: the estimator's matching is the sequential Hungarian algorithm in one wavefront; a frame
+                                       in which every new cluster is gated against every old one (a scene change, everything moved 1.5 m or more) or whose
+                                       cluster count jumps takes N (N + 1) / 2 steps for N = max(new, old) possibly-dynamic clusters.  Measured on the
+                                       MI355X (tools/velest_scaling.py): 17 ms at N = 128, 127 ms at N = 300, i.e. half the wait from about
+                                       270 clusters and the whole wait from about 340 (extrapolated: 0.7 s at 512, 8.5 s at the capacity of 1 228).
+                                       Such a frame is computed WITHOUT its birth stage, the next call returns DSPMAP_E_DEVICE once, and the handle goes on
+                                       with 0.  A caller whose scenes can hold more than ~250 clusters of 5+ points sets 0 here (no wait, the frame simply
+                                       takes as long as the matching) or DSPMAP_P_VELOCITY_ESTIMATOR = 1.  Frames whose clusters find their predecessors
+                                       take N steps: 0.4 ms at 128, 1.2 ms at 300 */
     DSPMAP_P_FRAME_BRANCHES = 26,   /* whole frames of dense large maps run as TWO BRANCHES (round 6): the part of the map the sensor can see this frame -- grown by
                                        the reach of a newborn (:871-873) and by the frame's largest displacement (:665-667) -- goes through prediction,
                                        placement, mapUpdate, births and resampling on the main stream, the rest of the map (most of it: prediction,
