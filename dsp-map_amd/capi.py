@@ -92,6 +92,13 @@ BOX_OK, BOX_SEED_BLOCKED, BOX_SEED_OUTSIDE, BOX_INVALID = 0, 1, 3, 4
 BOX_STOP_OBSTACLE, BOX_STOP_EDGE, BOX_STOP_LIMIT = 1, 2, 3
 BOX_MAX_GROW = 64        # DSPMAP_BOX_MAX_GROW
 BOX_WITH_CURRENT = 2     # DSPMAP_BOX_WITH_CURRENT
+# dspmap_reach_point (dspmap_build_reach_fields, dspmap_reach_paths) and the DSPMAP_REACH_* constants
+REACH_POINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("field", "i4")])
+REACH_MAX_FIELDS = 64        # DSPMAP_REACH_MAX_FIELDS
+REACH_MAX_STEPS = 4096       # DSPMAP_REACH_MAX_STEPS
+REACH_UNREACHED = 65535      # DSPMAP_REACH_UNREACHED
+REACH_WITH_CURRENT = 2       # DSPMAP_REACH_WITH_CURRENT
+REACH_DEVICE_SETS = 4        # DSPMAP_REACH_DEVICE_SETS
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -139,6 +146,14 @@ SIGNATURES = {
     "dspmap_cast_segments_device": (_i, [_P, _i, _P, _i, _P]),
     "dspmap_grow_boxes": (_i, [_P, _i, _P, _P, _i, _P]),
     "dspmap_grow_boxes_device": (_i, [_P, _i, _P, _P, _i, _P]),
+    "dspmap_build_reach_fields": (_i, [_P, _i, _i, _P, _f, _f, _i, _i]),
+    "dspmap_build_reach_fields_device": (_i, [_P, _i, _i, _P, _f, _f, _i, _i]),
+    "dspmap_reach_fields_device": (_P, [_P]),
+    "dspmap_get_reach_field": (_i, [_P, _i, _P]),
+    "dspmap_reach_paths": (_i, [_P, _i, _P, _i, _i, _P, _P]),
+    "dspmap_reach_paths_device": (_i, [_P, _i, _P, _i, _i, _P, _P]),
+    "dspmap_debug_reach_storage": (_i, [_P, _P]),
+    "dspmap_debug_set_cast_grid": (_i, [_P, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -688,6 +703,105 @@ class DSPMap:
         none = (lo < 0).any(-1)
         lo_m[none], hi_m[none] = np.nan, np.nan
         return lo_m, hi_m
+
+    # -- arrival-time fields (extension; semantics in include/dspmap.h next to dspmap_build_reach_fields)
+    @staticmethod
+    def _reach_points(pts, what):
+        """host points as REACH_POINT_DTYPE [n]: a structured array, or [n, 4] numbers {x, y, z, field}"""
+        a = np.asarray(pts)
+        if a.dtype == REACH_POINT_DTYPE:
+            return np.ascontiguousarray(a).reshape(-1)
+        if a.shape[-1:] != (4,):
+            raise ValueError("%s: points of shape [n, 4] or of REACH_POINT_DTYPE" % what)
+        out = np.zeros(a.size // 4, REACH_POINT_DTYPE)
+        a = a.reshape(-1, 4)
+        out["x"], out["y"], out["z"] = a[:, 0], a[:, 1], a[:, 2]
+        out["field"] = a[:, 3].astype(np.int64)
+        return out
+
+    @staticmethod
+    def _reach_points_device(pts, what):
+        """device points: an int32 or float32 tensor [n, 4] whose last column holds the BITS of the int field (REACH_POINT_DTYPE rows)"""
+        import torch
+        if pts.dtype not in (torch.float32, torch.int32) or tuple(pts.shape[-1:]) != (4,):
+            raise ValueError("%s: a float32 / int32 tensor of shape [n, 4] holding dspmap_reach_point rows" % what)
+        return pts.contiguous()
+
+    def build_reach_fields(self, sources, n_fields=1, t_start=-1.0, step_seconds=0.0, max_steps=REACH_MAX_STEPS, world=False,
+                           with_current=False, device_sets=False):
+        """grow n_fields arrival fields through the cast grid from sources {x, y, z, field}: step n happens at t_start + n * step_seconds
+        and tests the grid layer of that time (t_start < 0: the current layer; with_current adds it to the others); a cell's value is
+        the first step n <= max_steps at which the 6-connected front holds it.  numpy sources (REACH_POINT_DTYPE, or [n, 4] numbers)
+        -> synchronous; a torch tensor on the GPU ([n, 4] int32 / float32 holding the struct's bits) -> enqueued on the handle's stream
+        and ordered with torch's current stream like query_occupancy.  Read the result with reach_field / reach_fields_ptr."""
+        flags = (QUERY_WORLD if world else 0) | (REACH_WITH_CURRENT if with_current else 0) | (REACH_DEVICE_SETS if device_sets else 0)
+        if self._is_device_tensor(sources):
+            q = self._reach_points_device(sources, "build_reach_fields")
+            n = q.numel() // 4
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_build_reach_fields_device(self.h, int(n_fields), n, q.data_ptr(), float(t_start), float(step_seconds),
+                                                              int(max_steps), flags))
+            after()
+            return
+        q = self._reach_points(sources, "build_reach_fields")
+        self._chk(self.L.dspmap_build_reach_fields(self.h, int(n_fields), len(q), _ptr(q) if len(q) else None, float(t_start),
+                                                   float(step_seconds), int(max_steps), flags))
+
+    def reach_field(self, field=None, n_fields=None):
+        """the values of one field of the last build as numpy uint16 [nz, ny, nx] (REACH_UNREACHED where the front never came), or with
+        field=None those of the first n_fields fields [n_fields, nz, ny, nx] (synchronous host copies)"""
+        shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
+        if field is None and n_fields is None:
+            raise ValueError("reach_field: a field, or n_fields for all of them")
+        fields = range(int(n_fields)) if field is None else [int(field)]
+        out = np.zeros((len(fields),) + shape, np.uint16)
+        for j, f in enumerate(fields):
+            self._chk(self.L.dspmap_get_reach_field(self.h, f, _ptr(out[j])))
+        return out if field is None else out[0]
+
+    def reach_fields_ptr(self):
+        """device address of the [n_fields][V] uint16 values, or None when there are none / they are stale"""
+        return self.L.dspmap_reach_fields_device(self.h) or None
+
+    def reach_storage(self):
+        """(fields of the last build whose wave sets lived in LDS, ... in device memory)"""
+        out = (C.c_longlong * 2)()
+        self._chk(self.L.dspmap_debug_reach_storage(self.h, C.cast(out, C.c_void_p)))
+        return int(out[0]), int(out[1])
+
+    def reach_paths(self, starts, max_len, world=False):
+        """descend a time-invariant build from starts {x, y, z, field}: (steps [n] int32: the start's value, -1 unreached, -2 outside the
+        map, -3 invalid; cells [n, max_len] int32: voxel indices from the start's cell to a cell of value 0, -1 behind the end).  numpy in
+        -> numpy out, synchronous; a torch tensor on the GPU -> tensors on the same device, enqueued like build_reach_fields."""
+        flags = QUERY_WORLD if world else 0
+        max_len = int(max_len)
+        if self._is_device_tensor(starts):
+            import torch
+            q = self._reach_points_device(starts, "reach_paths")
+            n = q.numel() // 4
+            steps = torch.empty(n, dtype=torch.int32, device=q.device)
+            cells = torch.empty((n, max(max_len, 0)), dtype=torch.int32, device=q.device)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_reach_paths_device(self.h, n, q.data_ptr(), max_len, flags, steps.data_ptr(),
+                                                       cells.data_ptr() if max_len > 0 else None))
+            after()
+            return steps, cells
+        q = self._reach_points(starts, "reach_paths")
+        steps = np.zeros(len(q), np.int32)
+        cells = np.zeros((len(q), max(max_len, 0)), np.int32)
+        self._chk(self.L.dspmap_reach_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags, _ptr(steps) if len(q) else None,
+                                            _ptr(cells) if max_len > 0 else None))
+        return steps, cells
+
+    def set_cast_grid(self, words):
+        """test hook: replace all layers of the valid cast grid with words (uint64 [L, nz, ny, W], what cast_grid() returns)"""
+        w = np.ascontiguousarray(words, np.uint64)
+        shape = (self.T + 1, self.cfg.nz, self.cfg.ny, (self.cfg.nx + 63) // 64)
+        if w.shape != shape:
+            raise ValueError("set_cast_grid: words of shape %s" % (shape,))
+        self._chk(self.L.dspmap_debug_set_cast_grid(self.h, _ptr(w)))
 
     def getVoxelPositionFromIndexPublic(self, index):
         x, y, z = C.c_float(), C.c_float(), C.c_float()

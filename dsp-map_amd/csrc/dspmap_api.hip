@@ -229,6 +229,8 @@ static void free_dev(dspmap* m) {
     m->df_field = nullptr; m->df_g8 = nullptr; m->df_h16 = nullptr; m->df_valid = false;
     for (void* q : {(void*)m->cg_bits, (void*)m->cg_tmp}) if (q) chk(hipFree(q), "hipFree");
     m->cg_bits = nullptr; m->cg_tmp = nullptr; m->cg_valid = false;
+    for (void* q : {(void*)m->rf_field, (void*)m->rf_sets}) if (q) chk(hipFree(q), "hipFree");
+    m->rf_field = nullptr; m->rf_sets = nullptr; m->rf_field_cells = 0; m->rf_sets_words = 0; m->rf_valid = false;
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
@@ -1030,6 +1032,7 @@ extern "C" int dspmap_build_cast_grid(dspmap_t* m, float thr, int inflate_voxels
     READY(m);
     BENIGN(m);
     m->cg_valid = false;
+    m->rf_valid = false;   // (arrival fields are grown in the grid this build replaces)
     if (!m->cg_bits) {
         HIPCHK(m, hipMalloc(&m->cg_bits, sizeof(u64) * words));
         HIPCHK(m, hipMalloc(&m->cg_tmp, sizeof(u64) * words));
@@ -1142,6 +1145,197 @@ extern "C" int dspmap_grow_boxes_device(dspmap_t* m, int n, const dspmap_segment
     if (rc != DSPMAP_OK) return rc;
     launch_grow_boxes(dspmap_ctx_of(m), box_args(m, max_grow, flags), n, seed, out);
     HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+
+// --------------------------------------------------- arrival-time fields (dspmap_reach.hip; semantics in include/dspmap.h)
+// the layer step n tests: the host twin of reach_layer (dspmap_reach.hip) -- the same fp32 operations, the k(t) of q_horizon
+static int reach_layer_host(const MapDims& d, bool timed, float t_start, float step_seconds, int n) {
+    if (!timed) return 0;
+    volatile float prod = (float)n * step_seconds;   // (volatile: two roundings, whatever the host compiler would like to fuse)
+    volatile float t = t_start + prod;
+    const float tt = t;
+    int k = d.T - 1;
+    for (int j = d.T - 1; j >= 0; --j)
+        if (d.pred_t[j] >= tt) k = j;
+    return k + 1;
+}
+static int reach_build_check(dspmap* m, int n_fields, int n_src, const void* src, float t_start, float step_seconds, int max_steps, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n_fields < 1 || n_fields > DSPMAP_REACH_MAX_FIELDS)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: n_fields %d outside [1, %d]", n_fields, DSPMAP_REACH_MAX_FIELDS);
+    if (n_src < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: negative source count %d", n_src);
+    if (n_src > 0 && !src) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: NULL source array");
+    if (t_start != t_start) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: t_start is NaN");
+    if (!(step_seconds >= 0.f && step_seconds < INFINITY))
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: step_seconds %g is NaN, negative or infinite", (double)step_seconds);
+    if (max_steps < 1 || max_steps > DSPMAP_REACH_MAX_STEPS)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: max_steps %d outside [1, %d]", max_steps, DSPMAP_REACH_MAX_STEPS);
+    if (flags & ~(DSPMAP_QUERY_WORLD | DSPMAP_REACH_WITH_CURRENT | DSPMAP_REACH_DEVICE_SETS))
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: unknown flags 0x%x", flags);
+    const unsigned long long cells = (unsigned long long)n_fields * (unsigned long long)m->d.v_glob;
+    if (cells > 0x80000000ull) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: %d fields of %d cells exceed 2^31 cells", n_fields, m->d.v_glob);
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "reach fields: a slab handle holds part of the map; a wavefront crosses slabs");
+    return cast_grid_ready(m, "dspmap_build_reach_fields");
+}
+// the launch behind both entry points; src_dev may be NULL with n_src == 0
+static int reach_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_point* src_dev, float t_start, float step_seconds, int max_steps,
+                       int flags) {
+    const MapDims& d = m->d;
+    m->rf_valid = false;
+    const size_t cells = (size_t)n_fields * d.v_glob, lw = cast_layer_words(d);
+    const bool lds = 2 * sizeof(u64) * lw <= (size_t)REACH_LDS_BYTES && !(flags & DSPMAP_REACH_DEVICE_SETS);
+    const size_t set_words = lds ? 0 : 2 * lw * (size_t)n_fields;
+    if (cells > m->rf_field_cells || set_words > m->rf_sets_words) {   // grown only after the stream has drained (an earlier call may still read them)
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        if (!m->rf_field) reach_init_device();
+        if (cells > m->rf_field_cells) {
+            if (m->rf_field) { HIPCHK(m, hipFree(m->rf_field)); m->rf_field = nullptr; m->rf_field_cells = 0; }
+            HIPCHK(m, hipMalloc(&m->rf_field, sizeof(unsigned short) * cells));
+            m->rf_field_cells = cells;
+        }
+        if (set_words > m->rf_sets_words) {
+            if (m->rf_sets) { HIPCHK(m, hipFree(m->rf_sets)); m->rf_sets = nullptr; m->rf_sets_words = 0; }
+            HIPCHK(m, hipMalloc(&m->rf_sets, sizeof(u64) * set_words));
+            m->rf_sets_words = set_words;
+        }
+    }
+    ReachArgs a;
+    a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a.ox = m->cur_pos[0]; a.oy = m->cur_pos[1]; a.oz = m->cur_pos[2];
+    a.with_current = (flags & DSPMAP_REACH_WITH_CURRENT) ? 1 : 0;
+    const bool timed = !(t_start < 0.f) && d.T > 0;
+    a.timed = timed ? 1 : 0;
+    a.t_start = t_start; a.step_seconds = step_seconds; a.max_steps = max_steps;
+    const int l_last = reach_layer_host(d, timed, t_start, step_seconds, max_steps);
+    int n_fix = max_steps;
+    while (n_fix > 0 && reach_layer_host(d, timed, t_start, step_seconds, n_fix - 1) == l_last) --n_fix;
+    a.n_fix = n_fix;
+    a.n_fields = n_fields; a.n_src = n_src;
+    a.bits = m->cg_bits; a.field = m->rf_field; a.sets = lds ? nullptr : m->rf_sets;
+    HIPCHK(m, hipMemsetAsync(m->rf_field, 0xff, sizeof(unsigned short) * cells, m->stream));   // every value DSPMAP_REACH_UNREACHED
+    launch_reach(dspmap_ctx_of(m), a, src_dev);
+    HIPCHK(m, hipGetLastError());
+    m->rf_n = n_fields;
+    m->rf_invariant = reach_layer_host(d, timed, t_start, step_seconds, 0) == l_last;
+    m->rf_storage[0] = lds ? n_fields : 0; m->rf_storage[1] = lds ? 0 : n_fields;
+    m->rf_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_build_reach_fields(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds,
+                                         int max_steps, int flags) {
+    int rc = reach_build_check(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags);
+    if (rc != DSPMAP_OK) return rc;
+    dspmap_reach_point* ds = nullptr;
+    if (n_src > 0) {
+        if ((rc = query_buf(m, sizeof(dspmap_reach_point) * (size_t)n_src)) != DSPMAP_OK) return rc;
+        ds = (dspmap_reach_point*)m->q_buf;
+        HIPCHK(m, hipMemcpyAsync(ds, src, sizeof(dspmap_reach_point) * (size_t)n_src, hipMemcpyHostToDevice, m->stream));
+    }
+    if ((rc = reach_build(m, n_fields, n_src, ds, t_start, step_seconds, max_steps, flags)) != DSPMAP_OK) return rc;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_build_reach_fields_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start,
+                                                float step_seconds, int max_steps, int flags) {
+    const int rc = reach_build_check(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags);
+    if (rc != DSPMAP_OK) return rc;
+    return reach_build(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags);
+}
+extern "C" const unsigned short* dspmap_reach_fields_device(dspmap_t* m) { return (m && m->rf_valid && m->cg_valid) ? m->rf_field : nullptr; }
+static int reach_ready(dspmap* m, const char* what) {
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: a slab handle holds part of the map; a wavefront crosses slabs", what);
+    if (!m->rf_valid || !m->cg_valid)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no arrival fields, or the map or its cast grid has changed since they were built (dspmap_build_reach_fields)", what);
+    if (m->device >= 0) (void)hipSetDevice(m->device);
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_reach_field(dspmap_t* m, int field, unsigned short* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "reach field: NULL output array");
+    if (field < 0 || field >= DSPMAP_REACH_MAX_FIELDS) return dspmap_fail(m, DSPMAP_E_ARG, "reach field: field %d outside [0, %d)", field, DSPMAP_REACH_MAX_FIELDS);
+    const int rc = reach_ready(m, "dspmap_get_reach_field");
+    if (rc != DSPMAP_OK) return rc;
+    if (field >= m->rf_n) return dspmap_fail(m, DSPMAP_E_ARG, "reach field: field %d outside [0, %d), the fields of the last build", field, m->rf_n);
+    HIPCHK(m, hipMemcpyAsync(out, m->rf_field + (size_t)field * m->d.v_glob, sizeof(unsigned short) * (size_t)m->d.v_glob, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+static int reach_paths_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: negative start count %d", n);
+    if (max_len < 0 || max_len > DSPMAP_REACH_MAX_STEPS + 1)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: max_len %d outside [0, %d]", max_len, DSPMAP_REACH_MAX_STEPS + 1);
+    if (n > 0 && (!start || !steps_out)) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: NULL start or steps_out array");
+    if (n > 0 && max_len > 0 && !cells_out) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: NULL cells_out array with max_len %d", max_len);
+    if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: unknown flags 0x%x", flags);
+    if ((unsigned long long)n * (unsigned long long)max_len > 0x80000000ull)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: %d paths of %d cells exceed 2^31 cells", n, max_len);
+    const int rc = reach_ready(m, "dspmap_reach_paths");
+    if (rc != DSPMAP_OK) return rc;
+    if (!m->rf_invariant)
+        return dspmap_fail(m, DSPMAP_E_STATE, "reach paths: the fields of the last build are not time-invariant (the tested layer changed "
+                                              "during the steps): first arrivals alone do not determine a path");
+    return DSPMAP_OK;
+}
+static ReachPathArgs reach_path_args(const dspmap* m, int max_len, int flags) {
+    ReachPathArgs a;
+    a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a.ox = m->cur_pos[0]; a.oy = m->cur_pos[1]; a.oz = m->cur_pos[2];
+    a.n_fields = m->rf_n; a.max_len = max_len;
+    a.field = m->rf_field;
+    return a;
+}
+extern "C" int dspmap_reach_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
+    int rc = reach_paths_check(m, n, start, max_len, flags, steps_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    const size_t sb = q_align(sizeof(dspmap_reach_point) * (size_t)n), tb = q_align(sizeof(int) * (size_t)n), cb = sizeof(int) * (size_t)n * max_len;
+    if ((rc = query_buf(m, sb + tb + cb)) != DSPMAP_OK) return rc;
+    dspmap_reach_point* ds = (dspmap_reach_point*)m->q_buf;
+    int* dt = (int*)((char*)m->q_buf + sb);
+    int* dc = max_len ? (int*)((char*)m->q_buf + sb + tb) : nullptr;
+    HIPCHK(m, hipMemcpyAsync(ds, start, sizeof(dspmap_reach_point) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    launch_reach_paths(dspmap_ctx_of(m), reach_path_args(m, max_len, flags), n, ds, dt, dc);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(steps_out, dt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (max_len) HIPCHK(m, hipMemcpyAsync(cells_out, dc, cb, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_reach_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
+    const int rc = reach_paths_check(m, n, start, max_len, flags, steps_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    launch_reach_paths(dspmap_ctx_of(m), reach_path_args(m, max_len, flags), n, start, steps_out, cells_out);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_debug_reach_storage(dspmap_t* m, long long out[2]) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "reach storage: NULL output array");
+    out[0] = m->rf_storage[0]; out[1] = m->rf_storage[1];
+    return DSPMAP_OK;
+}
+// test hook: all L layers of the VALID cast grid are replaced by the caller's words
+extern "C" int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long* words) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!words) return dspmap_fail(m, DSPMAP_E_ARG, "set cast grid: NULL word array");
+    const MapDims& d = m->d;
+    const size_t nw = (size_t)((d.nx + 63) >> 6), total = (size_t)(d.T + 1) * cast_layer_words(d);
+    if (d.nx & 63) {
+        const unsigned long long pad = ~0ull << (d.nx & 63);
+        for (size_t i = nw - 1; i < total; i += nw)
+            if (words[i] & pad) return dspmap_fail(m, DSPMAP_E_ARG, "set cast grid: word %zu has a bit set at x >= nx", i);
+    }
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "set cast grid: a slab handle holds part of the map");
+    const int rc = cast_grid_ready(m, "dspmap_debug_set_cast_grid");
+    if (rc != DSPMAP_OK) return rc;
+    m->rf_valid = false;
+    HIPCHK(m, hipMemcpyAsync(m->cg_bits, words, sizeof(u64) * total, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));   // (the caller's array is free again)
     return DSPMAP_OK;
 }
 

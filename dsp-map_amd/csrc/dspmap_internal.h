@@ -182,6 +182,15 @@ struct dspmap {
     // by the first build, freed with the device state.  cg_valid: the life cycle of df_valid (dspmap_snapshots_stale)
     u64* cg_bits = nullptr; u64* cg_tmp = nullptr;
     bool cg_valid = false;
+    // arrival-time fields (dspmap_build_reach_fields): the values [rf_n][V] uint16 and, where the wave sets do not fit in LDS, their device
+    // scratch [rf_n][2][nz * ny * W]; allocated (and grown) by a build, freed with the device state.  rf_valid: a snapshot of the cast grid --
+    // cleared with cg_valid, by every dspmap_build_cast_grid and by dspmap_debug_set_cast_grid
+    unsigned short* rf_field = nullptr; size_t rf_field_cells = 0;
+    u64* rf_sets = nullptr; size_t rf_sets_words = 0;
+    bool rf_valid = false;
+    int rf_n = 0;                    // fields of the last build
+    bool rf_invariant = false;       // ... whose tested layer never changed: paths exist
+    long long rf_storage[2] = {0, 0};   // ... whose sets lived in LDS / in device memory (dspmap_debug_reach_storage)
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;
@@ -208,8 +217,9 @@ struct dspmap {
     float event_overhead_ms = 0.f;   // calibrated by dspmap_set_profiling(1): what an event bracket adds to the one kernel inside it
 };
 
-// everything that computes a frame or replaces state calls this: the distance field and the cast grid are snapshots of the map before it
-inline void dspmap_snapshots_stale(dspmap* m) { m->df_valid = false; m->cg_valid = false; }
+// everything that computes a frame or replaces state calls this: the distance field, the cast grid and the arrival fields grown in it are
+// snapshots of the map before it
+inline void dspmap_snapshots_stale(dspmap* m) { m->df_valid = false; m->cg_valid = false; m->rf_valid = false; }
 int dspmap_fail(dspmap* m, int code, const char* fmt, ...);
 void dspmap_prof_mark(dspmap* m, int i);
 void dspmap_prof_collect(dspmap* m);

@@ -198,6 +198,32 @@ struct BoxArgs {
 };
 struct dspmap_box;
 void launch_grow_boxes(const LaunchCtx& c, const BoxArgs& a, int n, const struct dspmap_segment* seed, struct dspmap_box* out);
+// arrival-time fields: a space-time wavefront through the cast grid, one workgroup per field (dspmap_reach.hip; semantics in include/dspmap.h,
+// dspmap_build_reach_fields)
+struct ReachArgs {
+    float ox, oy, oz;    // as QueryArgs
+    int world;
+    int with_current;    // DSPMAP_REACH_WITH_CURRENT: layer 0 is tested in addition
+    int timed;           // t_start >= 0 and T > 0: step n tests layer 1 + k(t_n); otherwise every step tests layer 0
+    float t_start, step_seconds;
+    int max_steps;
+    int n_fix;           // the first step from which the tested layer no longer changes (host: the schedule is walked once)
+    int n_fields, n_src;
+    const u64* bits;     // [L][nz][ny][W]
+    unsigned short* field;   // [n_fields][V], preset to DSPMAP_REACH_UNREACHED
+    u64* sets;           // [n_fields][2][nz * ny * W] device scratch of the two wave sets, or nullptr: they live in LDS
+};
+struct ReachPathArgs {
+    float ox, oy, oz;
+    int world;
+    int n_fields, max_len;
+    const unsigned short* field;
+};
+struct dspmap_reach_point;
+#define REACH_LDS_BYTES (160 * 1024 - 256)   // what a workgroup's two sets may take of the CU's 160 KiB (the rest: the step flags)
+void reach_init_device();   // per device, once (dspmap_init_device)
+void launch_reach(const LaunchCtx& c, const ReachArgs& a, const struct dspmap_reach_point* src);
+void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out, int* cells_out);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

@@ -1,0 +1,213 @@
+// dspmap_reach.hip -- arrival-time fields: a space-time wavefront through the cast grid (dspmap_build_reach_fields*, dspmap_reach_paths*;
+// semantics next to them in include/dspmap.h).  The reference has no counterpart: a planner that asks "which cells can I reach through
+// the predicted occupancy, and how early?" copies the grid out (getOccupancyMapWithFutureStatus :405-426) and runs a BFS on the host.
+//
+// The work: step n of a field is R_n = (R_{n-1} u N6(R_{n-1})) \ B_n on one bit per voxel -- per 64-bit word of a row a shift left, a shift
+// right, two carry bits out of the row's neighbouring words, four ORs with the words at y +- 1 and z +- 1, one and-not with the blocked
+// word of the step's layer.  The steps of a field are strictly sequential (up to 4096 of them), a step touches nz * ny * W words (960 on a
+// 40 x 40 x 24 map, 5 280 on 66 x 66 x 40, 23 760 on 132 x 132 x 60), and the fields of a batch are independent.
+//
+// Chosen: ONE WORKGROUP OF 1024 THREADS PER FIELD runs every step of its field in ONE launch; the batch of fields supplies the CUs.  A
+// thread owns the words t = tid, tid + 1024, ... of the set for the whole run.  The two sets (R_{n-1}, R_n) ping-pong in LDS whenever
+// 2 * nz * ny * W * 8 bytes fit REACH_LDS_BYTES (dynamic shared memory, raised to the CU's 160 KiB by hipFuncSetAttribute as
+// dspmap_sweep.hip does for k_rollout): 84 KB on 66 x 66 x 40.  Larger maps keep them in per-field device scratch instead, which one
+// workgroup re-reads every step and which therefore stays in L2; the code is the same template, and because a workgroup runs on one CU
+// the workgroup-scope ordering of __syncthreads() is all the two storages need.  Per step and word: seven reads of the old set, and ONLY
+// IF the grown word is non-zero one or two loads of the blocked words through L2 (the layer changes with n, so they are not cached in
+// LDS); the front is a thin shell, so most words of most steps stop at the seven reads.  The cells that are new in R_n (grown & ~old: the
+// front, not the volume) are walked bit by bit and the value n is stored where the field still reads 65535 -- a cell that was removed
+// and comes back keeps its first arrival.  The owner of a word is the only thread that ever reads or writes its 64 values, so that test
+// needs no atomic.  ONE barrier per step: the step's verdict {changed, non-empty} is ORed into one of three rotating LDS flags before
+// the barrier and read behind it; the flag of step n + 1 is cleared by thread 0 before the barrier of step n, when its last readers
+// (step n - 2) are provably past.  The loop leaves early when the set is empty (it stays empty) or when a step changed nothing and the
+// schedule has reached its last layer (n >= n_fix, walked once on the host): every later step would repeat it.  That is invisible in
+// the result.  Sources are ORed into R with atomics before step 0, every thread scanning a stride of the batch's sources for its field.
+// Every loop is bounded by max_steps, the word count or the source count; nothing waits on another workgroup.
+//
+// Rejected:
+//  - one launch per step over all fields (the textbook level-synchronous BFS): up to 4096 launches of a few microseconds of work each, and
+//    the early exit would need a read-back per step.  A serpentine maze of 700 steps would cost 700 launch gaps.
+//  - several workgroups per field with a grid-wide barrier or flags in memory between them: a spin on memory another workgroup writes
+//    deadlocks as soon as the workgroups are not all resident, and a hung kernel takes the device from everyone.  Very large maps pay
+//    with one CU per field instead (out of scope: more than one workgroup per field).
+//  - a third set "ever reached" in LDS to avoid the uint16 re-read: 126 KB instead of 84 KB on 66 x 66 x 40 and it would push
+//    maps between 107 and 160 KB out of LDS; the re-read is per FRONT bit, each of which is written at most a few times in a run.
+//  - a lane per cell and uint16 distances relaxed in place (Bellman-Ford style): 64 times the LDS of a bit set, so only toy maps would
+//    fit, and the blocked test becomes a bit extract per cell and step instead of one and-not per 64 cells.
+//  - keeping the blocked words of the tested layer in LDS: the layer changes with n in the scheduled case, and in the static case the
+//    and-not is already skipped for every word the front does not touch.
+#include "dspmap_device.h"
+#include "dspmap_internal.h"
+
+#define REACH_TPB 1024
+#define REACH_PATH_TPB 256
+
+__device__ __forceinline__ bool reach_finite(float v) { return fabsf(v) < INFINITY; }   // (false for NaN)
+
+// the cell of a source / start point (include/dspmap.h: the rules of the queries and of cast step 2): 0 = a cell, -2 = outside the map,
+// -3 = a non-finite coordinate
+__device__ __forceinline__ int reach_cell(const MapDims& d, float ox, float oy, float oz, int world, float px, float py, float pz, int& x, int& y,
+                                          int& z) {
+    if (!(reach_finite(px) && reach_finite(py) && reach_finite(pz))) return -3;
+    if (world) { px = __fsub_rn(px, ox); py = __fsub_rn(py, oy); pz = __fsub_rn(pz, oz); }
+    if (fabsf(px) >= d.half_x || fabsf(py) >= d.half_y || fabsf(pz) >= d.half_z) return -2;   // dspmap_point_voxel_index's test
+    x = (int)__fdiv_rn(__fadd_rn(px, d.half_x), d.res);                                       // (all >= 0: p > -half)
+    y = (int)__fdiv_rn(__fadd_rn(py, d.half_y), d.res);
+    z = (int)__fdiv_rn(__fadd_rn(pz, d.half_z), d.res);
+    return (x < d.nx && y < d.ny && z < d.nz) ? 0 : -2;
+}
+
+// the layer step n tests besides (with_current) layer 0
+__device__ __forceinline__ int reach_layer(const MapDims& d, const ReachArgs& a, int n) {
+    if (!a.timed) return 0;
+    return q_horizon(d, __fadd_rn(a.t_start, __fmul_rn((float)n, a.step_seconds))) + 1;
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, const float4* __restrict__ src) {
+    extern __shared__ u64 s_reach[];
+    __shared__ int s_flag[3];   // bit 0: the step changed the set, bit 1: the set is not empty
+    const unsigned tid = threadIdx.x, f = blockIdx.x;
+    const unsigned W = (unsigned)(d.nx + 63) >> 6, plane = (unsigned)d.ny * W, nwords = (unsigned)d.nz * plane;   // (< 2^31: the cast grid exists)
+    u64* set = LDS ? s_reach : a.sets + (size_t)f * 2 * nwords;
+    unsigned short* fld = a.field + (size_t)f * d.v_glob;
+    const u64* __restrict__ bits = a.bits;
+    const u64 row_mask = (d.nx & 63) ? ~0ull >> (64 - (d.nx & 63)) : ~0ull;   // bits at x >= nx are never reached
+    unsigned co = 0, no = nwords;                                             // R_{n-1} at set[co ..], R_n at set[no ..]
+
+    for (unsigned t = tid; t < nwords; t += REACH_TPB) set[co + t] = 0;
+    if (tid < 3) s_flag[tid] = 0;
+    __syncthreads();
+    for (unsigned i = tid; i < (unsigned)a.n_src; i += REACH_TPB) {
+        const float4 p = src[i];
+        if ((unsigned)__float_as_int(p.w) != f) continue;   // (a field outside [0, n_fields) matches no workgroup)
+        int x, y, z;
+        if (reach_cell(d, a.ox, a.oy, a.oz, a.world, p.x, p.y, p.z, x, y, z) != 0) continue;
+        atomicOr((unsigned long long*)&set[co + ((unsigned)z * d.ny + y) * W + ((unsigned)x >> 6)], 1ull << (x & 63));
+    }
+    __syncthreads();
+    {   // step 0: R_0 = S \ B_0, in place (a thread touches its own words only)
+        const int l = reach_layer(d, a, 0);
+        for (unsigned t = tid; t < nwords; t += REACH_TPB) {
+            u64 v = set[co + t];
+            if (!v) continue;
+            u64 b = bits[(size_t)l * nwords + t];
+            if (a.with_current && l > 0) b |= bits[t];
+            v &= ~b;
+            set[co + t] = v;
+            const unsigned row = t / W, w = t - row * W;
+            unsigned short* cell = fld + (size_t)row * d.nx + w * 64;
+            while (v) {
+                cell[__builtin_ctzll(v)] = 0;
+                v &= v - 1;
+            }
+        }
+    }
+    __syncthreads();
+    for (int n = 1; n <= a.max_steps; ++n) {
+        const int l = reach_layer(d, a, n);
+        int verdict = 0;
+        for (unsigned t = tid; t < nwords; t += REACH_TPB) {
+            const unsigned z = t / plane, r = t - z * plane, y = r / W, w = r - y * W;
+            const u64* cur = set + co + t;
+            const u64 c = cur[0];
+            u64 g = c | (c << 1) | (c >> 1);
+            if (w > 0) g |= cur[-1] >> 63;             // the carries of the row's neighbouring words, never across rows
+            if (w + 1 < W) g |= cur[1] << 63;
+            if (y > 0) g |= cur[-(int)W];
+            if (y + 1 < (unsigned)d.ny) g |= cur[W];
+            if (z > 0) g |= cur[-(int)plane];
+            if (z + 1 < (unsigned)d.nz) g |= cur[plane];
+            if (w + 1 == W) g &= row_mask;
+            if (g) {
+                u64 b = bits[(size_t)l * nwords + t];
+                if (a.with_current && l > 0) b |= bits[t];
+                g &= ~b;
+            }
+            set[no + t] = g;
+            verdict |= (g != c ? 1 : 0) | (g ? 2 : 0);
+            u64 fresh = g & ~c;                        // the front: cells of R_n that R_{n-1} did not hold
+            if (fresh) {
+                unsigned short* cell = fld + (size_t)(t / W) * d.nx + w * 64;
+                do {
+                    const int bit = __builtin_ctzll(fresh);
+                    fresh &= fresh - 1;
+                    if (cell[bit] == DSPMAP_REACH_UNREACHED) cell[bit] = (unsigned short)n;   // (a cell that comes back keeps its first arrival)
+                } while (fresh);
+            }
+        }
+        if (verdict) atomicOr(&s_flag[n % 3], verdict);
+        if (tid == 0) s_flag[(n + 1) % 3] = 0;         // (its last readers, those of step n - 2, are past the barrier of step n - 1)
+        __syncthreads();
+        const int v = s_flag[n % 3];
+        const unsigned tmp = co; co = no; no = tmp;
+        if (!(v & 2)) break;                           // an empty set stays empty
+        if (!(v & 1) && n >= a.n_fix) break;           // nothing changed and the layer never changes again: every later step repeats this one
+    }
+}
+
+// one lane per start: the steepest descent through a time-invariant field, first neighbour of value v - 1 in the order -x, +x, -y, +y, -z, +z
+__global__ void __launch_bounds__(REACH_PATH_TPB) k_reach_paths(MapDims d, ReachPathArgs a, int n, const float4* __restrict__ start,
+                                                                int* __restrict__ steps_out, int* __restrict__ cells_out) {
+    const unsigned i = blockIdx.x * REACH_PATH_TPB + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    const float4 p = start[i];
+    const int f = __float_as_int(p.w);
+    int x = 0, y = 0, z = 0;
+    int st = reach_cell(d, a.ox, a.oy, a.oz, a.world, p.x, p.y, p.z, x, y, z);
+    if ((unsigned)f >= (unsigned)a.n_fields) st = -3;   // (a non-finite coordinate is -3 as well; either wins over "outside")
+    const unsigned short* __restrict__ fld = a.field + (size_t)(st == 0 ? f : 0) * d.v_glob;
+    int v = 0;
+    if (st == 0) {
+        v = fld[((size_t)z * d.ny + y) * d.nx + x];
+        st = v == DSPMAP_REACH_UNREACHED ? -1 : v;
+    }
+    steps_out[i] = st;
+    int* out = cells_out + (size_t)i * a.max_len;
+    int j = 0;
+    if (st >= 0) {
+        const int sy = d.nx, sz = d.nx * d.ny;
+        int g = (z * d.ny + y) * d.nx + x;
+        for (; j < a.max_len;) {                       // (bounded by max_len; v falls by one per cell)
+            out[j++] = g;
+            if (v == 0) break;
+            // the six neighbour loads of a step are issued together: independent addresses, one wait
+            const bool ok[6] = {x > 0, x + 1 < d.nx, y > 0, y + 1 < d.ny, z > 0, z + 1 < d.nz};
+            const int off[6] = {-1, 1, -sy, sy, -sz, sz};
+            int nv[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) nv[k] = fld[g + (ok[k] ? off[k] : 0)];
+            int pick = -1;
+#pragma unroll
+            for (int k = 5; k >= 0; --k)
+                if (ok[k] && nv[k] == v - 1) pick = k;
+            if (pick < 0) break;                       // no such neighbour (never in a time-invariant field): stop, the rest is -1
+            g += off[pick];
+            x += pick == 1 ? 1 : (pick == 0 ? -1 : 0);
+            y += pick == 3 ? 1 : (pick == 2 ? -1 : 0);
+            z += pick == 5 ? 1 : (pick == 4 ? -1 : 0);
+            --v;
+        }
+    }
+    for (; j < a.max_len; ++j) out[j] = -1;
+}
+
+void reach_init_device() {   // per device, once (dspmap_init_device)
+    (void)hipFuncSetAttribute((const void*)k_reach<true>, hipFuncAttributeMaxDynamicSharedMemorySize, REACH_LDS_BYTES);
+}
+
+void launch_reach(const LaunchCtx& c, const ReachArgs& a, const dspmap_reach_point* src) {
+    if (a.n_fields <= 0) return;
+    const MapDims& d = c.d;
+    const size_t set_bytes = 2 * sizeof(u64) * (size_t)d.nz * d.ny * (size_t)((d.nx + 63) >> 6);
+    if (a.sets)
+        hipLaunchKernelGGL(k_reach<false>, dim3(a.n_fields), dim3(REACH_TPB), 0, c.stream, d, a, (const float4*)src);
+    else
+        hipLaunchKernelGGL(k_reach<true>, dim3(a.n_fields), dim3(REACH_TPB), set_bytes, c.stream, d, a, (const float4*)src);
+}
+
+void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const dspmap_reach_point* start, int* steps_out, int* cells_out) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_reach_paths, dim3((unsigned)(((long long)n + REACH_PATH_TPB - 1) / REACH_PATH_TPB)), dim3(REACH_PATH_TPB), 0, c.stream,
+                       c.d, a, n, (const float4*)start, steps_out, cells_out);
+}

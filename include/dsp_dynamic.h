@@ -283,6 +283,21 @@ public:
     int growBoxes(int n, const dspmap_segment* seeds, const int max_grow[3], dspmap_box* boxes, bool world = false, bool with_current = false) {
         return dspmap_grow_boxes(h_, n, seeds, max_grow, (world ? DSPMAP_QUERY_WORLD : 0) | (with_current ? DSPMAP_BOX_WITH_CURRENT : 0), boxes);
     }
+    /* extension: arrival-time fields grown through the cast grid (dspmap_build_reach_fields in dspmap.h): n_fields fields, each from the
+     * sources src[i] = {x, y, z, field} that name it; step n happens at t_start + n * step_seconds and tests the layer of that time
+     * (t_start < 0: the current layer).  Needs a grid built by buildCastGrid() since the last update(); read-only.  getReachField copies
+     * one field's V uint16 values (DSPMAP_REACH_UNREACHED where the front never came); reachPaths descends a time-invariant build from
+     * starts[i] (steps[i] = the start's value or a negative cause, cells[i * max_len + j] = voxel indices, -1 behind the path's end).
+     * Return DSPMAP_OK or a negative error code. */
+    int buildReachFields(int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds, int max_steps,
+                         bool world = false, bool with_current = false) {
+        return dspmap_build_reach_fields(h_, n_fields, n_src, src, t_start, step_seconds, max_steps,
+                                         (world ? DSPMAP_QUERY_WORLD : 0) | (with_current ? DSPMAP_REACH_WITH_CURRENT : 0));
+    }
+    int getReachField(int field, unsigned short* values) { return dspmap_get_reach_field(h_, field, values); }
+    int reachPaths(int n, const dspmap_reach_point* starts, int max_len, int* steps, int* cells, bool world = false) {
+        return dspmap_reach_paths(h_, n, starts, max_len, world ? DSPMAP_QUERY_WORLD : 0, steps, cells);
+    }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

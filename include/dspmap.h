@@ -481,6 +481,80 @@ int dspmap_grow_boxes(dspmap_t* m, int n, const dspmap_segment* seed_host, const
  * synchronisation */
 int dspmap_grow_boxes_device(dspmap_t* m, int n, const dspmap_segment* seed_dev, const int max_grow[3], int flags, dspmap_box* out_dev);
 
+/* ---- arrival-time fields: a space-time wavefront through the cast grid (no counterpart in the reference; the global question behind the
+ * local ones above -- from where the robot is, through the occupancy the map predicts, which cells can it reach, and how early?  Grown from
+ * a goal the same field is the cost-to-go a search uses as its heuristic and a local planner descends -- answered where the map lives
+ * instead of by a grid copy per frame and a BFS on the host).
+ *
+ * A build grows n_fields fields, each from its own source points, in the grid of the last dspmap_build_cast_grid (inflated as that grid
+ * is).  Exact integer work on its bits:
+ *  - cells, neighbours: the cells are the voxels of the map, the neighbours N6 of a cell its six face neighbours INSIDE the map.  The
+ *    outside of the map does not exist; bits at x >= nx are never reached.
+ *  - schedule: step n = 0, 1, ... happens at the time t_n = fl(t_start + fl((float)n * step_seconds)).  If t_start < 0 or T == 0 every
+ *    step tests layer 0; otherwise step n tests layer 1 + k(t_n) with the k(t) of dspmap_query_occupancy (monotone in n, clamped at the
+ *    last horizon).  With DSPMAP_REACH_WITH_CURRENT layer 0 is tested in addition.  B_n = the cells whose bit is set in a layer tested at
+ *    step n.
+ *  - sources: a dspmap_reach_point {x, y, z, field}; frame conventions and DSPMAP_QUERY_WORLD (p = fl(q - cur_pos) per axis) are those of
+ *    the queries.  Its cell is dspmap_point_voxel_index's voxel, per axis trunc(u), u = fl(fl(p + half) / res), with the trunc(u) >= n
+ *    rule of cast step 2 (such a point is outside).  A source with a non-finite coordinate, outside the map or with `field` outside
+ *    [0, n_fields) is ignored.  S_f = the source cells of field f.
+ *  - wavefront, per field: R_0 = S_f \ B_0, R_n = (R_{n-1} u N6(R_{n-1})) \ B_n.  Waiting in place is allowed; a reached cell that
+ *    becomes blocked is REMOVED, so the set is not monotone when the layers change, and a front that is blocked everywhere at one step
+ *    reaches nothing afterwards.
+ *  - value of a cell, uint16: the smallest n <= max_steps with the cell in R_n, or DSPMAP_REACH_UNREACHED.  Fields are
+ *    [n_fields][nz][ny][nx] in the reference's voxel index order, whatever DSPMAP_P_TILING stores.
+ *  - time-invariant fields: a build is time-invariant iff layer(0) == layer(max_steps) (decided on the host; the layer is monotone in n, so
+ *    no step tests another one).  In such a field every cell of value v > 0 has a neighbour of value v - 1.
+ *  - paths exist ONLY for time-invariant builds: when the layers change, a cell's first arrival may have come through a cell that was
+ *    itself reached earlier, removed and never reached at the step needed, so first arrivals alone do not determine a path.
+ *    A start is a dspmap_reach_point.  steps_out[i] = the value of its cell; -1 if that is DSPMAP_REACH_UNREACHED, -2 if the point is
+ *    outside the map, -3 if a coordinate is non-finite or `field` is outside [0, n_fields) (-3 wins over -2).
+ *    cells_out[i * max_len + j] are global voxel indices: j = 0 the start's cell, cell j + 1 the FIRST neighbour of cell j in the order
+ *    -x, +x, -y, +y, -z, +z whose value is one less.  The path ends at a cell of value 0 or after max_len cells; the remaining entries,
+ *    and all of them when steps_out[i] < 0, are -1.  Should no neighbour qualify the path stops there and the rest is -1: no loop is
+ *    unbounded.
+ *  - arguments, checked before the device is touched, DSPMAP_E_ARG with a text: a NULL handle, n_fields outside
+ *    1 .. DSPMAP_REACH_MAX_FIELDS, n_src < 0, a NULL array with n_src > 0, a NaN t_start, a step_seconds that is NaN, negative or infinite,
+ *    max_steps outside 1 .. DSPMAP_REACH_MAX_STEPS, flags outside DSPMAP_QUERY_WORLD | DSPMAP_REACH_WITH_CURRENT |
+ *    DSPMAP_REACH_DEVICE_SETS, n_fields * V > 2^31.  Paths: n < 0, max_len outside 0 .. DSPMAP_REACH_MAX_STEPS + 1, a NULL start or
+ *    steps_out with n > 0, a NULL cells_out with n > 0 and max_len > 0, flags other than DSPMAP_QUERY_WORLD, n * max_len > 2^31.
+ *  - state, after the arguments and in dspmap_grow_boxes' order: a sharded handle (slab) is DSPMAP_E_STATE; a build on a stale or
+ *    never-built grid is DSPMAP_E_STATE with a text naming dspmap_build_cast_grid (without a usable device there is no grid); the accessors
+ *    and the paths on a stale or never-built snapshot are DSPMAP_E_STATE with a text naming dspmap_build_reach_fields; paths on a build that
+ *    is not time-invariant are DSPMAP_E_STATE with a text saying so.  A device call that fails is DSPMAP_E_DEVICE.
+ *  - life cycle: the snapshot goes stale with everything that makes the cast grid stale, with every dspmap_build_cast_grid and with
+ *    dspmap_debug_set_cast_grid.  READ-ONLY towards the map and the grid in every sense listed for dspmap_grow_boxes.  The buffers are
+ *    allocated by the first build (grown by a larger one) and freed with the device state; a handle that never builds allocates nothing.
+ *    Enqueued on the handle's stream behind the grid's build and the frame. */
+#define DSPMAP_REACH_MAX_FIELDS 64
+#define DSPMAP_REACH_MAX_STEPS 4096
+#define DSPMAP_REACH_UNREACHED 65535
+#define DSPMAP_REACH_WITH_CURRENT 2        /* flag; DSPMAP_QUERY_WORLD (1) is the other public one */
+#define DSPMAP_REACH_DEVICE_SETS 4         /* diagnostic flag: keep the wave sets in device memory even where they fit in LDS; same result */
+typedef struct dspmap_reach_point {
+    float x, y, z;
+    int field;
+} dspmap_reach_point;   /* 16 bytes */
+/* grow n_fields fields from src_host[0 .. n_src); synchronous */
+int dspmap_build_reach_fields(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src_host, float t_start, float step_seconds,
+                              int max_steps, int flags);
+/* the same on a device array (src_dev: n_src x 16 B); enqueued on the handle's stream, no synchronisation */
+int dspmap_build_reach_fields_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src_dev, float t_start,
+                                     float step_seconds, int max_steps, int flags);
+/* device address of the [n_fields][V] uint16 values of the last build; NULL if there is none or it is stale */
+const unsigned short* dspmap_reach_fields_device(dspmap_t* m);
+/* out_host[0 .. V) = the values of one field of the last build; synchronous */
+int dspmap_get_reach_field(dspmap_t* m, int field, unsigned short* out_host);
+/* paths of n starts down a time-invariant build: steps_out[n], cells_out[n * max_len] (may be NULL when max_len == 0); synchronous */
+int dspmap_reach_paths(dspmap_t* m, int n, const dspmap_reach_point* start_host, int max_len, int flags, int* steps_out_host, int* cells_out_host);
+/* the same on device arrays; enqueued on the handle's stream, no synchronisation */
+int dspmap_reach_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start_dev, int max_len, int flags, int* steps_out_dev, int* cells_out_dev);
+/* diagnostic: out[0] / out[1] = the fields of the last build whose wave sets lived in LDS / in device memory */
+int dspmap_debug_reach_storage(dspmap_t* m, long long out[2]);
+/* test hook: replace all L layers ([L][nz][ny][W] words) of the VALID cast grid.  A NULL pointer or a set bit at x >= nx is DSPMAP_E_ARG, no
+ * valid grid DSPMAP_E_STATE.  The grid stays valid; arrival fields built before the call are stale.  Synchronous. */
+int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long* words_host);
+
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
 int dspmap_point_voxel_index(const dspmap_t* m, float px, float py, float pz, int* index);
