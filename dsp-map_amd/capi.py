@@ -99,6 +99,8 @@ REACH_MAX_STEPS = 4096       # DSPMAP_REACH_MAX_STEPS
 REACH_UNREACHED = 65535      # DSPMAP_REACH_UNREACHED
 REACH_WITH_CURRENT = 2       # DSPMAP_REACH_WITH_CURRENT
 REACH_DEVICE_SETS = 4        # DSPMAP_REACH_DEVICE_SETS
+FORECAST_MAX_TIMES = 64      # DSPMAP_FORECAST_MAX_TIMES
+FORECAST_LERP = 2            # DSPMAP_FORECAST_LERP
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -154,6 +156,12 @@ SIGNATURES = {
     "dspmap_reach_paths_device": (_i, [_P, _i, _P, _i, _i, _P, _P]),
     "dspmap_debug_reach_storage": (_i, [_P, _P]),
     "dspmap_debug_set_cast_grid": (_i, [_P, _P]),
+    "dspmap_build_forecast": (_i, [_P, _i, _P, _i]),
+    "dspmap_forecast_device": (_P, [_P]),
+    "dspmap_forecast_times": (_i, [_P, _P, _i]),
+    "dspmap_get_forecast": (_i, [_P, _i, _P]),
+    "dspmap_query_forecast": (_i, [_P, _i, _P, _i, _f, _P]),
+    "dspmap_query_forecast_device": (_i, [_P, _i, _P, _i, _f, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -794,6 +802,59 @@ class DSPMap:
         self._chk(self.L.dspmap_reach_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags, _ptr(steps) if len(q) else None,
                                             _ptr(cells) if max_len > 0 else None))
         return steps, cells
+
+    # -- occupancy forecast at caller-chosen times (extension; semantics in include/dspmap.h next to dspmap_build_forecast)
+    def build_forecast(self, times):
+        """enqueue the occupancy layers at `times` (seconds after the last frame: strictly ascending, finite, >= 0, at most
+        FORECAST_MAX_TIMES of them) on the handle's stream: every live particle rolled out to each time, newborns included, no weight
+        cull.  Read-only towards the map; the layers are a snapshot and go stale with the next frame."""
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        self._chk(self.L.dspmap_build_forecast(self.h, len(t), _ptr(t) if len(t) else None, 0))
+
+    def forecast_times(self):
+        """the times of the valid snapshot, float32 [n]"""
+        t = np.zeros(FORECAST_MAX_TIMES, np.float32)
+        n = self.L.dspmap_forecast_times(self.h, _ptr(t), len(t))
+        if n < 0:
+            self._chk(n)
+        return t[:n].copy()
+
+    def forecast(self, layer=None):
+        """one layer as numpy [V] (the reference's voxel order), or all layers [n, V] (synchronous host copies)"""
+        V = self.L.dspmap_voxel_num(self.h)
+        layers = range(len(self.forecast_times())) if layer is None else [int(layer)]
+        out = np.zeros((len(layers), V), np.float32)
+        for j, l in enumerate(layers):
+            self._chk(self.L.dspmap_get_forecast(self.h, l, _ptr(out[j])))
+        return out if layer is None else out[0]
+
+    def forecast_ptr(self):
+        """device address of the [n][V] float32 layers, or None when there are none / they are stale"""
+        return self.L.dspmap_forecast_device(self.h) or None
+
+    def query_forecast(self, q, world=False, lerp=False, outside=1.0):
+        """value of every sample {x, y, z, t} of q ([n, 4] float32) at its own voxel: the first layer whose time is >= t (the last one
+        beyond it), or with lerp the fp32 interpolation between that layer and the one before; `outside` for what lies outside the map.
+        numpy in -> numpy out (synchronous); a torch tensor on the GPU -> a tensor on the same device, enqueued on the handle's stream
+        and ordered with torch's current stream like query_occupancy."""
+        flags = (QUERY_WORLD if world else 0) | (FORECAST_LERP if lerp else 0)
+        if self._is_device_tensor(q):
+            import torch
+            q = self._device_samples(q, (4,), "query_forecast")
+            n = q.numel() // 4
+            out = torch.empty(n, dtype=torch.float32, device=q.device)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_query_forecast_device(self.h, n, q.data_ptr(), flags, float(outside), out.data_ptr()))
+            after()
+            return out
+        q = np.ascontiguousarray(q, np.float32)
+        if q.shape[-1:] != (4,):
+            raise ValueError("query_forecast: samples of shape [n, 4]")
+        n = q.size // 4
+        out = np.zeros(n, np.float32)
+        self._chk(self.L.dspmap_query_forecast(self.h, n, _ptr(q), flags, float(outside), _ptr(out)))
+        return out
 
     def set_cast_grid(self, words):
         """test hook: replace all layers of the valid cast grid with words (uint64 [L, nz, ny, W], what cast_grid() returns)"""

@@ -231,6 +231,8 @@ static void free_dev(dspmap* m) {
     m->cg_bits = nullptr; m->cg_tmp = nullptr; m->cg_valid = false;
     for (void* q : {(void*)m->rf_field, (void*)m->rf_sets}) if (q) chk(hipFree(q), "hipFree");
     m->rf_field = nullptr; m->rf_sets = nullptr; m->rf_field_cells = 0; m->rf_sets_words = 0; m->rf_valid = false;
+    for (void* q : {(void*)m->fc_field, (void*)m->fc_acc}) if (q) chk(hipFree(q), "hipFree");
+    m->fc_field = nullptr; m->fc_acc = nullptr; m->fc_cap = 0; m->fc_valid = false;
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
@@ -1336,6 +1338,118 @@ extern "C" int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long*
     m->rf_valid = false;
     HIPCHK(m, hipMemcpyAsync(m->cg_bits, words, sizeof(u64) * total, hipMemcpyHostToDevice, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));   // (the caller's array is free again)
+    return DSPMAP_OK;
+}
+
+// --------------------------------------------------- occupancy forecast at caller-chosen times (dspmap_forecast.hip; semantics in include/dspmap.h)
+static_assert(FORECAST_MAX_TIMES == DSPMAP_FORECAST_MAX_TIMES, "ForecastArgs holds DSPMAP_FORECAST_MAX_TIMES times");
+extern "C" int dspmap_build_forecast(dspmap_t* m, int n_times, const float* times, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n_times < 1 || n_times > DSPMAP_FORECAST_MAX_TIMES)
+        return dspmap_fail(m, DSPMAP_E_ARG, "forecast: n_times %d outside [1, %d]", n_times, DSPMAP_FORECAST_MAX_TIMES);
+    if (!times) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: NULL times array");
+    for (int j = 0; j < n_times; ++j) {
+        if (!(times[j] >= 0.f && times[j] < INFINITY))
+            return dspmap_fail(m, DSPMAP_E_ARG, "forecast: times[%d] = %g is NaN, infinite or negative", j, (double)times[j]);
+        if (j > 0 && !(times[j] > times[j - 1]))
+            return dspmap_fail(m, DSPMAP_E_ARG, "forecast: times[%d] = %g is not greater than times[%d] = %g", j, (double)times[j], j - 1, (double)times[j - 1]);
+    }
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: unknown flags 0x%x", flags);
+    if ((unsigned long long)n_times * (unsigned long long)m->d.v_glob >= 0x80000000ull)
+        return dspmap_fail(m, DSPMAP_E_ARG, "forecast: %d layers of %d cells reach 2^31 cells", n_times, m->d.v_glob);
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "forecast: a slab handle holds part of the map; particles cross slabs");
+    READY(m);
+    BENIGN(m);
+    const MapDims& d = m->d;
+    m->fc_valid = false;
+    if (n_times > m->fc_cap) {   // grown only after the stream has drained (an earlier call may still read them)
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        if (m->fc_field) { HIPCHK(m, hipFree(m->fc_field)); m->fc_field = nullptr; }
+        if (m->fc_acc) { HIPCHK(m, hipFree(m->fc_acc)); m->fc_acc = nullptr; }
+        m->fc_cap = 0;
+        HIPCHK(m, hipMalloc(&m->fc_field, sizeof(float) * (size_t)n_times * d.v_glob));
+        HIPCHK(m, hipMalloc(&m->fc_acc, sizeof(u64) * (size_t)(n_times + 1) * d.v_loc));
+        m->fc_cap = n_times;
+    }
+    ForecastArgs a;
+    a.n = n_times;
+    for (int j = 0; j < FORECAST_MAX_TIMES; ++j) a.t[j] = j < n_times ? times[j] : 0.f;
+    a.dyn = m->fc_acc; a.stat = m->fc_acc + (size_t)n_times * d.v_loc; a.out = m->fc_field;
+    HIPCHK(m, hipMemsetAsync(m->fc_acc, 0, sizeof(u64) * (size_t)(n_times + 1) * d.v_loc, m->stream));   // dyn and stat: one allocation
+    launch_forecast(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    m->fc_n = n_times;
+    for (int j = 0; j < n_times; ++j) m->fc_t[j] = times[j];
+    m->fc_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" const float* dspmap_forecast_device(dspmap_t* m) { return (m && m->fc_valid) ? m->fc_field : nullptr; }
+static int forecast_ready(dspmap* m, const char* what) {
+    if (!m->fc_valid)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no forecast, or the map has changed since it was built (dspmap_build_forecast)", what);
+    if (m->device >= 0) (void)hipSetDevice(m->device);
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_forecast_times(dspmap_t* m, float* times_out, int cap) {
+    if (!m) return DSPMAP_E_ARG;
+    if (cap > 0 && !times_out) return dspmap_fail(m, DSPMAP_E_ARG, "forecast times: NULL output array");
+    const int rc = forecast_ready(m, "dspmap_forecast_times");
+    if (rc != DSPMAP_OK) return rc;
+    for (int j = 0; j < m->fc_n && j < cap; ++j) times_out[j] = m->fc_t[j];
+    return m->fc_n;
+}
+extern "C" int dspmap_get_forecast(dspmap_t* m, int layer, float* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: NULL output array");
+    if (layer < 0 || layer >= DSPMAP_FORECAST_MAX_TIMES) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: layer %d outside [0, %d)", layer, DSPMAP_FORECAST_MAX_TIMES);
+    const int rc = forecast_ready(m, "dspmap_get_forecast");
+    if (rc != DSPMAP_OK) return rc;
+    if (layer >= m->fc_n) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: layer %d outside [0, %d), the layers of the last build", layer, m->fc_n);
+    const size_t V = (size_t)m->d.v_glob;
+    HIPCHK(m, hipMemcpyAsync(out, m->fc_field + V * layer, sizeof(float) * V, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+static int forecast_query_check(dspmap* m, int n, const void* in, const void* out, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "forecast query: negative sample count %d", n);
+    if (n > 0 && (!in || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "forecast query: NULL sample or output array");
+    if (flags & ~(DSPMAP_QUERY_WORLD | DSPMAP_FORECAST_LERP)) return dspmap_fail(m, DSPMAP_E_ARG, "forecast query: unknown flags 0x%x", flags);
+    if (outside != outside) return dspmap_fail(m, DSPMAP_E_ARG, "forecast query: outside_value is NaN");
+    return forecast_ready(m, "dspmap_query_forecast");
+}
+static ForecastQueryArgs forecast_query_args(const dspmap* m, int flags, float outside) {
+    ForecastQueryArgs a;
+    a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a.lerp = (flags & DSPMAP_FORECAST_LERP) ? 1 : 0;
+    a.ox = m->cur_pos[0]; a.oy = m->cur_pos[1]; a.oz = m->cur_pos[2];
+    a.outside = outside;
+    a.n = m->fc_n;
+    for (int j = 0; j < FORECAST_MAX_TIMES; ++j) a.t[j] = j < m->fc_n ? m->fc_t[j] : 0.f;
+    a.field = m->fc_field;
+    return a;
+}
+extern "C" int dspmap_query_forecast(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, float* out) {
+    int rc = forecast_query_check(m, n, q, out, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    const size_t qb = q_align(sizeof(dspmap_query) * (size_t)n);
+    if ((rc = query_buf(m, qb + sizeof(float) * (size_t)n)) != DSPMAP_OK) return rc;
+    float4* dq = (float4*)m->q_buf;
+    float* dout = (float*)((char*)m->q_buf + qb);
+    HIPCHK(m, hipMemcpyAsync(dq, q, sizeof(dspmap_query) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    launch_forecast_query(dspmap_ctx_of(m), forecast_query_args(m, flags, outside), n, dq, dout);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(out, dout, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_forecast_device(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, float* out) {
+    const int rc = forecast_query_check(m, n, q, out, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    launch_forecast_query(dspmap_ctx_of(m), forecast_query_args(m, flags, outside), n, (const float4*)q, out);
+    HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;
 }
 

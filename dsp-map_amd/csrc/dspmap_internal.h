@@ -191,6 +191,13 @@ struct dspmap {
     int rf_n = 0;                    // fields of the last build
     bool rf_invariant = false;       // ... whose tested layer never changed: paths exist
     long long rf_storage[2] = {0, 0};   // ... whose sets lived in LDS / in device memory (dspmap_debug_reach_storage)
+    // occupancy forecast (dspmap_build_forecast): the layers [fc_n][V] floats and the sweep's accumulators [fc_n + 1][v_loc] (the moving
+    // particles' per layer, then the static sums); allocated (and grown) by a build, freed with the device state.  fc_valid: the life cycle
+    // of df_valid (dspmap_snapshots_stale)
+    float* fc_field = nullptr; u64* fc_acc = nullptr; int fc_cap = 0;   // fc_cap: layers the two buffers hold
+    bool fc_valid = false;
+    int fc_n = 0;                    // layers of the last build ...
+    float fc_t[DSPMAP_FORECAST_MAX_TIMES] = {};   // ... and their times
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;
@@ -217,9 +224,9 @@ struct dspmap {
     float event_overhead_ms = 0.f;   // calibrated by dspmap_set_profiling(1): what an event bracket adds to the one kernel inside it
 };
 
-// everything that computes a frame or replaces state calls this: the distance field, the cast grid and the arrival fields grown in it are
-// snapshots of the map before it
-inline void dspmap_snapshots_stale(dspmap* m) { m->df_valid = false; m->cg_valid = false; m->rf_valid = false; }
+// everything that computes a frame or replaces state calls this: the distance field, the cast grid, the arrival fields grown in it and the
+// forecast are snapshots of the map before it
+inline void dspmap_snapshots_stale(dspmap* m) { m->df_valid = false; m->cg_valid = false; m->rf_valid = false; m->fc_valid = false; }
 int dspmap_fail(dspmap* m, int code, const char* fmt, ...);
 void dspmap_prof_mark(dspmap* m, int i);
 void dspmap_prof_collect(dspmap* m);

@@ -224,6 +224,26 @@ struct dspmap_reach_point;
 void reach_init_device();   // per device, once (dspmap_init_device)
 void launch_reach(const LaunchCtx& c, const ReachArgs& a, const struct dspmap_reach_point* src);
 void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out, int* cells_out);
+// occupancy forecast at caller-chosen times from the live particle set (dspmap_forecast.hip; semantics in include/dspmap.h, dspmap_build_forecast)
+#define FORECAST_MAX_TIMES 64   // == DSPMAP_FORECAST_MAX_TIMES
+struct ForecastArgs {
+    int n;               // layers
+    float t[FORECAST_MAX_TIMES];   // their times, strictly ascending
+    u64* dyn;            // [n][v_loc] quanta of the moving particles, storage order (zeroed on the stream before the sweep)
+    u64* stat;           // [v_loc] quanta of the static particles: the same in every layer (zeroed likewise: the sweep leaves empty tiles early)
+    float* out;          // [n][V] the layers in the reference's voxel order
+};
+void launch_forecast(const LaunchCtx& c, const ForecastArgs& a);
+struct ForecastQueryArgs {
+    float ox, oy, oz;    // as QueryArgs
+    int world;
+    int lerp;            // DSPMAP_FORECAST_LERP
+    float outside;       // what a point outside the map or a NaN sample reads
+    int n;
+    float t[FORECAST_MAX_TIMES];
+    const float* field;  // [n][V]
+};
+void launch_forecast_query(const LaunchCtx& c, const ForecastQueryArgs& a, int n, const float4* q, float* out);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

@@ -298,6 +298,16 @@ public:
     int reachPaths(int n, const dspmap_reach_point* starts, int max_len, int* steps, int* cells, bool world = false) {
         return dspmap_reach_paths(h_, n, starts, max_len, world ? DSPMAP_QUERY_WORLD : 0, steps, cells);
     }
+    /* extension: occupancy forecast at times of the caller's choosing (dspmap_build_forecast in dspmap.h): layer j = the mass of every live
+     * particle, newborns included, rolled out to times[j] seconds after the last update() -- strictly ascending, at most
+     * DSPMAP_FORECAST_MAX_TIMES.  Read-only towards the map; a snapshot that goes stale with the next update().  getForecast copies one
+     * layer's V floats; queryForecast reads each sample's own voxel in the first layer at or after its t, or with lerp interpolates between
+     * that layer and the one before.  Return DSPMAP_OK or a negative error code. */
+    int buildForecast(int n_times, const float* times) { return dspmap_build_forecast(h_, n_times, times, 0); }
+    int getForecast(int layer, float* values) { return dspmap_get_forecast(h_, layer, values); }
+    int queryForecast(int n, const dspmap_query* q, float* out, bool world = false, bool lerp = false, float outside_value = 1.f) {
+        return dspmap_query_forecast(h_, n, q, (world ? DSPMAP_QUERY_WORLD : 0) | (lerp ? DSPMAP_FORECAST_LERP : 0), outside_value, out);
+    }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

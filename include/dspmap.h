@@ -555,6 +555,62 @@ int dspmap_debug_reach_storage(dspmap_t* m, long long out[2]);
  * valid grid DSPMAP_E_STATE.  The grid stays valid; arrival fields built before the call are stale.  Synchronous. */
 int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long* words_host);
 
+/* ---- occupancy forecast at caller-chosen times from the live particle set (no counterpart in the reference, whose horizons are the
+ * PREDICTION_TIMES it was compiled with; everything above snaps a time t to the next configured horizon k(t), and the future status is a
+ * by-product of the resampling loop: taken from the weights before resampling, without the particles born in that frame (:944), kept in
+ * consume-and-clear accumulators (:397-400, :420-424).  A planner with knots of its own -- an MPC at 20 Hz, a spline's collocation
+ * times -- rolls the particles out to exactly its times instead, where they live).
+ *
+ * A snapshot with the life cycle of the distance field (dspmap_build_forecast), plus a point query on it.
+ *  - layers: layer j is the occupancy mass at times[j] seconds after the last frame.  Each layer is a dense [nz][ny][nx] grid in the
+ *    reference's voxel index order (:1081), whatever DSPMAP_P_TILING stores.  `times` is strictly ascending, every entry finite and >= 0.
+ *  - who contributes: every live particle of the handle -- every set bit of the live mask (what dspmap_export_state exports), which after
+ *    a frame means flags 0.6 and 1.  No weight cull and no newborn exclusion: the snapshot is of the state as it is.  A particle's
+ *    quantum is q = __float2ull_rn(w * 2^24) (round to nearest even; NaN or a negative weight gives 0).
+ *  - where a particle lands; every operation is rounded to fp32 on its own.  A static particle (vx == 0 && vy == 0) adds q to the voxel
+ *    it is stored in, in every layer.  A moving particle, for layer j:
+ *      1. fx = fl(px + fl(vx * t_j)), fy likewise;
+ *      2. it contributes nothing if fabsf(fx) >= half_x or fabsf(fy) >= half_y, or if fx or fy is NaN (an import can leave a
+ *         non-finite position or velocity; a particle with a NaN velocity counts as moving);
+ *      3. otherwise xi = (int)fl(fl(fx + half_x) / res), yi likewise (the IEEE quotient, dspmap_point_voxel_index's expression);
+ *      4. it contributes nothing if xi >= nx or yi >= ny (the one float just below half whose quotient rounds up to n, on the maps
+ *         that have one);
+ *      5. otherwise it adds q to voxel (xi, yi, z of the voxel it is stored in): the library's motion model has no vertical velocity
+ *         (vz == 0, :661-663).  A pending vz array left by dspmap_import_state with vz != 0 is ignored.
+ *  - value: (float)((double)Q * 2^-24), Q the 64-bit integer sum of the cell's quanta.  Integer sums do not depend on order: a layer is
+ *    defined bit for bit -- on every run, on both storage orders, with DSPMAP_P_STATIC_TILE_SKIP 0 or 1.  The layer at t = 0 approximates
+ *    dspmap_get_results column 0 but is not the same bits: that column is an fp32 sum in slot order.
+ *  - arguments, checked before the device is touched, DSPMAP_E_ARG with a text: a NULL handle, n_times outside
+ *    1 .. DSPMAP_FORECAST_MAX_TIMES, a NULL `times`, a time that is NaN, infinite or negative or not greater than its predecessor,
+ *    flags != 0, n_times * V >= 2^31.  Then a sharded handle (slab) is DSPMAP_E_STATE (particles cross slabs); without a usable device a
+ *    valid call is DSPMAP_E_DEVICE.
+ *  - snapshot: the build is enqueued on the handle's stream behind everything queued there before and does not synchronise.  READ-ONLY
+ *    towards the map in every sense listed for the distance field: the future accumulators, their static part, their dirty flags and the
+ *    pending clear are untouched, the captured frame and its parameter ring are untouched, no per-tile flag is written.  The buffers
+ *    (the layers and n_times + 1 accumulator grids of 8 bytes per stored voxel) are allocated by the first build, grown by a larger one
+ *    and freed with the device state; a handle that never builds allocates nothing.  The snapshot stays valid through readouts and
+ *    dspmap_clear_future and becomes STALE with exactly the calls that make a distance field stale (dspmap_build_distance_field above).
+ *    On a stale or never-built snapshot dspmap_forecast_device returns NULL, dspmap_forecast_times returns DSPMAP_E_STATE,
+ *    dspmap_get_forecast and dspmap_query_forecast* return DSPMAP_E_STATE with a text naming dspmap_build_forecast.  A `layer` outside
+ *    [0, n_times) or a NULL output is DSPMAP_E_ARG.
+ * dspmap_query_forecast*: samples, frame convention, DSPMAP_QUERY_WORLD and the argument checks are those of dspmap_query_occupancy.
+ *  - footprint: the own voxel only (dspmap_point_voxel_index's voxel); there is no radius.  A sample with a NaN coordinate or t, or a
+ *    point outside the map, reads `outside_value`.
+ *  - layer: j = the smallest index with times[j] >= t.  If there is none the value is layer n_times - 1; if j == 0 (this covers t < 0)
+ *    the value is layer 0; otherwise, without DSPMAP_FORECAST_LERP, the value is layer j; with the flag, a = layer j - 1 and b = layer j
+ *    at the voxel, u = fl(fl(t - times[j-1]) / fl(times[j] - times[j-1])) and the value is fl(a + fl(u * fl(b - a))).
+ *  - flags outside DSPMAP_QUERY_WORLD | DSPMAP_FORECAST_LERP are DSPMAP_E_ARG. */
+#define DSPMAP_FORECAST_MAX_TIMES 64
+#define DSPMAP_FORECAST_LERP 2            /* query flag; DSPMAP_QUERY_WORLD (1) is the other one */
+int dspmap_build_forecast(dspmap_t* m, int n_times, const float* times_host, int flags /* must be 0 */);
+const float* dspmap_forecast_device(dspmap_t* m);                 /* [n_times][V] floats, NULL if none / stale */
+int dspmap_forecast_times(dspmap_t* m, float* times_out_host, int cap);   /* returns n_times of the valid snapshot, copies min(cap, n) */
+int dspmap_get_forecast(dspmap_t* m, int layer, float* out_host); /* V floats; synchronous */
+/* out_host[i] = value of q_host[i]; synchronous */
+int dspmap_query_forecast(dspmap_t* m, int n, const dspmap_query* q_host, int flags, float outside_value, float* out_host);
+/* the same on device arrays; enqueued on the handle's stream, no synchronisation */
+int dspmap_query_forecast_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, float outside_value, float* out_dev);
+
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
 int dspmap_point_voxel_index(const dspmap_t* m, float px, float py, float pz, int* index);
