@@ -162,6 +162,14 @@ SIGNATURES = {
     "dspmap_get_forecast": (_i, [_P, _i, _P]),
     "dspmap_query_forecast": (_i, [_P, _i, _P, _i, _f, _P]),
     "dspmap_query_forecast_device": (_i, [_P, _i, _P, _i, _f, _P]),
+    "dspmap_known_integrate": (_i, [_P, _f, _i]),
+    "dspmap_known_reset": (_i, [_P]),
+    "dspmap_get_known": (_i, [_P, _P]),
+    "dspmap_query_known": (_i, [_P, _i, _P, _i, _P]),
+    "dspmap_query_known_device": (_i, [_P, _i, _P, _i, _P]),
+    "dspmap_mask_cast_grid": (_i, [_P, _i, _i]),
+    "dspmap_known_stats": (_i, [_P, _i, _P]),
+    "dspmap_get_view": (_i, [_P, _P, _P, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -855,6 +863,68 @@ class DSPMap:
         out = np.zeros(n, np.float32)
         self._chk(self.L.dspmap_query_forecast(self.h, n, _ptr(q), flags, float(outside), _ptr(out)))
         return out
+
+    # -- known-space layer (extension; semantics in include/dspmap.h next to dspmap_known_integrate)
+    def integrate_known(self, max_range=float("inf")):
+        """enqueue the integration of the last frame's view into the known-space layer on the handle's stream: every world lattice cell
+        of the window whose centre lies in a pyramid of the frame, not behind that pyramid's farthest return (plus the occlusion margin)
+        and within max_range of the sensor is stamped with the update counter.  Read-only towards the map."""
+        self._chk(self.L.dspmap_known_integrate(self.h, float(max_range), 0))
+
+    def reset_known(self):
+        """forget everything the layer has seen"""
+        self._chk(self.L.dspmap_known_reset(self.h))
+
+    def known_age(self):
+        """frames since each voxel was last seen, -1 = never: numpy int32 [nz, ny, nx] (synchronous host copy)"""
+        out = np.zeros((self.cfg.nz, self.cfg.ny, self.cfg.nx), np.int32)
+        self._chk(self.L.dspmap_get_known(self.h, _ptr(out)))
+        return out
+
+    def query_known(self, q, world=False):
+        """age of the cell that holds every sample {x, y, z, t} of q ([n, 4] float32; t is ignored), -1 outside the map, for a NaN
+        coordinate or for a cell never seen.  numpy in -> numpy int32 out (synchronous); a torch tensor on the GPU -> an int32 tensor on
+        the same device, enqueued on the handle's stream and ordered with torch's current stream like query_occupancy."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(q):
+            import torch
+            q = self._device_samples(q, (4,), "query_known")
+            n = q.numel() // 4
+            out = torch.empty(n, dtype=torch.int32, device=q.device)
+            self._chk(self.L.dspmap_init_device(self.h))   # (the handle's stream exists from here on)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_query_known_device(self.h, n, q.data_ptr(), flags, out.data_ptr()))
+            after()
+            return out
+        q = np.ascontiguousarray(q, np.float32)
+        if q.shape[-1:] != (4,):
+            raise ValueError("query_known: samples of shape [n, 4]")
+        n = q.size // 4
+        out = np.zeros(n, np.int32)
+        self._chk(self.L.dspmap_query_known(self.h, n, _ptr(q), flags, _ptr(out)))
+        return out
+
+    def mask_cast_grid(self, max_age):
+        """OR "unknown" into every layer of the valid cast grid: the bit of each voxel never seen or seen more than max_age frames ago.
+        Casts, boxes and arrival fields built afterwards treat that space as blocked; arrival fields built before are stale."""
+        self._chk(self.L.dspmap_mask_cast_grid(self.h, int(max_age), 0))
+
+    def known_stats(self, max_age):
+        """(cells with 0 <= age <= max_age, cells stamped by the current frame)"""
+        out = (C.c_longlong * 2)()
+        self._chk(self.L.dspmap_known_stats(self.h, int(max_age), C.cast(out, C.c_void_p)))
+        return int(out[0]), int(out[1])
+
+    def view(self):
+        """(planes_h [np_h + 1, 3], planes_v [np_v + 1, 3], maxlen [np_h, np_v]) of the last frame: the rotated boundary-plane normals and
+        the farthest return per pyramid (-1 = none), float32 host copies (synchronous)"""
+        nh = 2 * self.cfg.half_fov_h // self.cfg.angle_resolution
+        nv = 2 * self.cfg.half_fov_v // self.cfg.angle_resolution
+        assert nh * nv == self.NP
+        ph, pv, ml = np.zeros((nh + 1, 3), np.float32), np.zeros((nv + 1, 3), np.float32), np.zeros((nh, nv), np.float32)
+        self._chk(self.L.dspmap_get_view(self.h, _ptr(ph), _ptr(pv), _ptr(ml)))
+        return ph, pv, ml
 
     def set_cast_grid(self, words):
         """test hook: replace all layers of the valid cast grid with words (uint64 [L, nz, ny, W], what cast_grid() returns)"""

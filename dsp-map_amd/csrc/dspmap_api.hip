@@ -233,6 +233,8 @@ static void free_dev(dspmap* m) {
     m->rf_field = nullptr; m->rf_sets = nullptr; m->rf_field_cells = 0; m->rf_sets_words = 0; m->rf_valid = false;
     for (void* q : {(void*)m->fc_field, (void*)m->fc_acc}) if (q) chk(hipFree(q), "hipFree");
     m->fc_field = nullptr; m->fc_acc = nullptr; m->fc_cap = 0; m->fc_valid = false;
+    if (m->kn_stamp) chk(hipFree(m->kn_stamp), "hipFree");
+    m->kn_stamp = nullptr; m->kn_integrated = false;
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
@@ -1453,6 +1455,217 @@ extern "C" int dspmap_query_forecast_device(dspmap_t* m, int n, const dspmap_que
     return DSPMAP_OK;
 }
 
+// --------------------------------------------------- known-space layer (dspmap_known.hip; semantics in include/dspmap.h)
+// the window of the current position: lattice index k0 of map voxel 0 and the offset o of that cell's centre from the sensor, per axis, in
+// double from the floats cur_pos and res (dspmap.h states the arithmetic; tests/known_ref.py restates it)
+static int known_window(dspmap* m, long long k0[3], float o[3]) {
+    const int n[3] = {m->d.nx, m->d.ny, m->d.nz};
+    const double res = (double)m->d.res;
+    for (int a = 0; a < 3; ++a) {
+        const double cur = (double)m->cur_pos[a];
+        const double g = cur / res - (double)n[a] / 2.0;
+        if (!(fabs(g) < 4.0e15))   // (also NaN: dspmap_set_current_position takes any float)
+            return dspmap_fail(m, DSPMAP_E_STATE, "known space: the current position %g on axis %d is not finite or beyond 4e15 cells", cur, a);
+        k0[a] = (long long)floor(g + 0.5);
+        o[a] = (float)(((double)k0[a] + 0.5) * res - cur);
+    }
+    return DSPMAP_OK;
+}
+static int known_slot(long long k, int n) { const long long r = k % n; return (int)(r < 0 ? r + n : r); }
+// everything forgotten (dspmap_known_reset, dspmap_clear_state, dspmap_load_checkpoint); a handle without a layer has nothing to forget
+static int known_forget(dspmap* m) {
+    m->kn_integrated = false;
+    if (m->kn_stamp) HIPCHK(m, hipMemsetAsync(m->kn_stamp, 0, sizeof(unsigned) * (size_t)m->d.v_glob, m->stream));
+    return DSPMAP_OK;
+}
+// FIRST thing in every entry point that reads or writes the layer: move the window to the current position.  The lattice cells that entered
+// it since the last synchronisation are reset to "never" on the stream (their slots held the cells that left on the other side); a shift of
+// n or more cells on an axis resets everything.  Fills the kernels' arguments.
+static int known_sync(dspmap* m, KnownArgs* a) {
+    long long k0[3];
+    float o[3];
+    const int rc = known_window(m, k0, o);
+    if (rc != DSPMAP_OK) return rc;
+    const MapDims& d = m->d;
+    const int n[3] = {d.nx, d.ny, d.nz};
+    if (m->kn_stamp && (k0[0] != m->kn_k0[0] || k0[1] != m->kn_k0[1] || k0[2] != m->kn_k0[2])) {
+        int s0[3] = {0, 0, 0}, cnt[3] = {0, 0, 0};
+        bool all = false;
+        for (int ax = 0; ax < 3; ++ax) {
+            const long long delta = k0[ax] - m->kn_k0[ax];
+            if (delta >= n[ax] || -delta >= n[ax]) { all = true; break; }
+            // delta > 0: the cells [old + n, new + n) enter, delta < 0: the cells [new, old)
+            if (delta > 0) { s0[ax] = known_slot(m->kn_k0[ax], n[ax]); cnt[ax] = (int)delta; }
+            else if (delta < 0) { s0[ax] = known_slot(k0[ax], n[ax]); cnt[ax] = (int)-delta; }
+        }
+        if (all) HIPCHK(m, hipMemsetAsync(m->kn_stamp, 0, sizeof(unsigned) * (size_t)d.v_glob, m->stream));
+        else launch_known_clear(d, m->stream, m->kn_stamp, s0, cnt);
+        HIPCHK(m, hipGetLastError());
+    }
+    for (int ax = 0; ax < 3; ++ax) m->kn_k0[ax] = k0[ax];
+    a->stamp = m->kn_stamp;
+    a->bx = known_slot(k0[0], d.nx); a->by = known_slot(k0[1], d.ny); a->bz = known_slot(k0[2], d.nz);
+    a->ox = o[0]; a->oy = o[1]; a->oz = o[2];
+    a->max_range = INFINITY;
+    a->occl_margin = m->fp.occl_margin;
+    a->now = (unsigned)m->update_counter;
+    return DSPMAP_OK;
+}
+static int known_whole_map(dspmap* m, const char* what) {
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: a slab handle holds part of the map; the sensor's view crosses slabs", what);
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_known_integrate(dspmap_t* m, float max_range, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!(max_range > 0.f)) return dspmap_fail(m, DSPMAP_E_ARG, "known space: max_range %g is NaN or not positive", (double)max_range);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "known space: unknown flags 0x%x", flags);
+    int rc = known_whole_map(m, "dspmap_known_integrate");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (m->update_counter < 1)
+        return dspmap_fail(m, DSPMAP_E_STATE, "known space: no frame has been accepted yet, there is no view to integrate (dspmap_update)");
+    const bool fresh = !m->kn_stamp;
+    if (fresh) {
+        HIPCHK(m, hipMalloc(&m->kn_stamp, sizeof(unsigned) * (size_t)m->d.v_glob));
+        HIPCHK(m, hipMemsetAsync(m->kn_stamp, 0, sizeof(unsigned) * (size_t)m->d.v_glob, m->stream));
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) {
+        if (fresh) { (void)hipStreamSynchronize(m->stream); (void)hipFree(m->kn_stamp); m->kn_stamp = nullptr; }
+        return rc;
+    }
+    a.max_range = max_range;
+    launch_known_integrate(m->d, m->s, m->stream, a, m->n_cu);
+    HIPCHK(m, hipGetLastError());
+    m->kn_integrated = true;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_known_reset(dspmap_t* m) {
+    READY(m);
+    BENIGN(m);
+    return known_forget(m);
+}
+extern "C" int dspmap_get_known(dspmap_t* m, int* age_out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!age_out) return dspmap_fail(m, DSPMAP_E_ARG, "known space: NULL output array");
+    int rc = known_whole_map(m, "dspmap_get_known");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    const size_t V = (size_t)m->d.v_glob;
+    if (!m->kn_stamp) {   // never integrated: nothing allocated, nothing known
+        for (size_t i = 0; i < V; ++i) age_out[i] = -1;
+        return DSPMAP_OK;
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    if ((rc = query_buf(m, sizeof(int) * V)) != DSPMAP_OK) return rc;
+    launch_known_ages(m->d, m->stream, a, (int*)m->q_buf);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(age_out, m->q_buf, sizeof(int) * V, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+static int known_query_check(dspmap* m, int n, const void* in, const void* out, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "known query: negative sample count %d", n);
+    if (n > 0 && (!in || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "known query: NULL sample or output array");
+    if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "known query: unknown flags 0x%x", flags);
+    return known_whole_map(m, "dspmap_query_known");
+}
+extern "C" int dspmap_query_known(dspmap_t* m, int n, const dspmap_query* q, int flags, int* age_out) {
+    int rc = known_query_check(m, n, q, age_out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n == 0) return DSPMAP_OK;
+    if (!m->kn_stamp) {
+        for (int i = 0; i < n; ++i) age_out[i] = -1;
+        return DSPMAP_OK;
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    const size_t qb = q_align(sizeof(dspmap_query) * (size_t)n);
+    if ((rc = query_buf(m, qb + sizeof(int) * (size_t)n)) != DSPMAP_OK) return rc;
+    float4* dq = (float4*)m->q_buf;
+    int* dout = (int*)((char*)m->q_buf + qb);
+    HIPCHK(m, hipMemcpyAsync(dq, q, sizeof(dspmap_query) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    launch_known_query(m->d, m->stream, a, (flags & DSPMAP_QUERY_WORLD) ? 1 : 0, m->cur_pos, n, dq, dout);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(age_out, dout, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_known_device(dspmap_t* m, int n, const dspmap_query* q, int flags, int* age_out) {
+    int rc = known_query_check(m, n, q, age_out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n == 0) return DSPMAP_OK;
+    if (!m->kn_stamp) {   // never integrated: every byte 0xff is the int -1
+        HIPCHK(m, hipMemsetAsync(age_out, 0xff, sizeof(int) * (size_t)n, m->stream));
+        return DSPMAP_OK;
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    launch_known_query(m->d, m->stream, a, (flags & DSPMAP_QUERY_WORLD) ? 1 : 0, m->cur_pos, n, (const float4*)q, age_out);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_mask_cast_grid(dspmap_t* m, int max_age, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "mask cast grid: negative max_age %d", max_age);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "mask cast grid: unknown flags 0x%x", flags);
+    int rc = cast_grid_ready(m, "dspmap_mask_cast_grid");
+    if (rc != DSPMAP_OK) return rc;
+    if (!m->kn_stamp || !m->kn_integrated)
+        return dspmap_fail(m, DSPMAP_E_STATE, "mask cast grid: no frame has been integrated into the known-space layer (dspmap_known_integrate)");
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    m->rf_valid = false;   // (arrival fields were grown in the grid as it was)
+    launch_known_mask(m->d, m->stream, a, max_age, m->d.T + 1, m->cg_bits);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_known_stats(dspmap_t* m, int max_age, long long out[2]) {
+    if (!m) return DSPMAP_E_ARG;
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "known stats: negative max_age %d", max_age);
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "known stats: NULL output array");
+    int rc = known_whole_map(m, "dspmap_known_stats");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    out[0] = out[1] = 0;
+    if (!m->kn_stamp) return DSPMAP_OK;
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    if ((rc = query_buf(m, 2 * sizeof(u64))) != DSPMAP_OK) return rc;
+    u64 sums[2] = {0, 0};
+    HIPCHK(m, hipMemsetAsync(m->q_buf, 0, sizeof(sums), m->stream));
+    launch_known_count(m->d, m->stream, a, max_age, (u64*)m->q_buf);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(sums, m->q_buf, sizeof(sums), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    out[0] = (long long)sums[0]; out[1] = (long long)sums[1];
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_view(dspmap_t* m, float* planes_h, float* planes_v, float* maxlen) {
+    READY(m);
+    BENIGN(m);
+    const MapDims& d = m->d;
+    if (maxlen && m->update_counter < 1 && m->last_n_points == 0) {   // (before the first frame or binning stage the device array is not initialised)
+        for (int i = 0; i < d.np; ++i) maxlen[i] = -1.f;
+        maxlen = nullptr;
+    }
+    if (planes_h) HIPCHK(m, hipMemcpyAsync(planes_h, m->s.planes_h, sizeof(float) * 3 * (size_t)(d.np_h + 1), hipMemcpyDeviceToHost, m->stream));
+    if (planes_v) HIPCHK(m, hipMemcpyAsync(planes_v, m->s.planes_v, sizeof(float) * 3 * (size_t)(d.np_v + 1), hipMemcpyDeviceToHost, m->stream));
+    if (maxlen) HIPCHK(m, hipMemcpyAsync(maxlen, m->s.obs_maxlen, sizeof(float) * (size_t)d.np, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+
 extern "C" void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz) {  // :1556-1572
     const MapDims& d = m->d;
     const int zc = d.ny * d.nx;
@@ -1533,6 +1746,7 @@ extern "C" int dspmap_clear_state(dspmap_t* m) {
     m->fut_clear_pending = false;
     HIPCHK(m, hipMemsetAsync(m->s.pyr_cnt, 0, sizeof(int) * d.np, m->stream));
     HIPCHK(m, hipMemsetAsync(&m->s.fs->vmax_bits, 0, sizeof(int), m->stream));   // (no particle, no speed)
+    { const int rc = known_forget(m); if (rc != DSPMAP_OK) return rc; }   // a new state: nothing has been seen
     HIPCHK(m, hipStreamSynchronize(m->stream));
     if (m->stream3) HIPCHK(m, hipStreamSynchronize(m->stream3));
     if (m->hint_host) m->hint_host[3] = 0;   // a new state: an earlier frame's give-up on the estimator's queue is history (also: dspmap_load_checkpoint)
@@ -1917,6 +2131,7 @@ extern "C" int dspmap_save_checkpoint(dspmap_t* m, const char* path) {
 extern "C" int dspmap_load_checkpoint(dspmap_t* m, const char* path) {
     READY(m);
     dspmap_snapshots_stale(m);
+    { const int rc = known_forget(m); if (rc != DSPMAP_OK) return rc; }   // (the layer is not part of a checkpoint: its stamps belong to the counter of the state that is replaced)
     if (!path) return DSPMAP_E_ARG;
     FILE* f = fopen(path, "rb");
     if (!f) return dspmap_fail(m, DSPMAP_E_ARG, "cannot open %s", path);

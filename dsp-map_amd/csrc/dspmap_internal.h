@@ -198,6 +198,13 @@ struct dspmap {
     bool fc_valid = false;
     int fc_n = 0;                    // layers of the last build ...
     float fc_t[DSPMAP_FORECAST_MAX_TIMES] = {};   // ... and their times
+    // known-space layer (dspmap_known_integrate): one stamp per world lattice cell of the window, toroidal slots [nz][ny][nx]; allocated by the
+    // first integration, freed with the device state.  NOT a snapshot: it lives through frames.  kn_k0: the window (lattice index of map
+    // voxel 0 per axis) the slots were last synchronised to -- every entry point synchronises before it reads or writes (dspmap_known_sync
+    // in dspmap_api.hip); kn_integrated: some frame has been integrated since the layer was last reset
+    unsigned* kn_stamp = nullptr;
+    long long kn_k0[3] = {0, 0, 0};
+    bool kn_integrated = false;
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;

@@ -244,6 +244,22 @@ struct ForecastQueryArgs {
     const float* field;  // [n][V]
 };
 void launch_forecast_query(const LaunchCtx& c, const ForecastQueryArgs& a, int n, const float4* q, float* out);
+// known-space layer (dspmap_known.hip; semantics in include/dspmap.h, dspmap_known_integrate).  These launchers take the dimensions and the
+// stream, not a LaunchCtx: nothing of the frame's scratch or of its launch decisions is involved
+struct KnownArgs {
+    unsigned* stamp;     // [nz][ny][nx] SLOTS: lattice cell k of an axis lives in slot k mod n; 0 = never, else the update counter of the last frame that saw it
+    int bx, by, bz;      // the slot of map voxel 0 per axis: k0 mod n, in [0, n)
+    float ox, oy, oz;    // centre of the lattice cell behind voxel (0, 0, 0) relative to the sensor
+    float max_range;     // the caller's sensor range (+inf: none)
+    float occl_margin;   // FilterParams::occl_margin
+    unsigned now;        // the handle's update counter
+};
+void launch_known_integrate(const MapDims& d, const DevState& s, hipStream_t stream, const KnownArgs& a, int n_cu);
+void launch_known_clear(const MapDims& d, hipStream_t stream, unsigned* stamp, const int slot0[3], const int count[3]);   // per axis: slots [slot0, slot0 + count) mod n
+void launch_known_ages(const MapDims& d, hipStream_t stream, const KnownArgs& a, int* out);   // [V] ages, the reference's voxel order
+void launch_known_query(const MapDims& d, hipStream_t stream, const KnownArgs& a, int world, const float cur[3], int n, const float4* q, int* out);
+void launch_known_count(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, u64* sums);   // sums[2], zeroed by the caller
+void launch_known_mask(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, int L, u64* bits);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

@@ -308,6 +308,17 @@ public:
     int queryForecast(int n, const dspmap_query* q, float* out, bool world = false, bool lerp = false, float outside_value = 1.f) {
         return dspmap_query_forecast(h_, n, q, (world ? DSPMAP_QUERY_WORLD : 0) | (lerp ? DSPMAP_FORECAST_LERP : 0), outside_value, out);
     }
+    /* extension: known space (dspmap_known_integrate in dspmap.h): remember which voxels the last update()'s view reached -- inside a
+     * pyramid, not behind its farthest return, within max_range -- anchored in the world, so that "free because observed" stays apart
+     * from "free because nobody looked".  getKnownAge copies V ages (frames since a voxel was last seen, -1 = never), queryKnown reads
+     * the age at sample points, maskCastGridUnknown marks every voxel older than max_age (or never seen) as blocked in all layers of the
+     * cast grid, for the casts, boxes and arrival fields that read it.  Return DSPMAP_OK or a negative error code. */
+    int integrateKnownSpace(float max_range = INFINITY) { return dspmap_known_integrate(h_, max_range, 0); }
+    int getKnownAge(int* ages) { return dspmap_get_known(h_, ages); }
+    int queryKnown(int n, const dspmap_query* q, int* ages, bool world = false) {
+        return dspmap_query_known(h_, n, q, world ? DSPMAP_QUERY_WORLD : 0, ages);
+    }
+    int maskCastGridUnknown(int max_age) { return dspmap_mask_cast_grid(h_, max_age, 0); }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

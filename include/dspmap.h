@@ -611,6 +611,58 @@ int dspmap_query_forecast(dspmap_t* m, int n, const dspmap_query* q_host, int fl
 /* the same on device arrays; enqueued on the handle's stream, no synchronisation */
 int dspmap_query_forecast_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, float outside_value, float* out_dev);
 
+/* ---- known-space layer: which voxels the sensor has seen, and when (no counterpart in the reference, which decides per frame what it can
+ * see -- the rotated pyramid planes :1329-1367, the per-pyramid farthest return point_cloud_max_length, the occlusion rule of mapUpdate
+ * :761 -- and keeps none of it).  The map reports a mass of 0 both for a voxel the filter has looked through and emptied and for one it
+ * has never seen: behind a wall, outside the field of view, in the part of the map the vehicle has only just moved into.  This layer
+ * keeps "the last frame in which the weight update reached this cell" per cell, anchored in the WORLD so that it survives ego motion.
+ * It is an extension beside the frame: the frame path, its launch chain and the captured graph do not know about it.
+ *
+ *  - window.  Per axis a, on the host in double from the floats cur = current position (the sensor position of the last accepted
+ *    update, or dspmap_set_current_position) and res = voxel_resolution, n = the map's voxels on that axis:
+ *        g = cur / res - n / 2          k0 = floor(g + 0.5)  (64-bit)          o = (float)((k0 + 0.5) * res - cur)
+ *    Map voxel i of that axis corresponds one-to-one to the world lattice cell k0 + i (pitch res, aligned at multiples of res); the
+ *    voxel's centre always lies inside that cell.  A cell lives in slot (k0 + i) mod n (positive modulo) of a store of one 32-bit stamp
+ *    per cell.  When k0 differs from the k0 the layer was last synchronised at, every lattice cell that ENTERS the window is reset to 0
+ *    ("never") before anything reads or writes the layer; a shift of n or more cells on an axis resets everything.  Every entry point
+ *    below synchronises first, not only dspmap_known_integrate.  A current position that is not finite is DSPMAP_E_STATE.
+ *  - what a frame sees.  For cell (ix, iy, iz): p_a = fl(fl((float)i_a * res) + o_a), the cell's centre relative to the sensor.  The
+ *    cell is seen when (1) it lies in a pyramid b of the frame's rotated planes (ifInPyramidsArea + findPointPyramid*Index on p,
+ *    :1329-1367), (2) with dist = sqrtf(fl(fl(px * px + py * py) + pz * pz)) it is not occluded by :761, i.e. NOT (maxlen[b] > 0 and
+ *    dist > fl(maxlen[b] + DSPMAP_P_OCCLUSION_MARGIN)), and (3) dist <= max_range, the caller's sensor range.  max_range = +inf gives
+ *    the reference's own rule: a pyramid without a return counts as seen through, as mapUpdate treats its particles.  A cell is judged
+ *    at its centre, as the reference judges a particle at its position.
+ *  - stamps and ages.  A seen cell gets stamp = DSPMAP_P_UPDATE_COUNTER (>= 1); other cells keep theirs; integrating the same frame
+ *    twice changes nothing.  age = update counter now - stamp, or -1 for a cell never seen.  Frames without an integration age the
+ *    layer; a rejected update() changes neither the counter nor the view.
+ *  - dspmap_known_integrate: enqueued on the handle's stream behind the last frame, no synchronisation.  max_range NaN or <= 0 and
+ *    flags != 0 are DSPMAP_E_ARG; a sharded handle (slab) and a handle without an accepted frame are DSPMAP_E_STATE.  The store (4
+ *    bytes per voxel) is allocated by the first call and freed with the device state; a handle that never calls it allocates nothing.
+ *    The layer is no snapshot: it stays through frames.  dspmap_known_reset, dspmap_clear_state and dspmap_load_checkpoint forget
+ *    everything (the layer is not part of a checkpoint).
+ *  - dspmap_get_known: V ages in the reference's voxel order (:1081); synchronous.  Before the first integration every age is -1.
+ *  - dspmap_query_known*: the age of the cell behind the voxel that holds the sample (dspmap_point_voxel_index's expression); samples,
+ *    frame convention and DSPMAP_QUERY_WORLD as in dspmap_query_occupancy; t is ignored.  -1 outside the map or for a NaN coordinate.
+ *    The _device variant only enqueues.
+ *  - dspmap_mask_cast_grid: ORs into EVERY layer of the valid cast grid the bit of each voxel whose age is -1 or > max_age, so that
+ *    casts, boxes and arrival fields treat unknown space as blocked.  Bits at x >= nx stay 0; unknown space is not inflated; arrival
+ *    fields built before the call are stale.  Enqueued, no synchronisation.  max_age < 0 and flags != 0 are DSPMAP_E_ARG; a stale or
+ *    never-built grid is DSPMAP_E_STATE with a text naming dspmap_build_cast_grid, a layer without an integration since its last reset
+ *    DSPMAP_E_STATE with a text naming dspmap_known_integrate.
+ *  - dspmap_known_stats: out[0] = cells with 0 <= age <= max_age, out[1] = cells stamped by the current frame; synchronous.
+ *  - dspmap_get_view: host copies of the last frame's rotated plane normals ([(half_fov_h * 2 / angle_resolution) + 1][3] and the
+ *    vertical counterpart) and of the per-pyramid farthest return ([dspmap_pyramid_num], -1 = no return); any pointer may be NULL;
+ *    synchronous.
+ *  Arguments are checked before the device is touched; a valid call without a usable device is DSPMAP_E_DEVICE. */
+int dspmap_known_integrate(dspmap_t* m, float max_range, int flags /* must be 0 */);
+int dspmap_known_reset(dspmap_t* m);
+int dspmap_get_known(dspmap_t* m, int* age_out_host);             /* V ints; synchronous */
+int dspmap_query_known(dspmap_t* m, int n, const dspmap_query* q_host, int flags, int* age_out_host);
+int dspmap_query_known_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, int* age_out_dev);
+int dspmap_mask_cast_grid(dspmap_t* m, int max_age, int flags /* must be 0 */);
+int dspmap_known_stats(dspmap_t* m, int max_age, long long out[2]);
+int dspmap_get_view(dspmap_t* m, float* planes_h_host, float* planes_v_host, float* maxlen_host);
+
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
 int dspmap_point_voxel_index(const dspmap_t* m, float px, float py, float pz, int* index);
