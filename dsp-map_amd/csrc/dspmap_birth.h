@@ -60,12 +60,15 @@ struct BirthView {
 __device__ __forceinline__ BirthView birth_view(const DevState& s) {
     BirthView v;
     const FrameParams* fp = s.fpar;
-    const int mode = fp->static_birth;
-    v.live = mode == 1 && s.fs->view_epoch == fp->epoch;
+    // (every word the choice below may need is requested at once -- one scalar round trip, not one per decision: the birth kernels
+    // are as long as their chains of dependent loads)
+    const int mode = fp->static_birth, epoch = fp->epoch, n_pts = fp->n_pts, n_given = fp->n_birth;
+    const int view_epoch = s.fs->view_epoch, stale_n = s.fs->stale_n, est_n = s.fs->est_n;
+    v.live = mode == 1 && view_epoch == epoch;
     v.stored = fp->birth; v.rot = s.pt_rot; v.pyr = s.pt_pyr;
     v.cx = fp->cur_pos[0]; v.cy = fp->cur_pos[1]; v.cz = fp->cur_pos[2];
     // mode 2: the device velocity estimator wrote the cloud (and its length) -- or left the previous one (empty view)
-    v.n = mode == 1 ? (v.live ? fp->n_pts : s.fs->stale_n) : (mode == 2 ? s.fs->est_n : fp->n_birth);
+    v.n = mode == 1 ? (v.live ? n_pts : stale_n) : (mode == 2 ? est_n : n_given);
     return v;
 }
 __device__ __forceinline__ BirthSrc birth_at(const BirthView& v, int i) {
@@ -131,31 +134,40 @@ __device__ __forceinline__ void birth_rank_block(const MapDims& d, const DevStat
 // and the rank only: in a whole frame it rides on k_place's launch.
 #define BIRTH_BUCKET_CAP 128
 // inside_out: the caller collects the "inside the map" bits itself (a wave that generates all children of one point: a ballot)
+// The children's bucket entries, a wave at a time (call from wave-uniform control flow; lv < 0 = no entry for this lane).  The
+// children of a point land in a handful of neighbouring voxels, and a returning same-address atomic in memory is a round trip
+// of 12 - 100 ns that the next one queues behind: the lanes with the same voxel take ONE atomic together, and all those of the
+// wave go out in one instruction (wave_agg_inc_once).  Which children sit in a bucket, and where, is free: k_birth_insert ranks
+// by birth index over the bucket and the overflow list.
+__device__ __forceinline__ void birth_bucket_put(const DevState& s, int* __restrict__ vb_cnt, int* __restrict__ vb_idx, const int lv, const int t) {
+    const int pos = wave_agg_inc_once(vb_cnt, lv, lv >= 0);
+    if (lv >= 0) {
+        if (pos < BIRTH_BUCKET_CAP) vb_idx[(size_t)lv * BIRTH_BUCKET_CAP + pos] = t;
+        else s.birth_ovf[atomicAdd(&s.fs->n_birth_ovf, 1)] = t;   // bucket full: WHICH children land in it depends on the arrival
+                                                                  // order, so the others are kept too (k_birth_insert ranks over both)
+    }
+}
 __device__ __forceinline__ void birth_child_thread(const MapDims& d, const DevState& s, const FilterParams& fp, float4* __restrict__ child,
                                                    int* __restrict__ vb_cnt, int* __restrict__ vb_idx, const int t, bool* inside_out = nullptr) {
     const BirthView bv = birth_view(s);
     const int n_birth = bv.n;
     const int nb = fp.nb_num;
     const int i = t / nb, k = t - i * nb;
-    if (i >= n_birth) return;
     float cx, cy, cz; int gsrc;
-    if (!birth_src_voxel(d, s, birth_at(bv, i), cx, cy, cz, gsrc)) return;
-    const int c = (int)(((long long)s.plan_pbase[i] + 3 * k) % fp.tab_n);
-    const float x = cx + s.p_tab[c];                         // :871-873
-    const float y = cy + s.p_tab[(c + 1) % fp.tab_n];
-    const float z = cz + s.p_tab[(c + 2) % fp.tab_n];
-    int gv = 0;
     int lv = -1;
-    if (voxel_of_lv(d, x, y, z, gv, lv)) {                   // :875
-        if (inside_out) *inside_out = true; else atomicOr(&s.plan_inside[i], 1u << k);
-        if (lv >= 0) {                                       // children landing in another slab are inserted by their owner
-            const int pos = atomicAdd(&vb_cnt[lv], 1);
-            if (pos < BIRTH_BUCKET_CAP) vb_idx[(size_t)lv * BIRTH_BUCKET_CAP + pos] = t;
-            else s.birth_ovf[atomicAdd(&s.fs->n_birth_ovf, 1)] = t;   // bucket full: WHICH children land in it depends on the arrival
-                                                                      // order, so the others are kept too (k_birth_insert ranks over both)
+    if (i < n_birth && birth_src_voxel(d, s, birth_at(bv, i), cx, cy, cz, gsrc)) {
+        const int c = (int)(((long long)s.plan_pbase[i] + 3 * k) % fp.tab_n);
+        const float x = cx + s.p_tab[c];                         // :871-873
+        const float y = cy + s.p_tab[(c + 1) % fp.tab_n];
+        const float z = cz + s.p_tab[(c + 2) % fp.tab_n];
+        int gv = 0;
+        if (voxel_of_lv(d, x, y, z, gv, lv)) {                   // :875
+            if (inside_out) *inside_out = true; else atomicOr(&s.plan_inside[i], 1u << k);
+            if (lv < 0) lv = -1;                                 // children landing in another slab are inserted by their owner
         } else {
             lv = -1;
         }
+        child[t] = make_float4(x, y, z, __int_as_float(lv));
     }
-    child[t] = make_float4(x, y, z, __int_as_float(lv));
+    birth_bucket_put(s, vb_cnt, vb_idx, lv, t);
 }

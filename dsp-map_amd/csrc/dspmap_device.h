@@ -94,6 +94,27 @@ __device__ __forceinline__ int wave_agg_inc(int* cnt, int key, bool active) {
     }
     return pos;
 }
+// The same with ALL groups' atomics in ONE instruction, for counters in memory whose same-address atomics cost a round trip each:
+// the groups are formed first, with ballots and lane reads only (no memory access in the loop), then every group's lowest lane
+// adds its group's size at once and the members take base + rank.  (wave_agg_inc waits for one atomic per distinct key.)
+// Must be called from wave-uniform control flow (inactive lanes pass active=false).
+__device__ __forceinline__ int wave_agg_inc_once(int* cnt, int key, bool active) {
+    const int l = lane_id();
+    u64 todo = __ballot(active);
+    int gsize = 0, grank = 0, lead = l;
+    while (todo) {
+        const int first = __ffsll((long long)todo) - 1;
+        const int k = __builtin_amdgcn_readlane(key, first);
+        const bool mine = active && key == k;
+        const u64 grp = __ballot(mine);
+        if (mine) { gsize = (int)__popcll(grp); grank = (int)__popcll(grp & ((1ull << l) - 1ull)); lead = first; }
+        todo &= ~grp;
+    }
+    int base = 0;
+    if (active && lead == l) base = atomicAdd(&cnt[key], gsize);
+    base = __shfl(base, lead, WAVE);
+    return active ? base + grank : -1;
+}
 // single-counter variant
 __device__ __forceinline__ int wave_agg_inc1(int* cnt, bool active) {
     const u64 grp = __ballot(active);

@@ -1171,22 +1171,16 @@ __device__ __forceinline__ void birth_point_wave(const MapDims& d, const DevStat
     }
     // ... and this lane's child (:871-875)
     bool in = false;
+    const int t = i * nb + l;
+    int lvc = -1;
     if (l < nb) {
-        const int t = i * nb + l;
         const float x = pl.cx + t0, y = pl.cy + t1, z = pl.cz + t2;
-        int gvc = 0, lvc = -1;
-        if (voxel_of_lv(d, x, y, z, gvc, lvc)) {
-            in = true;
-            if (lvc >= 0) {                                      // children landing in another slab are inserted by their owner
-                const int pos = atomicAdd(&vb_cnt[lvc], 1);
-                if (pos < BIRTH_BUCKET_CAP) vb_idx[(size_t)lvc * BIRTH_BUCKET_CAP + pos] = t;
-                else s.birth_ovf[atomicAdd(&s.fs->n_birth_ovf, 1)] = t;
-            } else {
-                lvc = -1;
-            }
-        }
+        int gvc = 0;
+        if (voxel_of_lv(d, x, y, z, gvc, lvc)) in = true;
+        if (!in || lvc < 0) lvc = -1;                            // children landing in another slab are inserted by their owner
         child[t] = make_float4(x, y, z, __int_as_float(lvc));
     }
+    birth_bucket_put(s, vb_cnt, vb_idx, lvc, t);
     const unsigned inside = (unsigned)__ballot(in);
     // the split (:827-866)
     int n_static = 0;
@@ -1343,39 +1337,95 @@ template <bool FUSED>
 __global__ void __launch_bounds__(256) k_birth_insert(MapDims d, DevState s, FilterParams fp, const float4* __restrict__ child,
                                const int* __restrict__ vb_cnt, const int* __restrict__ vb_idx, int* __restrict__ part_birth,
                                const u64* __restrict__ nbsnap, int wg_off) {
-    // (DSPMAP_P_ESTIMATOR_QUEUE) the frame's first birth kernel gave up waiting for the estimator's queue: the birth cloud is not complete
-    // and nothing of it is inserted -- the frame ends without a birth stage, the host fails its next call (dspmap_check_estimator_queue)
-    if (s.xq && s.fpar->from_ring && __hip_atomic_load(s.xq + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)(s.fpar->ring_pos + 1u)) {
-        if (threadIdx.x < 2) part_birth[blockIdx.x * 2 + threadIdx.x] = 0;
-        return;
-    }
+    // This kernel is as long as its chain of dependent loads, so everything is requested in as few round trips as the data allow:
+    //   1  the frame's scalars and the estimator queue's give-up word
+    //   2  everything that only needs (i, t) -- plan, "inside" word, child, source point, newborn weight -- and (FUSED) the draw
+    //      counts the cursor prefix is made of: the split's group sums and the block's window of per-point counts
+    //   3  (behind the prefix's barrier) the destination voxel's bucket and occupancy, the table draws
+    // Nothing of round trip 2 is used before the give-up word has been looked at.
+    const int from_ring = s.fpar->from_ring;   // (with birth_view's words: one scalar round trip)
+    const unsigned ring_pos = s.fpar->ring_pos;
+    const bool ring = s.xq && from_ring;
+    const int xq_pos = (int)(ring_pos + 1u);
     const BirthView bv = birth_view(s);
     const int n_birth = bv.n;
+    int xq_word = 0;
+    if (ring) xq_word = __hip_atomic_load(s.xq + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int tid = (int)threadIdx.x;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int nb = fp.nb_num;
     const int i = t / nb, k = t - i * nb;
-    bool born = false, dropped = false;
-    int f_vbase = 0, f_rbase = 0;
+    // FUSED: the draws before point i = the sums of the split's workgroups (16 points each) wholly before this block's first point
+    // + the points of the block's window [16 G, i): the window is at most 16 + 256 / nb entries (272 at nb = 1), loaded coalesced
+    // -- one entry per thread and a remainder of 16 -- and scanned exclusively below.  (Integer sums: any order gives the same cursors.)
+    const int i_first = (int)((blockIdx.x * blockDim.x) / (unsigned)nb), i_last = (int)((blockIdx.x * blockDim.x + 255u) / (unsigned)nb);
+    const int G = min(i_first, n_birth) >> 4;
+    const int w_end = min(i_last + 1, n_birth);       // the window is [16 G, w_end)
+    const int ngr = (n_birth + 15) >> 4;
+    int2 we = make_int2(0, 0), wr = make_int2(0, 0);  // window entries tid and 256 + tid
+    int2 wg0 = make_int2(0, 0);                       // this thread's first group sum (the others, past 4096 points, follow below)
+    int v0 = 0, r0 = 0;
     if (FUSED) {
-        __shared__ int s_part[4][4];
-        const int tid = (int)threadIdx.x;
-        const int i_first = (int)((blockIdx.x * blockDim.x) / (unsigned)nb);
-        const int G = min(i_first, n_birth) >> 4;     // workgroups of the split (16 points each) wholly before this block's first point
-        const int ngr = (n_birth + 15) >> 4;
-        int acc[4] = {0, 0, 0, 0};                    // {velocity draws before, rand() draws before, all velocity draws, all rand() draws}
-        for (int g = tid; g < ngr; g += 256) {
+        if ((G << 4) + tid < w_end) we = s.birth_cvr[(G << 4) + tid];
+        if (tid < 16 && (G << 4) + 256 + tid < w_end) wr = s.birth_cvr[(G << 4) + 256 + tid];
+        if (tid < ngr) wg0 = s.birth_cvr[wg_off + tid];
+        v0 = s.fs->v_cur_in; r0 = s.fs->r_cur_in;
+    }
+    BirthPlan pl;
+    pl.gvox = -1; pl.n_static = 0;
+    unsigned pl_inside = 0u;
+    float4 ch = make_float4(0.f, 0.f, 0.f, 0.f);
+    BirthSrc src;
+    src.nx = src.ny = 0.f; src.intensity = 0.f;
+    float newborn_w = 0.f;
+    if (i < n_birth) {
+        pl = s.plan[i];
+        pl_inside = s.plan_inside[i];
+        ch = child[t];          // (garbage for children that were not generated: only used under the tests below)
+        src = birth_at(bv, i);
+        newborn_w = s.fs->newborn_w;
+    }
+    int acc[4] = {0, 0, 0, 0};                        // {velocity draws before, rand() draws before, all velocity draws, all rand() draws}
+    if (FUSED) {
+        acc[2] = wg0.x; acc[3] = wg0.y;
+        if (tid < G) { acc[0] = wg0.x; acc[1] = wg0.y; }
+        for (int g = tid + 256; g < ngr; g += 256) {
             const int2 w = s.birth_cvr[wg_off + g];
             acc[2] += w.x; acc[3] += w.y;
             if (g < G) { acc[0] += w.x; acc[1] += w.y; }
         }
-        int2 loc = make_int2(0, 0);
-        for (int j = G << 4; j < min(i, n_birth); ++j) { const int2 c = s.birth_cvr[j]; loc.x += c.x; loc.y += c.y; }   // (at most 15 + 256 / nb points)
+    }
+    asm volatile("" : "+v"(xq_word));   // (the word is looked at HERE, not where it was requested: its round trip is everybody's)
+    // (DSPMAP_P_ESTIMATOR_QUEUE) the frame's first birth kernel gave up waiting for the estimator's queue: the birth cloud is not complete
+    // and nothing of it is inserted -- the frame ends without a birth stage, the host fails its next call (dspmap_check_estimator_queue)
+    if (ring && xq_word == xq_pos) {
+        if (threadIdx.x < 2) part_birth[blockIdx.x * 2 + threadIdx.x] = 0;
+        return;
+    }
+    bool born = false, dropped = false;
+    int f_vbase = 0, f_rbase = 0;
+    if (FUSED) {
+        __shared__ int s_part[4][4];
+        __shared__ int2 s_pre[256 + 16];    // exclusive prefix of the window WITHIN each run of 64 entries (the remainder is a fifth run)
+        __shared__ int2 s_run[4];           // the totals of the four full runs
+        const int wv = tid >> 6;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { acc[q] = wave_sum_i(acc[q]); if (lane_id() == 0) s_part[tid >> 6][q] = acc[q]; }
+        for (int q = 0; q < 4; ++q) { acc[q] = wave_sum_i(acc[q]); if (lane_id() == 0) s_part[wv][q] = acc[q]; }
+        const int2 inc = make_int2(wave_incl_scan_i(we.x), wave_incl_scan_i(we.y));
+        s_pre[tid] = make_int2(inc.x - we.x, inc.y - we.y);
+        if (lane_id() == 63) s_run[wv] = inc;
+        if (wv == 0) {
+            const int2 rinc = make_int2(wave_incl_scan_i(wr.x), wave_incl_scan_i(wr.y));
+            if (tid < 16) s_pre[256 + tid] = make_int2(rinc.x - wr.x, rinc.y - wr.y);
+        }
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] = (s_part[0][q] + s_part[1][q]) + (s_part[2][q] + s_part[3][q]);
-        const int v0 = s.fs->v_cur_in, r0 = s.fs->r_cur_in;
+        const int idx = min(i, n_birth) - (G << 4);   // in [0, 270]: i >= i_first >= 16 G, i <= i_first + 255
+        int2 loc = s_pre[idx];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q < (idx >> 6)) { loc.x += s_run[q].x; loc.y += s_run[q].y; }
         f_vbase = (int)(((long long)v0 + acc[0] + loc.x) % fp.tab_n);
         f_rbase = (int)(((long long)r0 + acc[1] + loc.y) % max(fp.rtab_n, 1));
         if (t == 0) {
@@ -1385,15 +1435,8 @@ __global__ void __launch_bounds__(256) k_birth_insert(MapDims d, DevState s, Fil
     }
     if (bv.live && t == 0) s.fs->stale_n = n_birth;
     if (i < n_birth) {
-        // this kernel is a chain of dependent loads: everything that only needs (i, t) is requested at once, then
-        // everything that only needs the destination voxel
-        const BirthPlan pl = s.plan[i];
-        const unsigned pl_inside = s.plan_inside[i];
-        const float4 ch = child[t];          // (garbage for children that were not generated: only used under the tests below)
-        const BirthSrc src = birth_at(bv, i);
         // a non-empty view's synthesised cloud is kept for the frames whose view is empty (:1379-1381)
         if (bv.live && k == 0) const_cast<BirthSrc*>(bv.stored)[i] = src;
-        const float newborn_w = s.fs->newborn_w;
         if (pl.gvox >= 0 && ((pl_inside >> k) & 1u)) {
             const int lv = __float_as_int(ch.w);
             if (lv >= 0) {
