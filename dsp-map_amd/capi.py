@@ -20,7 +20,7 @@ OK, REJECTED = 1, 0
 P_POSITION_STDDEV, P_VELOCITY_STDDEV, P_OBSERVATION_STDDEV, P_NEWBORN_WEIGHT, P_NEWBORN_NUMBER, \
     P_VOXEL_FILTER_RES, P_KAPPA, P_DETECTION, P_VELOCITY_ESTIMATOR, P_REGENERATE_TABLES, P_USE_GRAPH, P_OCCLUSION_MARGIN, \
     P_PAIR_CULL_SIGMAS, P_UPDATE_TIME, P_UPDATE_COUNTER, P_PLACE_SPLIT_TILES, P_FAST_DIVISION, P_SPARSE_SWEEP, P_ROLLOUT_INLINE, \
-    P_RESAMPLE_WG_TILES, P_SWEEP_ALTERNATE, P_STATIC_TILE_SKIP, P_HOST_CLOUD_DIRECT, _P_REMOVED_24, P_ESTIMATOR_QUEUE, P_FRAME_BRANCHES, P_TILING, P_SIDE_PLACEMENT, P_RESAMPLE_SPLIT, P_TILE_BITMAPS = range(1, 31)
+    P_RESAMPLE_WG_TILES, P_SWEEP_ALTERNATE, P_STATIC_TILE_SKIP, P_HOST_CLOUD_DIRECT, _P_REMOVED_24, P_ESTIMATOR_QUEUE, P_FRAME_BRANCHES, P_TILING, P_SIDE_PLACEMENT, P_RESAMPLE_SPLIT, P_TILE_BITMAPS, P_VIEW_CHUNKS = range(1, 32)
 
 
 class Config(C.Structure):
@@ -101,6 +101,10 @@ REACH_WITH_CURRENT = 2       # DSPMAP_REACH_WITH_CURRENT
 REACH_DEVICE_SETS = 4        # DSPMAP_REACH_DEVICE_SETS
 FORECAST_MAX_TIMES = 64      # DSPMAP_FORECAST_MAX_TIMES
 FORECAST_LERP = 2            # DSPMAP_FORECAST_LERP
+# dspmap_view / dspmap_view_score (dspmap_score_views) and the DSPMAP_VIEW_* statuses
+VIEW_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("qw", "f4"), ("qx", "f4"), ("qy", "f4"), ("qz", "f4"), ("max_range", "f4"), ("t", "f4")])
+VIEW_SCORE_DTYPE = np.dtype([("n_seen", "i4"), ("n_unknown", "i4"), ("n_returns", "i4"), ("status", "i4")])
+VIEW_OK, VIEW_BLOCKED, VIEW_OUTSIDE, VIEW_INVALID = 0, 1, 3, 4
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -170,6 +174,10 @@ SIGNATURES = {
     "dspmap_mask_cast_grid": (_i, [_P, _i, _i]),
     "dspmap_known_stats": (_i, [_P, _i, _P]),
     "dspmap_get_view": (_i, [_P, _P, _P, _P]),
+    "dspmap_score_views": (_i, [_P, _i, _P, _i, _i, _P]),
+    "dspmap_score_views_device": (_i, [_P, _i, _P, _i, _i, _P]),
+    "dspmap_view_rays": (_i, [_P, _P, _P, _P, _P]),
+    "dspmap_debug_view_cells": (_i, [_P, _P, _i, _P, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -925,6 +933,56 @@ class DSPMap:
         ph, pv, ml = np.zeros((nh + 1, 3), np.float32), np.zeros((nv + 1, 3), np.float32), np.zeros((nh, nv), np.float32)
         self._chk(self.L.dspmap_get_view(self.h, _ptr(ph), _ptr(pv), _ptr(ml)))
         return ph, pv, ml
+
+    # -- scores of candidate viewpoints (extension; semantics in include/dspmap.h next to dspmap_score_views)
+    def score_views(self, views, max_age, world=False):
+        """what a frame taken from every view {x, y, z, qw, qx, qy, qz, max_range, t} of views ([n, 9] float32) would see in the cast grid
+        as it is: the voxels in its wedge, not behind the first blocked cell of their pyramid's central ray and within max_range
+        (n_seen), those of them whose age in the known-space layer is -1 or > max_age (n_unknown), and the rays that hit (n_returns).
+        numpy in -> structured numpy (VIEW_SCORE_DTYPE, status = VIEW_*) out, synchronous; a torch tensor on the GPU -> an int32 [n, 4]
+        tensor {n_seen, n_unknown, n_returns, status} on the same device, enqueued on the handle's stream and ordered with torch's
+        current stream like query_known."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(views):
+            import torch
+            q = self._device_samples(views, (9,), "score_views")
+            n = q.numel() // 9
+            out = torch.empty((n, 4), dtype=torch.int32, device=q.device)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_score_views_device(self.h, n, q.data_ptr(), int(max_age), flags, out.data_ptr()))
+            after()
+            return out
+        q = np.ascontiguousarray(views, np.float32)
+        if q.shape[-1:] != (9,):
+            raise ValueError("score_views: views of shape [n, 9]")
+        n = q.size // 9
+        out = np.zeros(n, VIEW_SCORE_DTYPE)
+        self._chk(self.L.dspmap_score_views(self.h, n, _ptr(q), int(max_age), flags, _ptr(out)))
+        return out
+
+    def view_rays(self, quat):
+        """(planes_h [np_h + 1, 3], planes_v [np_v + 1, 3], dirs [NP, 3]) of an attitude (w, x, y, z): the rotated boundary-plane normals a
+        frame with that attitude has, and the central ray of every pyramid, float32 host copies made on the device (synchronous)"""
+        nh = 2 * self.cfg.half_fov_h // self.cfg.angle_resolution
+        nv = 2 * self.cfg.half_fov_v // self.cfg.angle_resolution
+        q = np.ascontiguousarray(quat, np.float32)
+        if q.shape != (4,):
+            raise ValueError("view_rays: a quaternion (w, x, y, z)")
+        ph, pv, dirs = np.zeros((nh + 1, 3), np.float32), np.zeros((nv + 1, 3), np.float32), np.zeros((nh * nv, 3), np.float32)
+        self._chk(self.L.dspmap_view_rays(self.h, _ptr(q), _ptr(ph), _ptr(pv), _ptr(dirs)))
+        return ph, pv, dirs
+
+    def view_cells(self, view, world=False):
+        """test hook: (seen [nz, ny, W] uint64 in the cast grid's word layout, ml [NP] float32) of ONE view ([9] float32): the cells
+        score_views counts in n_seen and the farthest return every pyramid's ray gave (-1 = none); synchronous"""
+        q = np.ascontiguousarray(view, np.float32)
+        if q.shape != (9,):
+            raise ValueError("view_cells: one view of shape [9]")
+        words = np.zeros((self.cfg.nz, self.cfg.ny, (self.cfg.nx + 63) // 64), np.uint64)
+        ml = np.zeros(self.NP, np.float32)
+        self._chk(self.L.dspmap_debug_view_cells(self.h, _ptr(q), QUERY_WORLD if world else 0, _ptr(words), _ptr(ml)))
+        return words, ml
 
     def set_cast_grid(self, words):
         """test hook: replace all layers of the valid cast grid with words (uint64 [L, nz, ny, W], what cast_grid() returns)"""

@@ -235,6 +235,8 @@ static void free_dev(dspmap* m) {
     m->fc_field = nullptr; m->fc_acc = nullptr; m->fc_cap = 0; m->fc_valid = false;
     if (m->kn_stamp) chk(hipFree(m->kn_stamp), "hipFree");
     m->kn_stamp = nullptr; m->kn_integrated = false;
+    if (m->vw_dirs0) chk(hipFree(m->vw_dirs0), "hipFree");
+    m->vw_dirs0 = nullptr;
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
@@ -627,6 +629,7 @@ extern "C" int dspmap_set_param(dspmap_t* m, int key, double v) {
         case DSPMAP_P_FRAME_BRANCHES: m->frame_branches = v < 0 ? -1 : (v != 0 ? 1 : 0); m->graph_epoch++; break;
         case DSPMAP_P_RESAMPLE_SPLIT: m->resample_split = v != 0 ? 1 : 0; m->graph_epoch++; break;
         case DSPMAP_P_TILE_BITMAPS: m->tile_bitmaps = v != 0; m->graph_epoch++; break;
+        case DSPMAP_P_VIEW_CHUNKS: m->vw_chunks = v >= 1.f ? (int)fminf(v, 64.f) : 0; break;   // (launch shape of dspmap_score_views only)
         case DSPMAP_P_SIDE_PLACEMENT: {
             const int iv = v < 0 ? 16 + 3 : (int)v;
             m->side_fork = (iv >> 4) > 2 ? 0 : (iv >> 4);
@@ -691,6 +694,7 @@ extern "C" double dspmap_get_param(const dspmap_t* m, int key) {
         case DSPMAP_P_SIDE_PLACEMENT: return m->side_fork * 16 + m->side_wg;
         case DSPMAP_P_RESAMPLE_SPLIT: return m->resample_split;
         case DSPMAP_P_TILE_BITMAPS: return m->tile_bitmaps ? 1 : 0;
+        case DSPMAP_P_VIEW_CHUNKS: return (float)m->vw_chunks;
         case DSPMAP_P_TILING: return m->d.tiling;
         case DSPMAP_P_USE_GRAPH: return m->use_graph ? 1 : (m->direct_ring ? 2 : 0);
         default: return 0;
@@ -1662,6 +1666,133 @@ extern "C" int dspmap_get_view(dspmap_t* m, float* planes_h, float* planes_v, fl
     if (planes_h) HIPCHK(m, hipMemcpyAsync(planes_h, m->s.planes_h, sizeof(float) * 3 * (size_t)(d.np_h + 1), hipMemcpyDeviceToHost, m->stream));
     if (planes_v) HIPCHK(m, hipMemcpyAsync(planes_v, m->s.planes_v, sizeof(float) * 3 * (size_t)(d.np_v + 1), hipMemcpyDeviceToHost, m->stream));
     if (maxlen) HIPCHK(m, hipMemcpyAsync(maxlen, m->s.obs_maxlen, sizeof(float) * (size_t)d.np, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+
+// --------------------------------------------------- scores of candidate viewpoints (dspmap_view.hip; semantics in include/dspmap.h)
+// the table of unrotated central directions, once per handle: (1, tan alpha_h, tan beta_v) / |.| in double, rounded to fp32
+static int view_dirs(dspmap* m) {
+    if (m->vw_dirs0) return DSPMAP_OK;
+    const MapDims& d = m->d;
+    std::vector<float> t((size_t)d.np * 3);
+    const double step = (double)m->cfg.angle_resolution * 3.14159265358979323846 / 180.0;
+    for (int h = 0; h < d.np_h; ++h)
+        for (int v = 0; v < d.np_v; ++v) {
+            const double y = tan(((double)h - (double)d.np_h / 2.0 + 0.5) * step), z = tan(-((double)v - (double)d.np_v / 2.0 + 0.5) * step);
+            const double len = sqrt(1.0 + y * y + z * z);
+            float* o = &t[3 * ((size_t)h * d.np_v + v)];
+            o[0] = (float)(1.0 / len); o[1] = (float)(y / len); o[2] = (float)(z / len);
+        }
+    float* dev = nullptr;
+    HIPCHK(m, hipMalloc(&dev, sizeof(float) * t.size()));
+    const hipError_t e = hipMemcpy(dev, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice);   // (synchronous: t is a local)
+    if (e != hipSuccess) { (void)hipFree(dev); HIPCHK(m, e); }
+    m->vw_dirs0 = dev;
+    return DSPMAP_OK;
+}
+static void view_args_geometry(const dspmap* m, ViewArgs* a, int flags) {
+    const MapDims& d = m->d;
+    a->world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a->ox = m->cur_pos[0]; a->oy = m->cur_pos[1]; a->oz = m->cur_pos[2];
+    a->cx = -d.half_x + d.res * 0.5f; a->cy = -d.half_y + d.res * 0.5f; a->cz = -d.half_z + d.res * 0.5f;   // dspmap_voxel_center
+    a->dirs0 = m->vw_dirs0;
+    a->reach = d.res * (float)(d.nx + d.ny + d.nz);
+}
+// the argument and state rules of every scoring entry point, in dspmap_grow_boxes' order; then the layer synchronised and the arguments filled
+static int view_check(dspmap* m, int n, const void* in, int max_age, int flags, const void* out, const char* what) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative view count %d", what, n);
+    if (n > 0 && (!in || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL view or output array", what);
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative max_age %d", what, max_age);
+    if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: a slab handle holds part of the map; a view crosses slabs", what);
+    const int rc = cast_grid_ready(m, what);
+    if (rc != DSPMAP_OK) return rc;
+    if (!m->kn_stamp || !m->kn_integrated)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no frame has been integrated into the known-space layer (dspmap_known_integrate)", what);
+    return DSPMAP_OK;
+}
+static int view_args(dspmap* m, int max_age, int flags, ViewArgs* a) {
+    int rc = view_dirs(m);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = known_sync(m, &a->kn)) != DSPMAP_OK) return rc;
+    view_args_geometry(m, a, flags);
+    a->bits = m->cg_bits;
+    a->max_age = max_age;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_score_views(dspmap_t* m, int n, const dspmap_view* views, int max_age, int flags, dspmap_view_score* out) {
+    int rc = view_check(m, n, views, max_age, flags, out, "dspmap_score_views");
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    ViewArgs a;
+    if ((rc = view_args(m, max_age, flags, &a)) != DSPMAP_OK) return rc;
+    const size_t vb = q_align(sizeof(dspmap_view) * (size_t)n);
+    if ((rc = query_buf(m, vb + sizeof(dspmap_view_score) * (size_t)n)) != DSPMAP_OK) return rc;
+    dspmap_view* dv = (dspmap_view*)m->q_buf;
+    dspmap_view_score* ds = (dspmap_view_score*)((char*)m->q_buf + vb);
+    HIPCHK(m, hipMemcpyAsync(dv, views, sizeof(dspmap_view) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m, hipMemsetAsync(ds, 0, sizeof(dspmap_view_score) * (size_t)n, m->stream));
+    launch_view_score(m->d, m->s, m->stream, a, n, view_chunks(m->d, n, m->n_cu, m->vw_chunks), dv, ds, nullptr, nullptr);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(out, ds, sizeof(dspmap_view_score) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_score_views_device(dspmap_t* m, int n, const dspmap_view* views, int max_age, int flags, dspmap_view_score* out) {
+    int rc = view_check(m, n, views, max_age, flags, out, "dspmap_score_views");
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    ViewArgs a;
+    if ((rc = view_args(m, max_age, flags, &a)) != DSPMAP_OK) return rc;
+    HIPCHK(m, hipMemsetAsync(out, 0, sizeof(dspmap_view_score) * (size_t)n, m->stream));
+    launch_view_score(m->d, m->s, m->stream, a, n, view_chunks(m->d, n, m->n_cu, m->vw_chunks), views, out, nullptr, nullptr);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_view_rays(dspmap_t* m, const float quat[4], float* planes_h, float* planes_v, float* dirs) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!quat) return dspmap_fail(m, DSPMAP_E_ARG, "dspmap_view_rays: NULL quaternion");
+    int rc = known_whole_map(m, "dspmap_view_rays");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if ((rc = view_dirs(m)) != DSPMAP_OK) return rc;
+    const MapDims& d = m->d;
+    const size_t nh = 3 * (size_t)(d.np_h + 1), nv = 3 * (size_t)(d.np_v + 1), nd = 3 * (size_t)d.np;
+    if ((rc = query_buf(m, sizeof(float) * (nh + nv + nd))) != DSPMAP_OK) return rc;
+    ViewArgs a = {};
+    view_args_geometry(m, &a, 0);
+    float* o = (float*)m->q_buf;
+    launch_view_rays(d, m->s, m->stream, a, quat, o);
+    HIPCHK(m, hipGetLastError());
+    if (planes_h) HIPCHK(m, hipMemcpyAsync(planes_h, o, sizeof(float) * nh, hipMemcpyDeviceToHost, m->stream));
+    if (planes_v) HIPCHK(m, hipMemcpyAsync(planes_v, o + nh, sizeof(float) * nv, hipMemcpyDeviceToHost, m->stream));
+    if (dirs) HIPCHK(m, hipMemcpyAsync(dirs, o + nh + nv, sizeof(float) * nd, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+// test hook: the seen set of ONE view as a bit grid in the cast grid's word layout, and the farthest returns its rays gave
+extern "C" int dspmap_debug_view_cells(dspmap_t* m, const dspmap_view* view, int flags, unsigned long long* words_out, float* ml_out) {
+    int rc = view_check(m, 1, view, 0, flags, words_out, "dspmap_debug_view_cells");
+    if (rc != DSPMAP_OK) return rc;
+    ViewArgs a;
+    if ((rc = view_args(m, 0, flags, &a)) != DSPMAP_OK) return rc;
+    const size_t lw = cast_layer_words(m->d);
+    const size_t vb = q_align(sizeof(dspmap_view)), sb = q_align(sizeof(dspmap_view_score)), wb = q_align(sizeof(u64) * lw);
+    if ((rc = query_buf(m, vb + sb + wb + sizeof(float) * (size_t)m->d.np)) != DSPMAP_OK) return rc;
+    dspmap_view* dv = (dspmap_view*)m->q_buf;
+    dspmap_view_score* ds = (dspmap_view_score*)((char*)m->q_buf + vb);
+    u64* dw = (u64*)((char*)m->q_buf + vb + sb);
+    float* dm = (float*)((char*)m->q_buf + vb + sb + wb);
+    HIPCHK(m, hipMemcpyAsync(dv, view, sizeof(dspmap_view), hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m, hipMemsetAsync(ds, 0, sb + wb, m->stream));
+    launch_view_score(m->d, m->s, m->stream, a, 1, view_chunks(m->d, 1, m->n_cu, m->vw_chunks), dv, ds, dw, dm);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(words_out, dw, sizeof(u64) * lw, hipMemcpyDeviceToHost, m->stream));
+    if (ml_out) HIPCHK(m, hipMemcpyAsync(ml_out, dm, sizeof(float) * (size_t)m->d.np, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));
     return DSPMAP_OK;
 }

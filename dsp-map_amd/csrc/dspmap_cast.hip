@@ -23,7 +23,7 @@
 // covers the x steps, and segments of a planner's batch that start near each other share lines.  What a skip structure adds is a
 // second snapshot to build per layer and a second test per step in every lane.  A segment of 3 m at 0.15 m crosses ~20 - 35 cells;
 // 131 072 of them are 2 048 waves, eight per CU, whose long lanes overlap other waves' loads.
-#include "dspmap_device.h"
+#include "dspmap_cast_walk.h"
 #include "dspmap_internal.h"
 
 #define CAST_TPB 256
@@ -76,22 +76,6 @@ __global__ void __launch_bounds__(CAST_TPB) k_cast_inflate_z(MapDims d, CastGrid
     a.bits[t] = o;
 }
 
-// one axis of the DDA set-up (include/dspmap.h, steps 2 and 3); pa is inside the map along this axis
-__device__ __forceinline__ void cast_axis(float pa, float pb, float half, float res, int& i, int& st, float& tmax, float& tdelta) {
-    const float ua = __fdiv_rn(__fadd_rn(pa, half), res), ub = __fdiv_rn(__fadd_rn(pb, half), res);
-    i = (int)ua;
-    const float dd = __fsub_rn(ub, ua);
-    st = dd > 0.f ? 1 : (dd < 0.f ? -1 : 0);
-    tmax = INFINITY;
-    tdelta = 0.f;
-    if (st != 0) {
-        const float bnd = (float)(i + (st > 0 ? 1 : 0));
-        tmax = __fdiv_rn(__fsub_rn(bnd, ua), dd);
-        tdelta = __fdiv_rn(1.0f, fabsf(dd));
-    }
-}
-__device__ __forceinline__ bool cast_finite(float v) { return fabsf(v) < INFINITY; }   // (false for NaN)
-
 __global__ void __launch_bounds__(CAST_TPB) k_cast(MapDims d, CastArgs a, int n, const float4* __restrict__ seg, int4* __restrict__ out) {
     const unsigned i = blockIdx.x * CAST_TPB + threadIdx.x;   // (unsigned: n may come within a block of INT_MAX)
     if (i >= (unsigned)n) return;
@@ -106,52 +90,7 @@ __global__ void __launch_bounds__(CAST_TPB) k_cast(MapDims d, CastArgs a, int n,
             ax = __fsub_rn(ax, a.ox); ay = __fsub_rn(ay, a.oy); az = __fsub_rn(az, a.oz);
             bx = __fsub_rn(bx, a.ox); by = __fsub_rn(by, a.oy); bz = __fsub_rn(bz, a.oz);
         }
-        int ix = 0, iy = 0, iz = 0, sx = 0, sy = 0, sz = 0;
-        float tmx = INFINITY, tmy = INFINITY, tmz = INFINITY, tdx = 0.f, tdy = 0.f, tdz = 0.f;
-        bool inside = !(fabsf(ax) >= d.half_x || fabsf(ay) >= d.half_y || fabsf(az) >= d.half_z);   // dspmap_point_voxel_index's test
-        if (inside) {
-            cast_axis(ax, bx, d.half_x, d.res, ix, sx, tmx, tdx);
-            cast_axis(ay, by, d.half_y, d.res, iy, sy, tmy, tdy);
-            cast_axis(az, bz, d.half_z, d.res, iz, sz, tmz, tdz);
-            inside = ix < d.nx && iy < d.ny && iz < d.nz;   // (all >= 0: p > -half)
-        }
-        status = DSPMAP_CAST_START_OUTSIDE;
-        if (inside) {
-            const bool timed = !(A.w < 0.f) && d.T > 0;
-            const float dt = __fsub_rn(B.w, A.w);
-            const size_t nw = (size_t)(d.nx + 63) >> 6, rows = (size_t)d.ny * d.nz;
-            int l_in = timed ? q_horizon(d, __fadd_rn(A.w, __fmul_rn(0.f, dt))) + 1 : 0;
-            size_t key = ~(size_t)0;
-            u64 word = 0;
-            float s_in = 0.f;
-            status = DSPMAP_CAST_INVALID;   // (never left standing: the loop below ends within nx + ny + nz steps)
-            const int max_steps = d.nx + d.ny + d.nz;
-            for (int it = 0; it <= max_steps; ++it) {
-                const bool mx = tmx <= tmy && tmx <= tmz;
-                const bool my = !mx && tmy <= tmz;
-                const float tm = mx ? tmx : (my ? tmy : tmz);
-                int l_out = 0;
-                if (timed) l_out = q_horizon(d, __fadd_rn(A.w, __fmul_rn(fminf(tm, 1.f), dt))) + 1;
-                const int l0 = min(l_in, l_out), l1 = max(l_in, l_out);
-                const size_t cell = ((size_t)iz * d.ny + iy) * nw + ((unsigned)ix >> 6);
-                int l = l0;
-                for (; l <= l1; ++l) {
-                    const size_t k = (size_t)l * rows * nw + cell;
-                    if (k != key) { word = a.bits[k]; key = k; }
-                    if ((word >> (ix & 63)) & 1ull) break;
-                }
-                const int here = (iz * d.ny + iy) * d.nx + ix;
-                if (l <= l1) { s = s_in; voxel = here; layer = l; status = DSPMAP_CAST_HIT; break; }
-                if (!(tm <= 1.f)) { s = 1.f; status = DSPMAP_CAST_FREE; break; }
-                s_in = tm;
-                l_in = l_out;   // t_in of the next cell is t_out of this one: the same expression of the same parameter (tm <= 1)
-                bool left;
-                if (mx) { ix += sx; tmx = __fadd_rn(tm, tdx); left = (unsigned)ix >= (unsigned)d.nx; }
-                else if (my) { iy += sy; tmy = __fadd_rn(tm, tdy); left = (unsigned)iy >= (unsigned)d.ny; }
-                else { iz += sz; tmz = __fadd_rn(tm, tdz); left = (unsigned)iz >= (unsigned)d.nz; }
-                if (left) { s = s_in; voxel = here; status = DSPMAP_CAST_LEFT_MAP; break; }
-            }
-        }
+        cast_walk(d, a.bits, ax, ay, az, A.w, bx, by, bz, B.w, s, voxel, layer, status);
     }
     out[i] = make_int4(__float_as_int(s), voxel, layer, status);
 }

@@ -205,6 +205,10 @@ struct dspmap {
     unsigned* kn_stamp = nullptr;
     long long kn_k0[3] = {0, 0, 0};
     bool kn_integrated = false;
+    // viewpoint scores (dspmap_score_views): the unrotated central direction of every pyramid, [np][3]; uploaded by the first call, freed
+    // with the device state.  vw_chunks: DSPMAP_P_VIEW_CHUNKS
+    float* vw_dirs0 = nullptr;
+    int vw_chunks = 0;
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;

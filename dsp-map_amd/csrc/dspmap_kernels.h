@@ -260,6 +260,26 @@ void launch_known_ages(const MapDims& d, hipStream_t stream, const KnownArgs& a,
 void launch_known_query(const MapDims& d, hipStream_t stream, const KnownArgs& a, int world, const float cur[3], int n, const float4* q, int* out);
 void launch_known_count(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, u64* sums);   // sums[2], zeroed by the caller
 void launch_known_mask(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, int L, u64* bits);
+// scores of candidate viewpoints (dspmap_view.hip; semantics in include/dspmap.h, dspmap_score_views).  As the known-space launchers: the
+// dimensions and the stream, no LaunchCtx
+struct ViewArgs {
+    float ox, oy, oz;    // as QueryArgs
+    int world;
+    const u64* bits;     // [L][nz][ny][W] the cast grid
+    KnownArgs kn;        // the synchronised known-space layer (max_range is not read: every view brings its own)
+    int max_age;         // a seen cell is unknown iff its age is -1 or > max_age
+    float cx, cy, cz;    // as QueryArgs: dspmap_voxel_center
+    const float* dirs0;  // [np][3] unrotated central direction of every pyramid
+    float reach;         // fl(res * (float)(nx + ny + nz)): no ray is longer
+};
+struct dspmap_view;
+struct dspmap_view_score;
+int view_chunks(const MapDims& d, int n, int n_cu, int forced);   // workgroups per view for a batch of n (forced > 0: that many, capped)
+// out [n] zeroed by the caller; dbg_words ([nz][ny][W], zeroed) / dbg_ml ([np]): the seen set and the farthest returns (n == 1), or nullptr
+void launch_view_score(const MapDims& d, const DevState& s, hipStream_t stream, const ViewArgs& a, int n, int chunks, const struct dspmap_view* views,
+                       struct dspmap_view_score* out, u64* dbg_words, float* dbg_ml);
+// out: planes_h [(np_h + 1) * 3], planes_v [(np_v + 1) * 3], dirs [np * 3] of attitude q, consecutively
+void launch_view_rays(const MapDims& d, const DevState& s, hipStream_t stream, const ViewArgs& a, const float q[4], float* out);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

@@ -319,6 +319,16 @@ public:
         return dspmap_query_known(h_, n, q, world ? DSPMAP_QUERY_WORLD : 0, ages);
     }
     int maskCastGridUnknown(int max_age) { return dspmap_mask_cast_grid(h_, max_age, 0); }
+    /* extension: scores of candidate viewpoints (dspmap_score_views in dspmap.h): for every view {position, attitude, max_range, t} the
+     * voxels a frame taken from there would see through the cast grid as it is (n_seen), those of them that are unknown now -- never
+     * seen, or seen more than max_age frames ago -- (n_unknown), and the rays that ended on an obstacle (n_returns).  viewRays hands out
+     * the rotated planes and ray directions of an attitude (any pointer may be NULL).  Return DSPMAP_OK or a negative error code. */
+    int scoreViews(int n, const dspmap_view* views, int max_age, dspmap_view_score* scores, bool world = false) {
+        return dspmap_score_views(h_, n, views, max_age, world ? DSPMAP_QUERY_WORLD : 0, scores);
+    }
+    int viewRays(const float quat_wxyz[4], float* planes_h, float* planes_v, float* dirs) {
+        return dspmap_view_rays(h_, quat_wxyz, planes_h, planes_v, dirs);
+    }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

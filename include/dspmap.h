@@ -208,6 +208,9 @@ enum dspmap_param {
                                        and extended by whoever puts the first particle into an empty tile -- instead of from the tile's own words in
                                        memory: an empty tile's workgroup leaves as fast as the next one can be started (264x264x80 filled by the depth
                                        stream: 87 120 tiles, ~12 k with particles); 0 = every workgroup loads its tile's flags (rounds 3-5).  Same result */
+    DSPMAP_P_VIEW_CHUNKS = 31,      /* dspmap_score_views*: workgroups per view.  0 (default) = the handle spreads a batch over the device: about four
+                                       workgroups per compute unit in all, at most 64 per view and never more than the map has rows for; 1 .. 64 = that
+                                       many (capped likewise).  The scores are integer counts and do not depend on it */
     DSPMAP_P_PAIR_CULL_SIGMAS = 13  /* mapUpdate evaluates a (particle, observation) pair only if their ranges differ by at most this many
                                        sigma_ob (default 9: the dropped terms are < 1e-19 and zero on the fixed-point Ck grid);
                                        a huge value evaluates every pair of the neighbourhood like the reference's loops */
@@ -662,6 +665,74 @@ int dspmap_query_known_device(dspmap_t* m, int n, const dspmap_query* q_dev, int
 int dspmap_mask_cast_grid(dspmap_t* m, int max_age, int flags /* must be 0 */);
 int dspmap_known_stats(dspmap_t* m, int max_age, long long out[2]);
 int dspmap_get_view(dspmap_t* m, float* planes_h_host, float* planes_v_host, float* maxlen_host);
+
+/* ---- scores of candidate viewpoints: the unknown space a frame taken from a pose would see (no counterpart in the reference).  An
+ * exploration or active-perception planner asks, for some hundred candidate poses per replan: "if the sensor stood here, looking this
+ * way, how many cells that are unknown now would the next frame stamp?"  Every piece of the answer is defined above: the frame's rotated
+ * pyramid planes, the pyramid of a point, the occlusion rule of the known-space layer, and the segment cast.  An extension beside the
+ * frame, like the sections above: the frame path, its launch chain and the captured graph do not know about it.
+ *
+ *  A view is {x, y, z, qw, qx, qy, qz, max_range, t}: position and DSPMAP_QUERY_WORLD as in dspmap_query_occupancy (with the flag
+ *  p = fl(q - current position) per axis); the quaternion is used as given (the rotation divides by its squared norm, as the frame's
+ *  does); max_range > 0, +inf allowed; t selects ONE layer of the cast grid -- layer 0 for t < 0 or a map without horizons, else layer
+ *  1 + k(t) with the k(t) of dspmap_query_occupancy.  Sight is instantaneous: nothing is space-time along a ray.
+ *
+ *  The score is computed in the grid of the last dspmap_build_cast_grid EXACTLY AS IT IS: an inflated grid gives thicker obstacles; a
+ *  grid masked with dspmap_mask_cast_grid stops the rays at unknown space, which gives the CONSERVATIVE gain (only what is certainly
+ *  visible); an unmasked grid lets them pass through unknown space as through free space, the OPTIMISTIC gain.  The ages are those of
+ *  the known-space layer, synchronised to the current position first like every known-space entry point.  Per view:
+ *  1. validity.  A non-finite x, y, z or quaternion component, a squared norm fl(fl(fl(qx qx + qy qy) + qz qz) + qw qw) of zero, a NaN
+ *     t, or a max_range that is NaN or <= 0 gives {0, 0, 0, DSPMAP_VIEW_INVALID}.  Otherwise, if dspmap_point_voxel_index calls p
+ *     outside, or trunc(u_a) >= n on some axis (cast step 2), {0, 0, 0, DSPMAP_VIEW_OUTSIDE}.  Otherwise, if the bit of the view's own
+ *     cell is set in the selected layer, {0, 0, 0, DSPMAP_VIEW_BLOCKED}.
+ *  2. planes.  planes_h, planes_v = the handle's unrotated normals rotated by the quaternion: the frame's own expression on the frame's
+ *     own tables.  A frame taken with that attitude has these planes bit for bit (dspmap_get_view).
+ *  3. one ray per pyramid b = h * np_v + v.  Its unrotated direction d0 is the pyramid's centre,
+ *         (1, tan alpha_h, tan beta_v) / |.|      alpha_h = (h - np_h / 2 + 0.5) step      beta_v = -(v - np_v / 2 + 0.5) step
+ *     with step = angle_resolution * pi / 180, computed once on the host in double and rounded to fp32; d = d0 rotated like a plane.
+ *     The ray is the cast (steps 2 - 4 of dspmap_cast_segments) of the segment a = p, b_a = fl(p_a + fl(d_a * l)), ta = tb =
+ *     min(t, FLT_MAX) -- which selects the layer of step 1 in every cell -- with l = fminf(max_range, fl(res * (float)(nx + ny + nz))).
+ *     A ray whose end point is not finite is no cast.  A HIT gives pyramid b the synthetic farthest return ml[b] = the distance from
+ *     p to the CENTRE c of the hit voxel (dspmap_voxel_center): r_a = fl(c_a - p_a), sqrtf(fl(fl(rx rx + ry ry) + rz rz)).  Anything
+ *     else gives ml[b] = -1: no return, seen through, as the known-space layer treats a pyramid without one.  n_returns = the hits.
+ *     One ray per pyramid is the frame's own resolution -- it keeps one farthest return per pyramid --, so an obstacle narrower than a
+ *     pyramid, far from the sensor, can be looked past.
+ *  4. every voxel of the map, with c its centre and r_a = fl(c_a - p_a): b = the pyramid of r in the planes of step 2 (outside the wedge:
+ *     not seen); dist as above; occluded iff ml[b] > 0 and dist > fl(ml[b] + DSPMAP_P_OCCLUSION_MARGIN); seen iff in the wedge, not
+ *     occluded and dist <= max_range.  n_seen = the seen voxels; n_unknown = those of them whose age is -1 or > max_age
+ *     (dspmap_mask_cast_grid's notion of unknown; ages voxel by voxel as dspmap_get_known orders them); status = DSPMAP_VIEW_OK.
+ *  Everything is an integer count of exactly defined predicates: the scores are defined bit for bit and do not depend on the launch.
+ *
+ *  - dspmap_score_views: host arrays, synchronous.  dspmap_score_views_device: device arrays, enqueued on the handle's stream behind the
+ *    build and the frame, no synchronisation.
+ *  - dspmap_view_rays: what the device makes of an attitude -- planes_h [np_h + 1][3], planes_v [np_v + 1][3] and the ray directions
+ *    [dspmap_pyramid_num][3]; any pointer may be NULL; synchronous; needs no grid.
+ *  - dspmap_debug_view_cells (test hook): the seen set of ONE view as a bit grid [nz][ny][W] in the cast grid's word layout (bit = seen;
+ *    all zero for a view that is not OK) and its ml [dspmap_pyramid_num] (may be NULL; all -1 for such a view); synchronous.
+ *  - arguments, checked before the device is touched, DSPMAP_E_ARG with a text: a NULL handle, n < 0, a NULL array with n > 0,
+ *    max_age < 0, flags other than DSPMAP_QUERY_WORLD, a NULL quaternion or view.  Then, in dspmap_grow_boxes' order: a sharded handle
+ *    (slab) is DSPMAP_E_STATE; a stale or never-built grid is DSPMAP_E_STATE with a text naming dspmap_build_cast_grid; a layer without
+ *    an integration since its last reset is DSPMAP_E_STATE with a text naming dspmap_known_integrate (dspmap_mask_cast_grid's rule); a
+ *    valid call without a usable device is DSPMAP_E_DEVICE (dspmap_view_rays; for the others there is no grid without one).  n == 0
+ *    returns DSPMAP_OK and queues nothing.
+ *  - read-only in every sense listed for dspmap_grow_boxes, and towards the known-space layer: nothing goes stale, the captured frame
+ *    and its parameter ring are untouched.  The direction table (12 bytes per pyramid) is allocated by the first call and freed with
+ *    the device state; a handle that never calls allocates nothing. */
+typedef struct dspmap_view {
+    float x, y, z;
+    float qw, qx, qy, qz;
+    float max_range;
+    float t;
+} dspmap_view;
+typedef struct dspmap_view_score {
+    int n_seen, n_unknown, n_returns;
+    int status;   /* DSPMAP_VIEW_* */
+} dspmap_view_score;
+enum { DSPMAP_VIEW_OK = 0, DSPMAP_VIEW_BLOCKED = 1, DSPMAP_VIEW_OUTSIDE = 3, DSPMAP_VIEW_INVALID = 4 };
+int dspmap_score_views(dspmap_t* m, int n, const dspmap_view* views_host, int max_age, int flags, dspmap_view_score* out_host);
+int dspmap_score_views_device(dspmap_t* m, int n, const dspmap_view* views_dev, int max_age, int flags, dspmap_view_score* out_dev);
+int dspmap_view_rays(dspmap_t* m, const float quat_wxyz[4], float* planes_h_host, float* planes_v_host, float* dirs_host);
+int dspmap_debug_view_cells(dspmap_t* m, const dspmap_view* view_host, int flags, unsigned long long* words_out_host, float* ml_out_host);
 
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
