@@ -20,7 +20,7 @@ OK, REJECTED = 1, 0
 P_POSITION_STDDEV, P_VELOCITY_STDDEV, P_OBSERVATION_STDDEV, P_NEWBORN_WEIGHT, P_NEWBORN_NUMBER, \
     P_VOXEL_FILTER_RES, P_KAPPA, P_DETECTION, P_VELOCITY_ESTIMATOR, P_REGENERATE_TABLES, P_USE_GRAPH, P_OCCLUSION_MARGIN, \
     P_PAIR_CULL_SIGMAS, P_UPDATE_TIME, P_UPDATE_COUNTER, P_PLACE_SPLIT_TILES, P_FAST_DIVISION, P_SPARSE_SWEEP, P_ROLLOUT_INLINE, \
-    P_RESAMPLE_WG_TILES, P_SWEEP_ALTERNATE, P_STATIC_TILE_SKIP, P_HOST_CLOUD_DIRECT, _P_REMOVED_24, P_ESTIMATOR_QUEUE, P_FRAME_BRANCHES, P_TILING, P_SIDE_PLACEMENT, P_RESAMPLE_SPLIT, P_TILE_BITMAPS, P_VIEW_CHUNKS = range(1, 32)
+    P_RESAMPLE_WG_TILES, P_SWEEP_ALTERNATE, P_STATIC_TILE_SKIP, P_HOST_CLOUD_DIRECT, _P_REMOVED_24, P_ESTIMATOR_QUEUE, P_FRAME_BRANCHES, P_TILING, P_SIDE_PLACEMENT, P_RESAMPLE_SPLIT, P_TILE_BITMAPS, P_VIEW_CHUNKS, P_FRONTIER_MERGE = range(1, 33)
 
 
 class Config(C.Structure):
@@ -105,6 +105,9 @@ FORECAST_LERP = 2            # DSPMAP_FORECAST_LERP
 VIEW_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("qw", "f4"), ("qx", "f4"), ("qy", "f4"), ("qz", "f4"), ("max_range", "f4"), ("t", "f4")])
 VIEW_SCORE_DTYPE = np.dtype([("n_seen", "i4"), ("n_unknown", "i4"), ("n_returns", "i4"), ("status", "i4")])
 VIEW_OK, VIEW_BLOCKED, VIEW_OUTSIDE, VIEW_INVALID = 0, 1, 3, 4
+# dspmap_frontier_block (dspmap_build_frontiers)
+FRONTIER_BLOCK_DTYPE = np.dtype([("block", "i4"), ("count", "i4"), ("sum_x", "i4"), ("sum_y", "i4"), ("sum_z", "i4"), ("unknown_faces", "i4")])
+FRONTIER_MAX_BLOCK = 32
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -178,6 +181,16 @@ SIGNATURES = {
     "dspmap_score_views_device": (_i, [_P, _i, _P, _i, _i, _P]),
     "dspmap_view_rays": (_i, [_P, _P, _P, _P, _P]),
     "dspmap_debug_view_cells": (_i, [_P, _P, _i, _P, _P]),
+    "dspmap_build_frontiers": (_i, [_P, _f, _i, _i, _i, _i]),
+    "dspmap_frontier_counts": (_i, [_P, _P]),
+    "dspmap_get_frontier_grid": (_i, [_P, _P]),
+    "dspmap_get_frontier_cells": (_i, [_P, _i, _P, _P]),
+    "dspmap_get_frontier_blocks": (_i, [_P, _i, _P, _P]),
+    "dspmap_frontier_grid_device": (_P, [_P]),
+    "dspmap_frontier_cells_device": (_P, [_P]),
+    "dspmap_frontier_blocks_device": (_P, [_P]),
+    "dspmap_frontier_counts_device": (_P, [_P]),
+    "dspmap_debug_set_known": (_i, [_P, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -302,6 +315,13 @@ def make_config(nx=66, ny=66, nz=40, res=0.15, ppv=9, angle=3, half_fov_h=42, ha
 
 class DSPMapError(RuntimeError):
     pass
+
+
+class _DeviceSpan:
+    """device memory the library owns, for torch.as_tensor: the CUDA array interface, which torch wraps without a copy"""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
 
 
 def _ptr(a):
@@ -983,6 +1003,86 @@ class DSPMap:
         ml = np.zeros(self.NP, np.float32)
         self._chk(self.L.dspmap_debug_view_cells(self.h, _ptr(q), QUERY_WORLD if world else 0, _ptr(words), _ptr(ml)))
         return words, ml
+
+    # -- frontier cells and blocks (extension; semantics in include/dspmap.h next to dspmap_build_frontiers)
+    def build_frontiers(self, t=-1.0, max_age=0, min_unknown=1, block=4):
+        """enqueue the frontier of the layer t selects of the cast grid as it is, on the handle's stream: the cells that are known (0 <=
+        age <= max_age) with a clear bit and at least min_unknown (1 .. 6) of whose face neighbours inside the map are unknown, as a bit
+        grid, as an ascending list of voxel indices and summed over blocks of block^3 voxels (1 .. 32).  Read-only towards the map, the
+        grid and the layer; the result is a snapshot of all three."""
+        self._chk(self.L.dspmap_build_frontiers(self.h, float(t), int(max_age), int(min_unknown), int(block), 0))
+
+    def frontier_counts(self):
+        """(n_cells, n_blocks, n_free) of the last build (synchronous)"""
+        out = (C.c_longlong * 3)()
+        self._chk(self.L.dspmap_frontier_counts(self.h, C.cast(out, C.c_void_p)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def frontier_grid(self):
+        """the frontier bits as numpy uint64 [nz, ny, W] in the cast grid's word layout (synchronous host copy)"""
+        out = np.zeros((self.cfg.nz, self.cfg.ny, (self.cfg.nx + 63) // 64), np.uint64)
+        self._chk(self.L.dspmap_get_frontier_grid(self.h, _ptr(out)))
+        return out
+
+    def _frontier_device(self, device, which, ptr_fn, cols):
+        """the first n entries of a list of the last build as an int32 tensor over the handle's own buffer (no copy); n is read from
+        the device, which synchronises the handle's stream; torch's current stream is ordered behind it"""
+        import torch
+        n = self.frontier_counts()[which]   # (raises on a stale snapshot)
+        ptr = ptr_fn(self.h)
+        dev = torch.device(device)
+        _, after = self._handle_stream_order(dev)
+        after()
+        shape = (n, cols) if cols > 1 else (n,)
+        if n == 0:
+            return torch.empty(shape, dtype=torch.int32, device=dev)
+        return torch.as_tensor(_DeviceSpan(ptr, shape, "<i4"), device=dev)
+
+    def frontier_cells(self, device=None):
+        """the voxel indices of the frontier cells in ascending order: numpy int32 [n] (synchronous host copy); with device= (e.g. "cuda")
+        an int32 tensor [n] over the handle's own device buffer, without a copy, ordered with torch's current stream like score_views.
+        The tensor is valid until the next build_frontiers or close()."""
+        if device is not None:
+            return self._frontier_device(device, 0, self.L.dspmap_frontier_cells_device, 1)
+        n = C.c_int(0)
+        self._chk(self.L.dspmap_get_frontier_cells(self.h, 0, None, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            self._chk(self.L.dspmap_get_frontier_cells(self.h, n.value, _ptr(out), C.byref(n)))
+        return out
+
+    def frontier_blocks(self, device=None):
+        """the records of the non-empty blocks in ascending block index: structured numpy (FRONTIER_BLOCK_DTYPE) [k] (synchronous host
+        copy); with device= an int32 tensor [k, 6] {block, count, sum_x, sum_y, sum_z, unknown_faces} over the handle's own device
+        buffer, without a copy, as frontier_cells"""
+        if device is not None:
+            return self._frontier_device(device, 1, self.L.dspmap_frontier_blocks_device, 6)
+        n = C.c_int(0)
+        self._chk(self.L.dspmap_get_frontier_blocks(self.h, 0, None, C.byref(n)))
+        out = np.zeros(n.value, FRONTIER_BLOCK_DTYPE)
+        if n.value:
+            self._chk(self.L.dspmap_get_frontier_blocks(self.h, n.value, _ptr(out), C.byref(n)))
+        return out
+
+    def frontier_block_centers(self, min_count=1):
+        """float32 [k, 3]: the centroid of the frontier cells of every block with at least min_count of them, in the map frame:
+        ((sum / count) + 0.5) * res - half per axis (a mean voxel index is the centre of that voxel)"""
+        b = self.frontier_blocks()
+        b = b[b["count"] >= int(min_count)]
+        cfg = self.cfg
+        res = float(np.float32(cfg.voxel_resolution))
+        half = np.array([cfg.nx, cfg.ny, cfg.nz], np.float64) * res / 2.0
+        mean = np.stack([b["sum_x"], b["sum_y"], b["sum_z"]], 1) / np.maximum(b["count"], 1)[:, None]
+        return ((mean + 0.5) * res - half).astype(np.float32)
+
+    def set_known(self, ages):
+        """test hook: replace the ages of the known-space layer (int32 [nz, ny, nx], what known_age() returns; -1 = never, else 0 ..
+        update counter - 1); the layer counts as integrated"""
+        a = np.ascontiguousarray(ages, np.int32)
+        shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
+        if a.shape != shape:
+            raise ValueError("set_known: ages of shape %s" % (shape,))
+        self._chk(self.L.dspmap_debug_set_known(self.h, _ptr(a)))
 
     def set_cast_grid(self, words):
         """test hook: replace all layers of the valid cast grid with words (uint64 [L, nz, ny, W], what cast_grid() returns)"""

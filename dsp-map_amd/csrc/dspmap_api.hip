@@ -237,6 +237,11 @@ static void free_dev(dspmap* m) {
     m->kn_stamp = nullptr; m->kn_integrated = false;
     if (m->vw_dirs0) chk(hipFree(m->vw_dirs0), "hipFree");
     m->vw_dirs0 = nullptr;
+    for (void* q : {(void*)m->fr_grid, (void*)m->fr_cells, (void*)m->fr_counts, (void*)m->fr_item_free, (void*)m->fr_dense, (void*)m->fr_blocks,
+                    (void*)m->fr_tiles})
+        if (q) chk(hipFree(q), "hipFree");
+    m->fr_grid = nullptr; m->fr_cells = nullptr; m->fr_counts = nullptr; m->fr_item_free = nullptr; m->fr_dense = nullptr; m->fr_blocks = nullptr;
+    m->fr_tiles = nullptr; m->fr_nb_cap = 0; m->fr_valid = false;
     if (m->pp_box) chk(hipFree(m->pp_box), "hipFree");
     if (m->pp_acc) chk(hipFree(m->pp_acc), "hipFree");
     if (m->pp_blk) chk(hipFree(m->pp_blk), "hipFree");
@@ -630,6 +635,7 @@ extern "C" int dspmap_set_param(dspmap_t* m, int key, double v) {
         case DSPMAP_P_RESAMPLE_SPLIT: m->resample_split = v != 0 ? 1 : 0; m->graph_epoch++; break;
         case DSPMAP_P_TILE_BITMAPS: m->tile_bitmaps = v != 0; m->graph_epoch++; break;
         case DSPMAP_P_VIEW_CHUNKS: m->vw_chunks = v >= 1.f ? (int)fminf(v, 64.f) : 0; break;   // (launch shape of dspmap_score_views only)
+        case DSPMAP_P_FRONTIER_MERGE: m->fr_merge = v != 0; break;   // (how dspmap_build_frontiers adds up its block sums only)
         case DSPMAP_P_SIDE_PLACEMENT: {
             const int iv = v < 0 ? 16 + 3 : (int)v;
             m->side_fork = (iv >> 4) > 2 ? 0 : (iv >> 4);
@@ -695,6 +701,7 @@ extern "C" double dspmap_get_param(const dspmap_t* m, int key) {
         case DSPMAP_P_RESAMPLE_SPLIT: return m->resample_split;
         case DSPMAP_P_TILE_BITMAPS: return m->tile_bitmaps ? 1 : 0;
         case DSPMAP_P_VIEW_CHUNKS: return (float)m->vw_chunks;
+        case DSPMAP_P_FRONTIER_MERGE: return m->fr_merge ? 1.f : 0.f;
         case DSPMAP_P_TILING: return m->d.tiling;
         case DSPMAP_P_USE_GRAPH: return m->use_graph ? 1 : (m->direct_ring ? 2 : 0);
         default: return 0;
@@ -1041,6 +1048,7 @@ extern "C" int dspmap_build_cast_grid(dspmap_t* m, float thr, int inflate_voxels
     BENIGN(m);
     m->cg_valid = false;
     m->rf_valid = false;   // (arrival fields are grown in the grid this build replaces)
+    m->fr_valid = false;   // (... and frontiers found in it)
     if (!m->cg_bits) {
         HIPCHK(m, hipMalloc(&m->cg_bits, sizeof(u64) * words));
         HIPCHK(m, hipMalloc(&m->cg_tmp, sizeof(u64) * words));
@@ -1342,6 +1350,7 @@ extern "C" int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long*
     const int rc = cast_grid_ready(m, "dspmap_debug_set_cast_grid");
     if (rc != DSPMAP_OK) return rc;
     m->rf_valid = false;
+    m->fr_valid = false;
     HIPCHK(m, hipMemcpyAsync(m->cg_bits, words, sizeof(u64) * total, hipMemcpyHostToDevice, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));   // (the caller's array is free again)
     return DSPMAP_OK;
@@ -1479,6 +1488,7 @@ static int known_slot(long long k, int n) { const long long r = k % n; return (i
 // everything forgotten (dspmap_known_reset, dspmap_clear_state, dspmap_load_checkpoint); a handle without a layer has nothing to forget
 static int known_forget(dspmap* m) {
     m->kn_integrated = false;
+    m->fr_valid = false;   // (frontiers are a snapshot of the layer)
     if (m->kn_stamp) HIPCHK(m, hipMemsetAsync(m->kn_stamp, 0, sizeof(unsigned) * (size_t)m->d.v_glob, m->stream));
     return DSPMAP_OK;
 }
@@ -1530,6 +1540,7 @@ extern "C" int dspmap_known_integrate(dspmap_t* m, float max_range, int flags) {
     BENIGN(m);
     if (m->update_counter < 1)
         return dspmap_fail(m, DSPMAP_E_STATE, "known space: no frame has been accepted yet, there is no view to integrate (dspmap_update)");
+    m->fr_valid = false;   // (frontiers are a snapshot of the layer)
     const bool fresh = !m->kn_stamp;
     if (fresh) {
         HIPCHK(m, hipMalloc(&m->kn_stamp, sizeof(unsigned) * (size_t)m->d.v_glob));
@@ -1629,6 +1640,7 @@ extern "C" int dspmap_mask_cast_grid(dspmap_t* m, int max_age, int flags) {
     KnownArgs a;
     if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
     m->rf_valid = false;   // (arrival fields were grown in the grid as it was)
+    m->fr_valid = false;   // (... and frontiers found in it)
     launch_known_mask(m->d, m->stream, a, max_age, m->d.T + 1, m->cg_bits);
     HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;
@@ -1794,6 +1806,162 @@ extern "C" int dspmap_debug_view_cells(dspmap_t* m, const dspmap_view* view, int
     HIPCHK(m, hipMemcpyAsync(words_out, dw, sizeof(u64) * lw, hipMemcpyDeviceToHost, m->stream));
     if (ml_out) HIPCHK(m, hipMemcpyAsync(ml_out, dm, sizeof(float) * (size_t)m->d.np, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+
+// --------------------------------------------------- frontier cells and blocks (dspmap_frontier.hip; semantics in include/dspmap.h)
+// the layer t selects: the host twin of q_horizon (dspmap_device.h) + 1.  (t is not NaN here.)
+static int frontier_layer_host(const MapDims& d, float t) {
+    if (!(t >= 0.f) || d.T == 0) return 0;
+    int k = d.T - 1;
+    for (int j = d.T - 1; j >= 0; --j)
+        if (d.pred_t[j] >= t) k = j;
+    return k + 1;
+}
+// the buffers of a build with nb blocks: what does not depend on the block size once, the rest again when nb outgrows it
+static int frontier_alloc(dspmap* m, size_t nb) {
+    const MapDims& d = m->d;
+    const size_t lw = cast_layer_words(d);
+    if (!m->fr_grid) HIPCHK(m, hipMalloc(&m->fr_grid, sizeof(u64) * lw));
+    if (!m->fr_cells) HIPCHK(m, hipMalloc(&m->fr_cells, sizeof(int) * (size_t)d.v_glob));
+    if (!m->fr_counts) HIPCHK(m, hipMalloc(&m->fr_counts, 3 * sizeof(long long)));
+    if (!m->fr_item_free) HIPCHK(m, hipMalloc(&m->fr_item_free, sizeof(int) * lw));
+    if (nb > m->fr_nb_cap) {
+        if (m->fr_nb_cap) HIPCHK(m, hipStreamSynchronize(m->stream));   // (an earlier build may still write the smaller buffers)
+        for (void* q : {(void*)m->fr_dense, (void*)m->fr_blocks, (void*)m->fr_tiles}) if (q) (void)hipFree(q);
+        m->fr_dense = nullptr; m->fr_blocks = nullptr; m->fr_tiles = nullptr; m->fr_nb_cap = 0;
+        HIPCHK(m, hipMalloc(&m->fr_dense, sizeof(dspmap_frontier_block) * nb));
+        HIPCHK(m, hipMalloc(&m->fr_blocks, sizeof(dspmap_frontier_block) * nb));
+        HIPCHK(m, hipMalloc(&m->fr_tiles, sizeof(int) * (2 * (size_t)frontier_tiles((long long)lw) + (size_t)frontier_tiles((long long)nb))));
+        m->fr_nb_cap = nb;
+    }
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_build_frontiers(dspmap_t* m, float t, int max_age, int min_unknown, int block, int flags) {
+    const char* what = "dspmap_build_frontiers";
+    if (!m) return DSPMAP_E_ARG;
+    if (t != t) return dspmap_fail(m, DSPMAP_E_ARG, "%s: t is NaN", what);
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative max_age %d", what, max_age);
+    if (min_unknown < 1 || min_unknown > 6) return dspmap_fail(m, DSPMAP_E_ARG, "%s: min_unknown %d outside [1, 6]", what, min_unknown);
+    if (block < 1 || block > DSPMAP_FRONTIER_MAX_BLOCK)
+        return dspmap_fail(m, DSPMAP_E_ARG, "%s: block %d outside [1, %d]", what, block, DSPMAP_FRONTIER_MAX_BLOCK);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: a slab handle holds part of the map; a frontier crosses slabs", what);
+    int rc = cast_grid_ready(m, what);
+    if (rc != DSPMAP_OK) return rc;
+    if (!m->kn_stamp || !m->kn_integrated)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no frame has been integrated into the known-space layer (dspmap_known_integrate)", what);
+    const MapDims& d = m->d;
+    m->fr_valid = false;
+    FrontierArgs a;
+    if ((rc = known_sync(m, &a.kn)) != DSPMAP_OK) return rc;
+    a.nbx = (d.nx + block - 1) / block; a.nby = (d.ny + block - 1) / block;
+    const size_t nb = (size_t)a.nbx * a.nby * (size_t)((d.nz + block - 1) / block);   // (<= V < 2^31)
+    a.nb = (int)nb;
+    if ((rc = frontier_alloc(m, nb)) != DSPMAP_OK) return rc;
+    const size_t lw = cast_layer_words(d);
+    a.bits = m->cg_bits + lw * (size_t)frontier_layer_host(d, t);
+    a.max_age = max_age; a.min_unknown = min_unknown; a.block = block;
+    a.grid = m->fr_grid; a.cells = m->fr_cells; a.dense = m->fr_dense; a.blocks = m->fr_blocks;
+    a.item_free = m->fr_item_free;
+    a.tile_sum = m->fr_tiles;
+    a.tile_free = m->fr_tiles + frontier_tiles((long long)lw) + frontier_tiles((long long)nb);
+    a.counts = m->fr_counts;
+    a.merge = m->fr_merge ? 1 : 0;
+    HIPCHK(m, hipMemsetAsync(m->fr_dense, 0, sizeof(dspmap_frontier_block) * nb, m->stream));
+    launch_frontiers(d, m->stream, a);
+    HIPCHK(m, hipGetLastError());
+    m->fr_valid = true;
+    return DSPMAP_OK;
+}
+static int frontier_ready(dspmap* m, const char* what) {
+    if (!m->fr_valid)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no frontiers, or the grid, the known-space layer or the position has changed since they were built (dspmap_build_frontiers)", what);
+    if (m->device >= 0) (void)hipSetDevice(m->device);
+    return DSPMAP_OK;
+}
+static int frontier_counts_host(dspmap* m, long long out[3]) {
+    HIPCHK(m, hipMemcpyAsync(out, m->fr_counts, 3 * sizeof(long long), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_frontier_counts(dspmap_t* m, long long out[3]) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "dspmap_frontier_counts: NULL output array");
+    const int rc = frontier_ready(m, "dspmap_frontier_counts");
+    if (rc != DSPMAP_OK) return rc;
+    return frontier_counts_host(m, out);
+}
+extern "C" int dspmap_get_frontier_grid(dspmap_t* m, unsigned long long* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "dspmap_get_frontier_grid: NULL output array");
+    const int rc = frontier_ready(m, "dspmap_get_frontier_grid");
+    if (rc != DSPMAP_OK) return rc;
+    HIPCHK(m, hipMemcpyAsync(out, m->fr_grid, sizeof(u64) * cast_layer_words(m->d), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+// the first min(cap, n) entries of list `which` (0: cells, 1: blocks) of `bytes` each, and n
+static int frontier_list(dspmap* m, const char* what, int which, const void* dev, size_t bytes, int cap, void* out, int* n_out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (cap < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative capacity %d", what, cap);
+    if (!n_out || (cap > 0 && !out)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL output", what);
+    int rc = frontier_ready(m, what);
+    if (rc != DSPMAP_OK) return rc;
+    long long c[3];
+    if ((rc = frontier_counts_host(m, c)) != DSPMAP_OK) return rc;
+    const long long n = c[which], take = n < cap ? n : cap;
+    if (take > 0) {
+        HIPCHK(m, hipMemcpyAsync(out, dev, bytes * (size_t)take, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+    }
+    *n_out = (int)n;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_frontier_cells(dspmap_t* m, int cap, int* out, int* n_out) {
+    return frontier_list(m, "dspmap_get_frontier_cells", 0, m ? m->fr_cells : nullptr, sizeof(int), cap, out, n_out);
+}
+extern "C" int dspmap_get_frontier_blocks(dspmap_t* m, int cap, dspmap_frontier_block* out, int* n_out) {
+    return frontier_list(m, "dspmap_get_frontier_blocks", 1, m ? m->fr_blocks : nullptr, sizeof(dspmap_frontier_block), cap, out, n_out);
+}
+extern "C" const unsigned long long* dspmap_frontier_grid_device(dspmap_t* m) { return (m && m->fr_valid) ? m->fr_grid : nullptr; }
+extern "C" const int* dspmap_frontier_cells_device(dspmap_t* m) { return (m && m->fr_valid) ? m->fr_cells : nullptr; }
+extern "C" const dspmap_frontier_block* dspmap_frontier_blocks_device(dspmap_t* m) { return (m && m->fr_valid) ? m->fr_blocks : nullptr; }
+extern "C" const long long* dspmap_frontier_counts_device(dspmap_t* m) { return (m && m->fr_valid) ? m->fr_counts : nullptr; }
+// test hook: the ages of the known-space layer replaced cell by cell, written through the toroidal slot mapping
+extern "C" int dspmap_debug_set_known(dspmap_t* m, const int* age) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!age) return dspmap_fail(m, DSPMAP_E_ARG, "set known: NULL age array");
+    int rc = known_whole_map(m, "dspmap_debug_set_known");
+    if (rc != DSPMAP_OK) return rc;
+    if (m->update_counter < 1)
+        return dspmap_fail(m, DSPMAP_E_STATE, "set known: no frame has been accepted yet, there is no counter to age against (dspmap_update)");
+    const MapDims& d = m->d;
+    const size_t V = (size_t)d.v_glob;
+    for (size_t i = 0; i < V; ++i)
+        if (age[i] < -1 || age[i] > m->update_counter - 1)
+            return dspmap_fail(m, DSPMAP_E_ARG, "set known: age[%zu] = %d outside [-1, %d]", i, age[i], m->update_counter - 1);
+    READY(m);
+    BENIGN(m);
+    m->fr_valid = false;   // (frontiers are a snapshot of the layer)
+    if (!m->kn_stamp) {
+        HIPCHK(m, hipMalloc(&m->kn_stamp, sizeof(unsigned) * V));
+        HIPCHK(m, hipMemsetAsync(m->kn_stamp, 0, sizeof(unsigned) * V, m->stream));
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    std::vector<unsigned> stamp(V);
+    auto slot = [](int i, int b, int n) { const int s = i + b; return s >= n ? s - n : s; };   // kn_slot
+    size_t g = 0;
+    for (int z = 0; z < d.nz; ++z)
+        for (int y = 0; y < d.ny; ++y) {
+            unsigned* row = &stamp[((size_t)slot(z, a.bz, d.nz) * d.ny + slot(y, a.by, d.ny)) * d.nx];
+            for (int x = 0; x < d.nx; ++x, ++g) row[slot(x, a.bx, d.nx)] = age[g] < 0 ? 0u : a.now - (unsigned)age[g];
+        }
+    HIPCHK(m, hipMemcpyAsync(m->kn_stamp, stamp.data(), sizeof(unsigned) * V, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));   // (the local array is free again)
+    m->kn_integrated = true;
     return DSPMAP_OK;
 }
 

@@ -209,6 +209,16 @@ struct dspmap {
     // with the device state.  vw_chunks: DSPMAP_P_VIEW_CHUNKS
     float* vw_dirs0 = nullptr;
     int vw_chunks = 0;
+    // frontiers (dspmap_build_frontiers): the bit grid [nz][ny][W], the cell list [V], the counts {n_cells, n_blocks, n_free} and the
+    // per-word free counts, allocated by the first build; the blocks' accumulators and records [fr_nb_cap] each and the compaction's tile
+    // scratch, allocated by the first build and again when a smaller block needs more; all freed with the device state.  fr_valid: a
+    // snapshot of the cast grid AND of the known-space layer -- cleared with cg_valid (dspmap_snapshots_stale), by every call that changes
+    // the grid or the layer, and by dspmap_set_current_position
+    u64* fr_grid = nullptr; int* fr_cells = nullptr; long long* fr_counts = nullptr; int* fr_item_free = nullptr;
+    dspmap_frontier_block* fr_dense = nullptr; dspmap_frontier_block* fr_blocks = nullptr; int* fr_tiles = nullptr;
+    size_t fr_nb_cap = 0;
+    bool fr_valid = false;
+    bool fr_merge = true;            // DSPMAP_P_FRONTIER_MERGE
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;
@@ -235,9 +245,9 @@ struct dspmap {
     float event_overhead_ms = 0.f;   // calibrated by dspmap_set_profiling(1): what an event bracket adds to the one kernel inside it
 };
 
-// everything that computes a frame or replaces state calls this: the distance field, the cast grid, the arrival fields grown in it and the
-// forecast are snapshots of the map before it
-inline void dspmap_snapshots_stale(dspmap* m) { m->df_valid = false; m->cg_valid = false; m->rf_valid = false; m->fc_valid = false; }
+// everything that computes a frame or replaces state calls this: the distance field, the cast grid, the arrival fields grown in it, the
+// frontiers found in it and the forecast are snapshots of the map before it
+inline void dspmap_snapshots_stale(dspmap* m) { m->df_valid = false; m->cg_valid = false; m->rf_valid = false; m->fc_valid = false; m->fr_valid = false; }
 int dspmap_fail(dspmap* m, int code, const char* fmt, ...);
 void dspmap_prof_mark(dspmap* m, int i);
 void dspmap_prof_collect(dspmap* m);

@@ -280,6 +280,27 @@ void launch_view_score(const MapDims& d, const DevState& s, hipStream_t stream, 
                        struct dspmap_view_score* out, u64* dbg_words, float* dbg_ml);
 // out: planes_h [(np_h + 1) * 3], planes_v [(np_v + 1) * 3], dirs [np * 3] of attitude q, consecutively
 void launch_view_rays(const MapDims& d, const DevState& s, hipStream_t stream, const ViewArgs& a, const float q[4], float* out);
+// frontier cells and blocks (dspmap_frontier.hip; semantics in include/dspmap.h, dspmap_build_frontiers).  As the known-space launchers: the
+// dimensions and the stream, no LaunchCtx
+struct dspmap_frontier_block;
+#define FR_TILE 256   // items (grid words / blocks) per tile of the ordered compaction: one workgroup, one item per thread
+inline int frontier_tiles(long long n) { return (int)((n + FR_TILE - 1) / FR_TILE); }
+struct FrontierArgs {
+    KnownArgs kn;        // the synchronised known-space layer
+    const u64* bits;     // [nz][ny][W] the SELECTED layer of the cast grid
+    int max_age, min_unknown, block;
+    int nbx, nby, nb;    // blocks along x, along y, and in all
+    u64* grid;           // out [nz][ny][W] frontier bits
+    int* cells;          // out [n_cells <= V] ascending voxel indices
+    struct dspmap_frontier_block* dense;    // [nb] the blocks' accumulators, zeroed by the caller (.block is not used)
+    struct dspmap_frontier_block* blocks;   // out [n_blocks <= nb] the non-empty ones, ascending
+    int* item_free;      // scratch [nz * ny * W] free cells per grid word
+    int* tile_sum;       // scratch [tiles of the words + tiles of the blocks] per-tile sums, then exclusive bases
+    int* tile_free;      // scratch [tiles of the words]
+    long long* counts;   // out {n_cells, n_blocks, n_free}
+    int merge;           // DSPMAP_P_FRONTIER_MERGE: block sums per (wave, block) instead of per cell
+};
+void launch_frontiers(const MapDims& d, hipStream_t stream, const FrontierArgs& a);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

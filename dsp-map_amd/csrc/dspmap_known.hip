@@ -20,16 +20,10 @@
 // Nothing of the map is written.
 #include "dspmap_device.h"
 #include "dspmap_internal.h"
+#include "dspmap_known_slots.h"   // kn_slot, kn_cell, kn_age
 
 #define KN_TPB 256
 #define KN_WAVES (KN_TPB / 64)
-
-// the slot of map voxel i of an axis whose voxel 0 lives in slot b (0 <= b < n, 0 <= i < n)
-__device__ __forceinline__ int kn_slot(int i, int b, int n) { const int s = i + b; return s >= n ? s - n : s; }
-__device__ __forceinline__ size_t kn_cell(const MapDims& d, const KnownArgs& a, int x, int y, int z) {
-    return ((size_t)kn_slot(z, a.bz, d.nz) * d.ny + kn_slot(y, a.by, d.ny)) * d.nx + kn_slot(x, a.bx, d.nx);
-}
-__device__ __forceinline__ int kn_age(unsigned stamp, unsigned now) { return stamp ? (int)(now - stamp) : -1; }
 
 __global__ void __launch_bounds__(KN_TPB) k_known_integrate(MapDims d, KnownArgs a, const float* __restrict__ planes_h,
                                                              const float* __restrict__ planes_v, const float* __restrict__ maxlen, int n_items) {

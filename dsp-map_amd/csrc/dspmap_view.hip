@@ -20,15 +20,14 @@
 // Nothing of the map, the grid or the layer is written.
 #include "dspmap_cast_walk.h"
 #include "dspmap_internal.h"
+#include "dspmap_known_slots.h"   // kn_cell, kn_age
 
 #define VW_TPB 256
 #define VW_WAVES (VW_TPB / 64)
 
-// (dspmap_known.hip's slot arithmetic: the age of map voxel (x, y, z))
-__device__ __forceinline__ int vw_slot(int i, int b, int n) { const int s = i + b; return s >= n ? s - n : s; }
+// the age of map voxel (x, y, z)
 __device__ __forceinline__ int vw_age(const MapDims& d, const KnownArgs& a, int x, int y, int z) {
-    const unsigned stamp = a.stamp[((size_t)vw_slot(z, a.bz, d.nz) * d.ny + vw_slot(y, a.by, d.ny)) * d.nx + vw_slot(x, a.bx, d.nx)];
-    return stamp ? (int)(a.now - stamp) : -1;
+    return kn_age(a.stamp[kn_cell(d, a, x, y, z)], a.now);
 }
 
 // the planes of attitude q into ph [(np_h + 1) * 3], pv [(np_v + 1) * 3]: k_reset's expression on k_reset's tables

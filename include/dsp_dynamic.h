@@ -329,6 +329,15 @@ public:
     int viewRays(const float quat_wxyz[4], float* planes_h, float* planes_v, float* dirs) {
         return dspmap_view_rays(h_, quat_wxyz, planes_h, planes_v, dirs);
     }
+    /* extension: frontiers (dspmap_build_frontiers in dspmap.h): the known cells (0 <= age <= max_age) with a clear bit in the layer t
+     * selects of the cast grid and at least min_unknown unknown face neighbours, as an ascending list of voxel indices and summed over
+     * blocks of block^3 voxels, whose centroids (sum / count) are where a planner puts its candidate views.  buildFrontiers enqueues;
+     * the getters copy the first min(cap, n) entries and report n.  Return DSPMAP_OK or a negative error code. */
+    int buildFrontiers(int max_age, int min_unknown = 1, int block = 4, float t = -1.f) {
+        return dspmap_build_frontiers(h_, t, max_age, min_unknown, block, 0);
+    }
+    int getFrontierCells(int cap, int* cells, int& n) { return dspmap_get_frontier_cells(h_, cap, cells, &n); }
+    int getFrontierBlocks(int cap, dspmap_frontier_block* blocks, int& n) { return dspmap_get_frontier_blocks(h_, cap, blocks, &n); }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

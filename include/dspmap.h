@@ -211,6 +211,9 @@ enum dspmap_param {
     DSPMAP_P_VIEW_CHUNKS = 31,      /* dspmap_score_views*: workgroups per view.  0 (default) = the handle spreads a batch over the device: about four
                                        workgroups per compute unit in all, at most 64 per view and never more than the map has rows for; 1 .. 64 = that
                                        many (capped likewise).  The scores are integer counts and do not depend on it */
+    DSPMAP_P_FRONTIER_MERGE = 32,   /* dspmap_build_frontiers: 1 (default) = the frontier lanes of a wave that fall into one block are summed with
+                                       ballots and popcounts and added to the block's record by one lane (five integer atomics per wave and block);
+                                       0 = every frontier lane adds its own cell (five per cell).  For measurement: integer sums, the same result */
     DSPMAP_P_PAIR_CULL_SIGMAS = 13  /* mapUpdate evaluates a (particle, observation) pair only if their ranges differ by at most this many
                                        sigma_ob (default 9: the dropped terms are < 1e-19 and zero on the fixed-point Ck grid);
                                        a huge value evaluates every pair of the neighbourhood like the reference's loops */
@@ -733,6 +736,73 @@ int dspmap_score_views(dspmap_t* m, int n, const dspmap_view* views_host, int ma
 int dspmap_score_views_device(dspmap_t* m, int n, const dspmap_view* views_dev, int max_age, int flags, dspmap_view_score* out_dev);
 int dspmap_view_rays(dspmap_t* m, const float quat_wxyz[4], float* planes_h_host, float* planes_v_host, float* dirs_host);
 int dspmap_debug_view_cells(dspmap_t* m, const dspmap_view* view_host, int flags, unsigned long long* words_out_host, float* ml_out_host);
+
+/* ---- frontier cells and frontier blocks: the known-free cells that touch unknown space (no counterpart in the reference).  Every
+ * exploration planner starts from the frontier; block centroids are what it turns into dspmap_view candidates, so that the loop
+ * update -> known_integrate -> build_cast_grid -> build_frontiers -> score_views never leaves the device.  An extension beside the
+ * frame, like the sections above: the frame path, its launch chain and the captured graph do not know about it.
+ *
+ *  Inputs: the grid of the last dspmap_build_cast_grid EXACTLY AS IT IS (inflated, masked or replaced through
+ *  dspmap_debug_set_cast_grid) and the known-space layer, synchronised to the current position first like every known-space entry
+ *  point.  t selects ONE layer as for a view: layer 0 for t < 0 or a map without horizons, else layer 1 + k(t) with the k(t) of
+ *  dspmap_query_occupancy.  Per voxel c, with the ages voxel by voxel as dspmap_get_known orders them:
+ *     known(c)    <=>  0 <= age <= max_age
+ *     unknown(c)  <=>  not known(c)                      (dspmap_mask_cast_grid's notion of unknown)
+ *     free(c)     <=>  known(c) and the bit of c is clear in the selected layer
+ *     u(c)         =   the number of c's six face neighbours INSIDE THE MAP that are unknown.  The outside of the map does not exist, as
+ *                      for arrival fields, so 0 <= u <= 6.  Unknown is decided by age alone: the neighbour's bit is not consulted (a
+ *                      masked grid has it set).
+ *     frontier(c) <=>  free(c) and u(c) >= min_unknown,  min_unknown in 1 .. 6
+ *  Blocks: voxel (x, y, z) belongs to block (x / block, y / block, z / block) in map indices, block in 1 ..
+ *  DSPMAP_FRONTIER_MAX_BLOCK; with nb_a = ceil(n_a / block) the block index is (Z * nb_y + Y) * nb_x + X.  A block's record is {block
+ *  index, count = its frontier cells, sum_x, sum_y, sum_z = the sums of their voxel indices per axis, unknown_faces = the sum of their
+ *  u}: six ints.  count <= 32^3 = 2^15 and an index is < 1024 = 2^10 (dspmap_create's limits), u <= 6: every sum stays below 2^25.  The
+ *  host derives a centroid as sum / count.
+ *  One build gives, all integers, defined bit for bit and independent of the launch:
+ *   1. the frontier bit grid [nz][ny][W] in the cast grid's word layout; bits at x >= nx are 0;
+ *   2. the voxel indices (the reference's voxel order, :1081) of the frontier cells in ASCENDING order;
+ *   3. the records of the non-empty blocks in ASCENDING block index;
+ *   4. the counts {n_cells, n_blocks, n_free}; n_free = the cells with free(c).
+ *
+ *  - dspmap_build_frontiers: enqueued on the handle's stream behind the grid's build and the frame, no synchronisation.
+ *  - dspmap_frontier_counts, dspmap_get_frontier_grid: host copies, synchronous.  dspmap_get_frontier_cells / _blocks copy the first
+ *    min(cap, n) entries of the list and set *n_out = n, the length of the whole list; out_host may be NULL for cap == 0.
+ *  - dspmap_frontier_*_device: the device buffers of the last build, NULL when there is none or it is stale; valid once the handle's
+ *    stream has reached the build (the three counts too), until the next build or the handle's destruction.
+ *  - arguments, checked before the device is touched, DSPMAP_E_ARG with a text: a NULL handle, a NaN t, max_age < 0, min_unknown outside
+ *    1 .. 6, block outside 1 .. DSPMAP_FRONTIER_MAX_BLOCK, flags != 0, a NULL output, cap < 0.  Then, in dspmap_score_views' order: a
+ *    sharded handle (slab) is DSPMAP_E_STATE; a stale or never-built grid is DSPMAP_E_STATE with a text naming dspmap_build_cast_grid
+ *    (without a usable device this is what a valid call reports: there is no grid without one); a layer without an integration since
+ *    its last reset is DSPMAP_E_STATE with a text naming dspmap_known_integrate.  The accessors on a stale or never-built snapshot
+ *    are DSPMAP_E_STATE with a text naming dspmap_build_frontiers.
+ *  - life cycle.  The result is a snapshot of the grid, of the layer and of the window.  It goes stale with everything that makes the
+ *    cast grid stale, with every dspmap_build_cast_grid, dspmap_mask_cast_grid and dspmap_debug_set_cast_grid, with
+ *    dspmap_known_integrate, dspmap_known_reset and dspmap_debug_set_known, and with dspmap_set_current_position.
+ *  - read-only towards the map, the grid and the known-space layer, beyond the layer's own synchronisation; the captured frame and its
+ *    parameter ring are untouched.  The first build allocates one bit grid, V ints for the cell list, one int per grid word and,
+ *    per block of the map, two records and a few bytes of scan scratch (these grow when a later build uses a smaller block); all of
+ *    it is freed with the device state.  A handle that never builds frontiers allocates nothing.
+ *  - dspmap_debug_set_known (test hook): age_host holds V ints in the reference's voxel order, each in [-1, DSPMAP_P_UPDATE_COUNTER -
+ *    1]; anything else is DSPMAP_E_ARG; a handle without an accepted frame is DSPMAP_E_STATE.  It synchronises the window, allocates
+ *    the store if needed and writes stamp = counter - age (0 for -1) through the toroidal slot mapping, so that dspmap_get_known
+ *    returns exactly age_host; the layer counts as integrated.  Synchronous. */
+#define DSPMAP_FRONTIER_MAX_BLOCK 32
+typedef struct dspmap_frontier_block {
+    int block;           /* (Z * nb_y + Y) * nb_x + X */
+    int count;           /* frontier cells of the block, >= 1 */
+    int sum_x, sum_y, sum_z;   /* sums of their voxel indices per axis */
+    int unknown_faces;   /* sum of their u */
+} dspmap_frontier_block;
+int dspmap_build_frontiers(dspmap_t* m, float t, int max_age, int min_unknown, int block, int flags /* must be 0 */);
+int dspmap_frontier_counts(dspmap_t* m, long long out[3]);                       /* {n_cells, n_blocks, n_free}; synchronous */
+int dspmap_get_frontier_grid(dspmap_t* m, unsigned long long* out_host);         /* nz * ny * W words; synchronous */
+int dspmap_get_frontier_cells(dspmap_t* m, int cap, int* out_host, int* n_out);
+int dspmap_get_frontier_blocks(dspmap_t* m, int cap, dspmap_frontier_block* out_host, int* n_out);
+const unsigned long long* dspmap_frontier_grid_device(dspmap_t* m);
+const int* dspmap_frontier_cells_device(dspmap_t* m);
+const dspmap_frontier_block* dspmap_frontier_blocks_device(dspmap_t* m);
+const long long* dspmap_frontier_counts_device(dspmap_t* m);
+int dspmap_debug_set_known(dspmap_t* m, const int* age_host);
 
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
