@@ -99,6 +99,7 @@ REACH_MAX_STEPS = 4096       # DSPMAP_REACH_MAX_STEPS
 REACH_UNREACHED = 65535      # DSPMAP_REACH_UNREACHED
 REACH_WITH_CURRENT = 2       # DSPMAP_REACH_WITH_CURRENT
 REACH_DEVICE_SETS = 4        # DSPMAP_REACH_DEVICE_SETS
+REACH_TIMELINE_MAX_BYTES = 1 << 30   # DSPMAP_REACH_TIMELINE_MAX_BYTES
 FORECAST_MAX_TIMES = 64      # DSPMAP_FORECAST_MAX_TIMES
 FORECAST_LERP = 2            # DSPMAP_FORECAST_LERP
 # dspmap_view / dspmap_view_score (dspmap_score_views) and the DSPMAP_VIEW_* statuses
@@ -162,6 +163,13 @@ SIGNATURES = {
     "dspmap_reach_paths": (_i, [_P, _i, _P, _i, _i, _P, _P]),
     "dspmap_reach_paths_device": (_i, [_P, _i, _P, _i, _i, _P, _P]),
     "dspmap_debug_reach_storage": (_i, [_P, _P]),
+    "dspmap_build_reach_timeline": (_i, [_P, _i, _i, _P, _f, _f, _i, _i]),
+    "dspmap_build_reach_timeline_device": (_i, [_P, _i, _i, _P, _f, _f, _i, _i]),
+    "dspmap_reach_timeline_device": (_P, [_P]),
+    "dspmap_reach_last_steps": (_i, [_P, _P]),
+    "dspmap_get_reach_sets": (_i, [_P, _i, _i, _i, _P]),
+    "dspmap_reach_timeline_paths": (_i, [_P, _i, _P, _i, _i, _P, _P]),
+    "dspmap_reach_timeline_paths_device": (_i, [_P, _i, _P, _i, _i, _P, _P]),
     "dspmap_debug_set_cast_grid": (_i, [_P, _P]),
     "dspmap_build_forecast": (_i, [_P, _i, _P, _i]),
     "dspmap_forecast_device": (_P, [_P]),
@@ -778,19 +786,23 @@ class DSPMap:
         the first step n <= max_steps at which the 6-connected front holds it.  numpy sources (REACH_POINT_DTYPE, or [n, 4] numbers)
         -> synchronous; a torch tensor on the GPU ([n, 4] int32 / float32 holding the struct's bits) -> enqueued on the handle's stream
         and ordered with torch's current stream like query_occupancy.  Read the result with reach_field / reach_fields_ptr."""
+        self._build_reach(False, sources, n_fields, t_start, step_seconds, max_steps, world, with_current, device_sets)
+
+    def _build_reach(self, timeline, sources, n_fields, t_start, step_seconds, max_steps, world, with_current, device_sets):
+        """build_reach_fields (timeline False) / build_reach_timeline (True): the same argument list on either pair of entry points"""
         flags = (QUERY_WORLD if world else 0) | (REACH_WITH_CURRENT if with_current else 0) | (REACH_DEVICE_SETS if device_sets else 0)
         if self._is_device_tensor(sources):
             q = self._reach_points_device(sources, "build_reach_fields")
             n = q.numel() // 4
             before, after = self._handle_stream_order(q.device)
             before()
-            self._chk(self.L.dspmap_build_reach_fields_device(self.h, int(n_fields), n, q.data_ptr(), float(t_start), float(step_seconds),
-                                                              int(max_steps), flags))
+            fn = self.L.dspmap_build_reach_timeline_device if timeline else self.L.dspmap_build_reach_fields_device
+            self._chk(fn(self.h, int(n_fields), n, q.data_ptr(), float(t_start), float(step_seconds), int(max_steps), flags))
             after()
             return
         q = self._reach_points(sources, "build_reach_fields")
-        self._chk(self.L.dspmap_build_reach_fields(self.h, int(n_fields), len(q), _ptr(q) if len(q) else None, float(t_start),
-                                                   float(step_seconds), int(max_steps), flags))
+        fn = self.L.dspmap_build_reach_timeline if timeline else self.L.dspmap_build_reach_fields
+        self._chk(fn(self.h, int(n_fields), len(q), _ptr(q) if len(q) else None, float(t_start), float(step_seconds), int(max_steps), flags))
 
     def reach_field(self, field=None, n_fields=None):
         """the values of one field of the last build as numpy uint16 [nz, ny, nx] (REACH_UNREACHED where the front never came), or with
@@ -837,6 +849,60 @@ class DSPMap:
         cells = np.zeros((len(q), max(max_len, 0)), np.int32)
         self._chk(self.L.dspmap_reach_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags, _ptr(steps) if len(q) else None,
                                             _ptr(cells) if max_len > 0 else None))
+        return steps, cells
+
+    # -- space-time paths (extension; semantics in include/dspmap.h next to dspmap_build_reach_timeline)
+    def build_reach_timeline(self, sources, n_fields=1, t_start=-1.0, step_seconds=0.0, max_steps=REACH_MAX_STEPS, world=False,
+                             with_current=False, device_sets=False):
+        """build_reach_fields -- the same arguments, the same fields, numpy synchronous and a torch GPU tensor enqueued -- that also keeps
+        the reached set of every step (n_fields * (max_steps + 1) * nz * ny * W * 8 bytes, at most REACH_TIMELINE_MAX_BYTES): what
+        reach_sets hands out and reach_timeline_paths walks backwards through, also where the tested layer changed during the steps."""
+        self._build_reach(True, sources, n_fields, t_start, step_seconds, max_steps, world, with_current, device_sets)
+        self._timeline_steps = int(max_steps)
+
+    def reach_last_steps(self, n_fields):
+        """int32 [n_fields]: the last step each field of the last timeline build executed (a later step repeats its set); synchronous"""
+        out = np.zeros(REACH_MAX_FIELDS, np.int32)
+        self._chk(self.L.dspmap_reach_last_steps(self.h, _ptr(out)))
+        return out[:int(n_fields)].copy()
+
+    def reach_sets(self, field, first_step=0, n_steps=None):
+        """the sets R_first_step .. of one field of the last timeline build as numpy uint64 [n_steps, nz, ny, W] (bit x & 63 of word
+        x >> 6, as cast_grid); n_steps=None: every step from first_step to the build's max_steps.  Steps behind the field's last executed
+        one repeat it.  Synchronous host copy."""
+        n = max(getattr(self, "_timeline_steps", 0) + 1 - int(first_step), 0) if n_steps is None else int(n_steps)
+        out = np.zeros((max(n, 0), self.cfg.nz, self.cfg.ny, (self.cfg.nx + 63) // 64), np.uint64)
+        self._chk(self.L.dspmap_get_reach_sets(self.h, int(field), int(first_step), n, _ptr(out) if n > 0 else None))
+        return out
+
+    def reach_timeline_ptr(self):
+        """device address of the rows [n_fields][max_steps + 1][nz][ny][W], or None when there are none / they are stale"""
+        return self.L.dspmap_reach_timeline_device(self.h) or None
+
+    def reach_timeline_paths(self, starts, max_len, world=False):
+        """walk backwards through the sets of the last timeline build from starts {x, y, z, field}: (steps [n] int32: the start's first
+        arrival v, -1 unreached, -2 outside the map, -3 invalid; cells [n, max_len] int32: the voxel occupied at step v - j, waits
+        included, down to a source cell at step 0, -1 behind the end).  numpy in -> numpy out, synchronous; a torch tensor on the GPU ->
+        tensors on the same device, enqueued like reach_paths."""
+        flags = QUERY_WORLD if world else 0
+        max_len = int(max_len)
+        if self._is_device_tensor(starts):
+            import torch
+            q = self._reach_points_device(starts, "reach_timeline_paths")
+            n = q.numel() // 4
+            steps = torch.empty(n, dtype=torch.int32, device=q.device)
+            cells = torch.empty((n, max(max_len, 0)), dtype=torch.int32, device=q.device)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_reach_timeline_paths_device(self.h, n, q.data_ptr(), max_len, flags, steps.data_ptr(),
+                                                                cells.data_ptr() if max_len > 0 else None))
+            after()
+            return steps, cells
+        q = self._reach_points(starts, "reach_timeline_paths")
+        steps = np.zeros(len(q), np.int32)
+        cells = np.zeros((len(q), max(max_len, 0)), np.int32)
+        self._chk(self.L.dspmap_reach_timeline_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags,
+                                                     _ptr(steps) if len(q) else None, _ptr(cells) if max_len > 0 else None))
         return steps, cells
 
     # -- occupancy forecast at caller-chosen times (extension; semantics in include/dspmap.h next to dspmap_build_forecast)

@@ -229,8 +229,9 @@ static void free_dev(dspmap* m) {
     m->df_field = nullptr; m->df_g8 = nullptr; m->df_h16 = nullptr; m->df_valid = false;
     for (void* q : {(void*)m->cg_bits, (void*)m->cg_tmp}) if (q) chk(hipFree(q), "hipFree");
     m->cg_bits = nullptr; m->cg_tmp = nullptr; m->cg_valid = false;
-    for (void* q : {(void*)m->rf_field, (void*)m->rf_sets}) if (q) chk(hipFree(q), "hipFree");
+    for (void* q : {(void*)m->rf_field, (void*)m->rf_sets, (void*)m->tl_hist, (void*)m->tl_last}) if (q) chk(hipFree(q), "hipFree");
     m->rf_field = nullptr; m->rf_sets = nullptr; m->rf_field_cells = 0; m->rf_sets_words = 0; m->rf_valid = false;
+    m->tl_hist = nullptr; m->tl_last = nullptr; m->tl_hist_words = 0; m->tl_valid = false;
     for (void* q : {(void*)m->fc_field, (void*)m->fc_acc}) if (q) chk(hipFree(q), "hipFree");
     m->fc_field = nullptr; m->fc_acc = nullptr; m->fc_cap = 0; m->fc_valid = false;
     if (m->kn_stamp) chk(hipFree(m->kn_stamp), "hipFree");
@@ -1048,6 +1049,7 @@ extern "C" int dspmap_build_cast_grid(dspmap_t* m, float thr, int inflate_voxels
     BENIGN(m);
     m->cg_valid = false;
     m->rf_valid = false;   // (arrival fields are grown in the grid this build replaces)
+    m->tl_valid = false;   // (... and so is their timeline)
     m->fr_valid = false;   // (... and frontiers found in it)
     if (!m->cg_bits) {
         HIPCHK(m, hipMalloc(&m->cg_bits, sizeof(u64) * words));
@@ -1176,7 +1178,9 @@ static int reach_layer_host(const MapDims& d, bool timed, float t_start, float s
         if (d.pred_t[j] >= tt) k = j;
     return k + 1;
 }
-static int reach_build_check(dspmap* m, int n_fields, int n_src, const void* src, float t_start, float step_seconds, int max_steps, int flags) {
+// the checks of both builds; `timeline`: dspmap_build_reach_timeline*, which adds the cap on the kept sets behind the other arguments
+static int reach_build_check(dspmap* m, int n_fields, int n_src, const void* src, float t_start, float step_seconds, int max_steps, int flags,
+                             bool timeline = false) {
     if (!m) return DSPMAP_E_ARG;
     if (n_fields < 1 || n_fields > DSPMAP_REACH_MAX_FIELDS)
         return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: n_fields %d outside [1, %d]", n_fields, DSPMAP_REACH_MAX_FIELDS);
@@ -1191,19 +1195,29 @@ static int reach_build_check(dspmap* m, int n_fields, int n_src, const void* src
         return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: unknown flags 0x%x", flags);
     const unsigned long long cells = (unsigned long long)n_fields * (unsigned long long)m->d.v_glob;
     if (cells > 0x80000000ull) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: %d fields of %d cells exceed 2^31 cells", n_fields, m->d.v_glob);
+    if (timeline) {   // (n_fields <= 64, max_steps + 1 <= 4097, a layer's words < 2^31: no overflow in 64 bits)
+        const unsigned long long bytes = (unsigned long long)n_fields * (unsigned long long)(max_steps + 1) * cast_layer_words(m->d) * sizeof(u64);
+        if (bytes > DSPMAP_REACH_TIMELINE_MAX_BYTES)
+            return dspmap_fail(m, DSPMAP_E_ARG, "reach timeline: the sets of %d fields and %d steps take %llu bytes, more than "
+                                                "DSPMAP_REACH_TIMELINE_MAX_BYTES = %llu", n_fields, max_steps + 1, bytes,
+                               (unsigned long long)DSPMAP_REACH_TIMELINE_MAX_BYTES);
+    }
     if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
         return dspmap_fail(m, DSPMAP_E_STATE, "reach fields: a slab handle holds part of the map; a wavefront crosses slabs");
-    return cast_grid_ready(m, "dspmap_build_reach_fields");
+    return cast_grid_ready(m, timeline ? "dspmap_build_reach_timeline" : "dspmap_build_reach_fields");
 }
-// the launch behind both entry points; src_dev may be NULL with n_src == 0
+// the launch behind all four build entry points; src_dev may be NULL with n_src == 0.  keep: the timeline build, which also stores every
+// step's set (a plain build replaces the fields a timeline belongs to, so it leaves none)
 static int reach_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_point* src_dev, float t_start, float step_seconds, int max_steps,
-                       int flags) {
+                       int flags, bool keep = false) {
     const MapDims& d = m->d;
     m->rf_valid = false;
+    m->tl_valid = false;
     const size_t cells = (size_t)n_fields * d.v_glob, lw = cast_layer_words(d);
     const bool lds = 2 * sizeof(u64) * lw <= (size_t)REACH_LDS_BYTES && !(flags & DSPMAP_REACH_DEVICE_SETS);
     const size_t set_words = lds ? 0 : 2 * lw * (size_t)n_fields;
-    if (cells > m->rf_field_cells || set_words > m->rf_sets_words) {   // grown only after the stream has drained (an earlier call may still read them)
+    const size_t hist_words = keep ? (size_t)n_fields * ((size_t)max_steps + 1) * lw : 0;
+    if (cells > m->rf_field_cells || set_words > m->rf_sets_words || hist_words > m->tl_hist_words || (keep && !m->tl_last)) {   // grown only after the stream has drained (an earlier call may still read them)
         HIPCHK(m, hipStreamSynchronize(m->stream));
         if (!m->rf_field) reach_init_device();
         if (cells > m->rf_field_cells) {
@@ -1216,6 +1230,12 @@ static int reach_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_po
             HIPCHK(m, hipMalloc(&m->rf_sets, sizeof(u64) * set_words));
             m->rf_sets_words = set_words;
         }
+        if (hist_words > m->tl_hist_words) {
+            if (m->tl_hist) { HIPCHK(m, hipFree(m->tl_hist)); m->tl_hist = nullptr; m->tl_hist_words = 0; }
+            HIPCHK(m, hipMalloc(&m->tl_hist, sizeof(u64) * hist_words));
+            m->tl_hist_words = hist_words;
+        }
+        if (keep && !m->tl_last) HIPCHK(m, hipMalloc(&m->tl_last, sizeof(int) * DSPMAP_REACH_MAX_FIELDS));
     }
     ReachArgs a;
     a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
@@ -1231,17 +1251,20 @@ static int reach_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_po
     a.n_fields = n_fields; a.n_src = n_src;
     a.bits = m->cg_bits; a.field = m->rf_field; a.sets = lds ? nullptr : m->rf_sets;
     HIPCHK(m, hipMemsetAsync(m->rf_field, 0xff, sizeof(unsigned short) * cells, m->stream));   // every value DSPMAP_REACH_UNREACHED
-    launch_reach(dspmap_ctx_of(m), a, src_dev);
+    launch_reach(dspmap_ctx_of(m), a, src_dev, keep ? m->tl_hist : nullptr, keep ? m->tl_last : nullptr);
     HIPCHK(m, hipGetLastError());
     m->rf_n = n_fields;
     m->rf_invariant = reach_layer_host(d, timed, t_start, step_seconds, 0) == l_last;
     m->rf_storage[0] = lds ? n_fields : 0; m->rf_storage[1] = lds ? 0 : n_fields;
     m->rf_valid = true;
+    m->tl_valid = keep;
+    m->tl_max_steps = max_steps;
     return DSPMAP_OK;
 }
-extern "C" int dspmap_build_reach_fields(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds,
-                                         int max_steps, int flags) {
-    int rc = reach_build_check(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags);
+// the synchronous entry points: the sources go through the query staging buffer
+static int reach_build_host(dspmap* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds, int max_steps,
+                            int flags, bool keep) {
+    int rc = reach_build_check(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, keep);
     if (rc != DSPMAP_OK) return rc;
     dspmap_reach_point* ds = nullptr;
     if (n_src > 0) {
@@ -1249,9 +1272,23 @@ extern "C" int dspmap_build_reach_fields(dspmap_t* m, int n_fields, int n_src, c
         ds = (dspmap_reach_point*)m->q_buf;
         HIPCHK(m, hipMemcpyAsync(ds, src, sizeof(dspmap_reach_point) * (size_t)n_src, hipMemcpyHostToDevice, m->stream));
     }
-    if ((rc = reach_build(m, n_fields, n_src, ds, t_start, step_seconds, max_steps, flags)) != DSPMAP_OK) return rc;
+    if ((rc = reach_build(m, n_fields, n_src, ds, t_start, step_seconds, max_steps, flags, keep)) != DSPMAP_OK) return rc;
     HIPCHK(m, hipStreamSynchronize(m->stream));
     return DSPMAP_OK;
+}
+extern "C" int dspmap_build_reach_fields(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds,
+                                         int max_steps, int flags) {
+    return reach_build_host(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, false);
+}
+extern "C" int dspmap_build_reach_timeline(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds,
+                                           int max_steps, int flags) {
+    return reach_build_host(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, true);
+}
+extern "C" int dspmap_build_reach_timeline_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start,
+                                                  float step_seconds, int max_steps, int flags) {
+    const int rc = reach_build_check(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, true);
+    if (rc != DSPMAP_OK) return rc;
+    return reach_build(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, true);
 }
 extern "C" int dspmap_build_reach_fields_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start,
                                                 float step_seconds, int max_steps, int flags) {
@@ -1279,7 +1316,58 @@ extern "C" int dspmap_get_reach_field(dspmap_t* m, int field, unsigned short* ou
     HIPCHK(m, hipStreamSynchronize(m->stream));
     return DSPMAP_OK;
 }
-static int reach_paths_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
+// the fields' timeline: valid while the fields it was built with are
+static int reach_timeline_ready(dspmap* m, const char* what) {
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: a slab handle holds part of the map; a wavefront crosses slabs", what);
+    if (!m->tl_valid || !m->rf_valid || !m->cg_valid)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no timeline, or the map, its cast grid or the arrival fields have changed since it was built "
+                                              "(dspmap_build_reach_timeline)", what);
+    if (m->device >= 0) (void)hipSetDevice(m->device);
+    return DSPMAP_OK;
+}
+extern "C" const unsigned long long* dspmap_reach_timeline_device(dspmap_t* m) {
+    return (m && m->tl_valid && m->rf_valid && m->cg_valid) ? (const unsigned long long*)m->tl_hist : nullptr;
+}
+extern "C" int dspmap_reach_last_steps(dspmap_t* m, int* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "reach last steps: NULL output array");
+    const int rc = reach_timeline_ready(m, "dspmap_reach_last_steps");
+    if (rc != DSPMAP_OK) return rc;
+    HIPCHK(m, hipMemcpyAsync(out, m->tl_last, sizeof(int) * (size_t)m->rf_n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_reach_sets(dspmap_t* m, int field, int first_step, int n_steps, unsigned long long* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (field < 0 || field >= DSPMAP_REACH_MAX_FIELDS) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: field %d outside [0, %d)", field, DSPMAP_REACH_MAX_FIELDS);
+    if (first_step < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: negative first_step %d", first_step);
+    if (n_steps < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: negative n_steps %d", n_steps);
+    if (first_step > DSPMAP_REACH_MAX_STEPS + 1 || n_steps > DSPMAP_REACH_MAX_STEPS + 1 - first_step)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: steps [%d, %d + %d) outside [0, %d]", first_step, first_step, n_steps, DSPMAP_REACH_MAX_STEPS);
+    if (n_steps > 0 && !out) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: NULL output array with n_steps %d", n_steps);
+    const int rc = reach_timeline_ready(m, "dspmap_get_reach_sets");
+    if (rc != DSPMAP_OK) return rc;
+    if (field >= m->rf_n) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: field %d outside [0, %d), the fields of the last build", field, m->rf_n);
+    if (first_step + n_steps > m->tl_max_steps + 1)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: steps [%d, %d) outside [0, %d], the steps of the last build", first_step, first_step + n_steps,
+                           m->tl_max_steps);
+    if (n_steps == 0) return DSPMAP_OK;
+    int last = 0;   // the field's last executed step: a later one repeats its row
+    HIPCHK(m, hipMemcpyAsync(&last, m->tl_last + field, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    if (last < 0 || last > m->tl_max_steps) return dspmap_fail(m, DSPMAP_E_DEVICE, "reach sets: field %d reports last step %d outside [0, %d]", field, last, m->tl_max_steps);
+    const size_t lw = cast_layer_words(m->d);
+    const u64* rows = m->tl_hist + (size_t)field * ((size_t)m->tl_max_steps + 1) * lw;
+    const int n_own = first_step > last ? 0 : (first_step + n_steps - 1 > last ? last - first_step + 1 : n_steps);   // rows the build wrote
+    if (n_own > 0) HIPCHK(m, hipMemcpyAsync(out, rows + (size_t)first_step * lw, sizeof(u64) * lw * (size_t)n_own, hipMemcpyDeviceToHost, m->stream));
+    for (int k = n_own; k < n_steps; ++k)
+        HIPCHK(m, hipMemcpyAsync(out + (size_t)k * lw, rows + (size_t)last * lw, sizeof(u64) * lw, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+// the argument checks of dspmap_reach_paths* and dspmap_reach_timeline_paths*
+static int reach_paths_args_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
     if (!m) return DSPMAP_E_ARG;
     if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: negative start count %d", n);
     if (max_len < 0 || max_len > DSPMAP_REACH_MAX_STEPS + 1)
@@ -1289,8 +1377,12 @@ static int reach_paths_check(dspmap* m, int n, const void* start, int max_len, i
     if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: unknown flags 0x%x", flags);
     if ((unsigned long long)n * (unsigned long long)max_len > 0x80000000ull)
         return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: %d paths of %d cells exceed 2^31 cells", n, max_len);
-    const int rc = reach_ready(m, "dspmap_reach_paths");
+    return DSPMAP_OK;
+}
+static int reach_paths_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
+    int rc = reach_paths_args_check(m, n, start, max_len, flags, steps_out, cells_out);
     if (rc != DSPMAP_OK) return rc;
+    if ((rc = reach_ready(m, "dspmap_reach_paths")) != DSPMAP_OK) return rc;
     if (!m->rf_invariant)
         return dspmap_fail(m, DSPMAP_E_STATE, "reach paths: the fields of the last build are not time-invariant (the tested layer changed "
                                               "during the steps): first arrivals alone do not determine a path");
@@ -1328,6 +1420,45 @@ extern "C" int dspmap_reach_paths_device(dspmap_t* m, int n, const dspmap_reach_
     HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;
 }
+static ReachTimelinePathArgs reach_timeline_path_args(const dspmap* m, int max_len, int flags) {
+    ReachTimelinePathArgs a;
+    a.world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a.ox = m->cur_pos[0]; a.oy = m->cur_pos[1]; a.oz = m->cur_pos[2];
+    a.n_fields = m->rf_n; a.max_len = max_len; a.max_steps = m->tl_max_steps;
+    a.field = m->rf_field; a.hist = m->tl_hist; a.last = m->tl_last;
+    return a;
+}
+static int reach_timeline_paths_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
+    const int rc = reach_paths_args_check(m, n, start, max_len, flags, steps_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    return reach_timeline_ready(m, "dspmap_reach_timeline_paths");
+}
+extern "C" int dspmap_reach_timeline_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out,
+                                           int* cells_out) {
+    int rc = reach_timeline_paths_check(m, n, start, max_len, flags, steps_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    const size_t sb = q_align(sizeof(dspmap_reach_point) * (size_t)n), tb = q_align(sizeof(int) * (size_t)n), cb = sizeof(int) * (size_t)n * max_len;
+    if ((rc = query_buf(m, sb + tb + cb)) != DSPMAP_OK) return rc;
+    dspmap_reach_point* ds = (dspmap_reach_point*)m->q_buf;
+    int* dt = (int*)((char*)m->q_buf + sb);
+    int* dc = max_len ? (int*)((char*)m->q_buf + sb + tb) : nullptr;
+    HIPCHK(m, hipMemcpyAsync(ds, start, sizeof(dspmap_reach_point) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+    launch_reach_timeline_paths(dspmap_ctx_of(m), reach_timeline_path_args(m, max_len, flags), n, ds, dt, dc);
+    HIPCHK(m, hipGetLastError());
+    HIPCHK(m, hipMemcpyAsync(steps_out, dt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (max_len) HIPCHK(m, hipMemcpyAsync(cells_out, dc, cb, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_reach_timeline_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out,
+                                                  int* cells_out) {
+    const int rc = reach_timeline_paths_check(m, n, start, max_len, flags, steps_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    launch_reach_timeline_paths(dspmap_ctx_of(m), reach_timeline_path_args(m, max_len, flags), n, start, steps_out, cells_out);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
 extern "C" int dspmap_debug_reach_storage(dspmap_t* m, long long out[2]) {
     if (!m) return DSPMAP_E_ARG;
     if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "reach storage: NULL output array");
@@ -1350,6 +1481,7 @@ extern "C" int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long*
     const int rc = cast_grid_ready(m, "dspmap_debug_set_cast_grid");
     if (rc != DSPMAP_OK) return rc;
     m->rf_valid = false;
+    m->tl_valid = false;
     m->fr_valid = false;
     HIPCHK(m, hipMemcpyAsync(m->cg_bits, words, sizeof(u64) * total, hipMemcpyHostToDevice, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));   // (the caller's array is free again)
@@ -1640,6 +1772,7 @@ extern "C" int dspmap_mask_cast_grid(dspmap_t* m, int max_age, int flags) {
     KnownArgs a;
     if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
     m->rf_valid = false;   // (arrival fields were grown in the grid as it was)
+    m->tl_valid = false;
     m->fr_valid = false;   // (... and frontiers found in it)
     launch_known_mask(m->d, m->stream, a, max_age, m->d.T + 1, m->cg_bits);
     HIPCHK(m, hipGetLastError());

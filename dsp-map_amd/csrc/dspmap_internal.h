@@ -191,6 +191,13 @@ struct dspmap {
     int rf_n = 0;                    // fields of the last build
     bool rf_invariant = false;       // ... whose tested layer never changed: paths exist
     long long rf_storage[2] = {0, 0};   // ... whose sets lived in LDS / in device memory (dspmap_debug_reach_storage)
+    // their timeline (dspmap_build_reach_timeline): every step's set [rf_n][tl_max_steps + 1][nz * ny * W] and the last step each field
+    // executed [DSPMAP_REACH_MAX_FIELDS]; allocated by the first timeline build (grown by a larger one), freed with the device state.
+    // tl_valid: the fields of the last build came with a timeline -- cleared wherever rf_valid is, and by every plain build
+    u64* tl_hist = nullptr; size_t tl_hist_words = 0;
+    int* tl_last = nullptr;
+    bool tl_valid = false;
+    int tl_max_steps = 0;            // max_steps of the build that wrote it
     // occupancy forecast (dspmap_build_forecast): the layers [fc_n][V] floats and the sweep's accumulators [fc_n + 1][v_loc] (the moving
     // particles' per layer, then the static sums); allocated (and grown) by a build, freed with the device state.  fc_valid: the life cycle
     // of df_valid (dspmap_snapshots_stale)
@@ -247,7 +254,9 @@ struct dspmap {
 
 // everything that computes a frame or replaces state calls this: the distance field, the cast grid, the arrival fields grown in it, the
 // frontiers found in it and the forecast are snapshots of the map before it
-inline void dspmap_snapshots_stale(dspmap* m) { m->df_valid = false; m->cg_valid = false; m->rf_valid = false; m->fc_valid = false; m->fr_valid = false; }
+inline void dspmap_snapshots_stale(dspmap* m) {
+    m->df_valid = false; m->cg_valid = false; m->rf_valid = false; m->tl_valid = false; m->fc_valid = false; m->fr_valid = false;
+}
 int dspmap_fail(dspmap* m, int code, const char* fmt, ...);
 void dspmap_prof_mark(dspmap* m, int i);
 void dspmap_prof_collect(dspmap* m);

@@ -219,10 +219,21 @@ struct ReachPathArgs {
     int n_fields, max_len;
     const unsigned short* field;
 };
+struct ReachTimelinePathArgs {   // dspmap_reach_timeline_paths: backwards through the sets a timeline build kept
+    float ox, oy, oz;
+    int world;
+    int n_fields, max_len;
+    int max_steps;           // of the build: a field's history has max_steps + 1 rows
+    const unsigned short* field;
+    const u64* hist;         // [n_fields][max_steps + 1][nz * ny * W]
+    const int* last;         // [n_fields]: the last row the build wrote
+};
 struct dspmap_reach_point;
 #define REACH_LDS_BYTES (160 * 1024 - 256)   // what a workgroup's two sets may take of the CU's 160 KiB (the rest: the step flags)
 void reach_init_device();   // per device, once (dspmap_init_device)
-void launch_reach(const LaunchCtx& c, const ReachArgs& a, const struct dspmap_reach_point* src);
+void launch_reach(const LaunchCtx& c, const ReachArgs& a, const struct dspmap_reach_point* src, u64* hist, int* last);
+void launch_reach_timeline_paths(const LaunchCtx& c, const ReachTimelinePathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out,
+                                 int* cells_out);
 void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out, int* cells_out);
 // occupancy forecast at caller-chosen times from the live particle set (dspmap_forecast.hip; semantics in include/dspmap.h, dspmap_build_forecast)
 #define FORECAST_MAX_TIMES 64   // == DSPMAP_FORECAST_MAX_TIMES

@@ -24,6 +24,11 @@
 // the result.  Sources are ORed into R with atomics before step 0, every thread scanning a stride of the batch's sources for its field.
 // Every loop is bounded by max_steps, the word count or the source count; nothing waits on another workgroup.
 //
+// The timeline build (dspmap_build_reach_timeline*) is the same launch with KEEP: every step's set also goes to a dense row of device
+// memory, one more word store per word and step, and k_reach_timeline_paths walks backwards through the rows in a launch of its own.
+// Dense rows against compacting the non-zero words (a count across the workgroup per step, a search per load of the walk) and against
+// re-running the wavefront per path: DESIGN.md, "Space-time paths".
+//
 // Rejected:
 //  - one launch per step over all fields (the textbook level-synchronous BFS): up to 4096 launches of a few microseconds of work each, and
 //    the early exit would need a read-back per step.  A serpentine maze of 700 steps would cost 700 launch gaps.
@@ -63,8 +68,14 @@ __device__ __forceinline__ int reach_layer(const MapDims& d, const ReachArgs& a,
     return q_horizon(d, __fadd_rn(a.t_start, __fmul_rn((float)n, a.step_seconds))) + 1;
 }
 
-template <bool LDS>
-__global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, const float4* __restrict__ src) {
+// KEEP (dspmap_build_reach_timeline): the owner of word t also stores R_n's word to row n of its field's history, hist[(f * (max_steps + 1)
+// + n) * nwords + t] -- in step 0 and in every later step, zero words too, because nothing clears the rows -- and thread 0 leaves the last
+// step executed in last[f].  The history is write-only inside the launch (k_reach_timeline_paths reads it behind the kernel boundary), so
+// the one barrier per step and its flag rotation are those of the plain build.  hist and last follow src in the argument list so that the
+// KEEP = false instantiations read their arguments where they always did.
+template <bool LDS, bool KEEP>
+__global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, const float4* __restrict__ src, u64* __restrict__ hist,
+                                                     int* __restrict__ last) {
     extern __shared__ u64 s_reach[];
     __shared__ int s_flag[3];   // bit 0: the step changed the set, bit 1: the set is not empty
     const unsigned tid = threadIdx.x, f = blockIdx.x;
@@ -74,6 +85,8 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
     const u64* __restrict__ bits = a.bits;
     const u64 row_mask = (d.nx & 63) ? ~0ull >> (64 - (d.nx & 63)) : ~0ull;   // bits at x >= nx are never reached
     unsigned co = 0, no = nwords;                                             // R_{n-1} at set[co ..], R_n at set[no ..]
+    u64* row = KEEP ? hist + (size_t)f * ((size_t)a.max_steps + 1) * nwords : nullptr;   // row n of this field's history, from row 0 on
+    int done = a.max_steps;                                                   // (KEEP) the last step executed
 
     for (unsigned t = tid; t < nwords; t += REACH_TPB) set[co + t] = 0;
     if (tid < 3) s_flag[tid] = 0;
@@ -90,13 +103,15 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
         const int l = reach_layer(d, a, 0);
         for (unsigned t = tid; t < nwords; t += REACH_TPB) {
             u64 v = set[co + t];
+            if (KEEP && !v) row[t] = 0;
             if (!v) continue;
             u64 b = bits[(size_t)l * nwords + t];
             if (a.with_current && l > 0) b |= bits[t];
             v &= ~b;
             set[co + t] = v;
-            const unsigned row = t / W, w = t - row * W;
-            unsigned short* cell = fld + (size_t)row * d.nx + w * 64;
+            if (KEEP) row[t] = v;
+            const unsigned yz = t / W, w = t - yz * W;
+            unsigned short* cell = fld + (size_t)yz * d.nx + w * 64;
             while (v) {
                 cell[__builtin_ctzll(v)] = 0;
                 v &= v - 1;
@@ -107,6 +122,7 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
     for (int n = 1; n <= a.max_steps; ++n) {
         const int l = reach_layer(d, a, n);
         int verdict = 0;
+        if (KEEP) row += nwords;
         for (unsigned t = tid; t < nwords; t += REACH_TPB) {
             const unsigned z = t / plane, r = t - z * plane, y = r / W, w = r - y * W;
             const u64* cur = set + co + t;
@@ -125,6 +141,7 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
                 g &= ~b;
             }
             set[no + t] = g;
+            if (KEEP) row[t] = g;
             verdict |= (g != c ? 1 : 0) | (g ? 2 : 0);
             u64 fresh = g & ~c;                        // the front: cells of R_n that R_{n-1} did not hold
             if (fresh) {
@@ -141,9 +158,11 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
         __syncthreads();
         const int v = s_flag[n % 3];
         const unsigned tmp = co; co = no; no = tmp;
+        if (KEEP) done = n;
         if (!(v & 2)) break;                           // an empty set stays empty
         if (!(v & 1) && n >= a.n_fix) break;           // nothing changed and the layer never changes again: every later step repeats this one
     }
+    if (KEEP && tid == 0) last[f] = done;              // rows (done, max_steps] are never written: R_n = R_done there, for both exits
 }
 
 // one lane per start: the steepest descent through a time-invariant field, first neighbour of value v - 1 in the order -x, +x, -y, +y, -z, +z
@@ -192,22 +211,86 @@ __global__ void __launch_bounds__(REACH_PATH_TPB) k_reach_paths(MapDims d, Reach
     for (; j < a.max_len; ++j) out[j] = -1;
 }
 
-void reach_init_device() {   // per device, once (dspmap_init_device)
-    (void)hipFuncSetAttribute((const void*)k_reach<true>, hipFuncAttributeMaxDynamicSharedMemorySize, REACH_LDS_BYTES);
+// one lane per start: backwards through the sets a timeline build kept.  The cell at step s > 0 came from R_{s-1}: it waits where it is if
+// it is in that set, else it moves to the first face neighbour in the order -x, +x, -y, +y, -z, +z that is (one exists, because
+// R_s is a subset of R_{s-1} u N6(R_{s-1})).  Every loop is bounded by max_len and by the value, which falls by one per cell.
+__global__ void __launch_bounds__(REACH_PATH_TPB) k_reach_timeline_paths(MapDims d, ReachTimelinePathArgs a, int n, const float4* __restrict__ start,
+                                                                         int* __restrict__ steps_out, int* __restrict__ cells_out) {
+    const unsigned i = blockIdx.x * REACH_PATH_TPB + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    const float4 p = start[i];
+    const int f = __float_as_int(p.w);
+    int x = 0, y = 0, z = 0;
+    int st = reach_cell(d, a.ox, a.oy, a.oz, a.world, p.x, p.y, p.z, x, y, z);
+    if ((unsigned)f >= (unsigned)a.n_fields) st = -3;   // (a non-finite coordinate is -3 as well; either wins over "outside")
+    int v = 0;
+    if (st == 0) {
+        v = a.field[(size_t)f * d.v_glob + ((size_t)z * d.ny + y) * d.nx + x];
+        st = v == DSPMAP_REACH_UNREACHED ? -1 : v;
+    }
+    steps_out[i] = st;
+    int* out = cells_out + (size_t)i * a.max_len;
+    int j = 0;
+    if (st >= 0) {
+        const unsigned W = (unsigned)(d.nx + 63) >> 6;
+        const size_t nwords = (size_t)d.nz * d.ny * W;
+        const u64* __restrict__ rows = a.hist + (size_t)f * ((size_t)a.max_steps + 1) * nwords;
+        const int lastf = a.last[f];
+        for (; j < a.max_len;) {                       // (bounded by max_len; v falls by one per cell)
+            out[j++] = (z * d.ny + y) * d.nx + x;
+            if (v == 0) break;
+            const u64* __restrict__ P = rows + (size_t)min(v - 1, lastf) * nwords;   // R_{v-1} (a step behind the last one executed repeats it)
+            // the seven bit loads of a step are issued together: the own cell, then the six neighbours; independent addresses, one wait
+            const bool ok[7] = {true, x > 0, x + 1 < d.nx, y > 0, y + 1 < d.ny, z > 0, z + 1 < d.nz};
+            const int dx[7] = {0, -1, 1, 0, 0, 0, 0}, dy[7] = {0, 0, 0, -1, 1, 0, 0}, dz[7] = {0, 0, 0, 0, 0, -1, 1};
+            u64 wv[7];
+#pragma unroll
+            for (int k = 0; k < 7; ++k) {
+                const int cx = ok[k] ? x + dx[k] : x, cy = ok[k] ? y + dy[k] : y, cz = ok[k] ? z + dz[k] : z;
+                wv[k] = P[((size_t)cz * d.ny + cy) * W + ((unsigned)cx >> 6)];
+            }
+            int pick = -1;
+#pragma unroll
+            for (int k = 6; k >= 0; --k)
+                if (ok[k] && ((wv[k] >> ((x + dx[k]) & 63)) & 1)) pick = k;
+            if (pick < 0) break;                       // neither the cell nor a neighbour (never, see above): stop, the rest is -1
+            x += dx[pick]; y += dy[pick]; z += dz[pick];
+            --v;
+        }
+    }
+    for (; j < a.max_len; ++j) out[j] = -1;
 }
 
-void launch_reach(const LaunchCtx& c, const ReachArgs& a, const dspmap_reach_point* src) {
+void reach_init_device() {   // per device, once (dspmap_init_device)
+    (void)hipFuncSetAttribute((const void*)k_reach<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, REACH_LDS_BYTES);
+    (void)hipFuncSetAttribute((const void*)k_reach<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, REACH_LDS_BYTES);
+}
+
+// hist != nullptr: the timeline build -- every step's set goes to hist, the last step executed per field to last
+void launch_reach(const LaunchCtx& c, const ReachArgs& a, const dspmap_reach_point* src, u64* hist, int* last) {
     if (a.n_fields <= 0) return;
     const MapDims& d = c.d;
     const size_t set_bytes = 2 * sizeof(u64) * (size_t)d.nz * d.ny * (size_t)((d.nx + 63) >> 6);
-    if (a.sets)
-        hipLaunchKernelGGL(k_reach<false>, dim3(a.n_fields), dim3(REACH_TPB), 0, c.stream, d, a, (const float4*)src);
+    const dim3 grid(a.n_fields), block(REACH_TPB);
+    if (a.sets && hist)
+        hipLaunchKernelGGL((k_reach<false, true>), grid, block, 0, c.stream, d, a, (const float4*)src, hist, last);
+    else if (a.sets)
+        hipLaunchKernelGGL((k_reach<false, false>), grid, block, 0, c.stream, d, a, (const float4*)src, hist, last);
+    else if (hist)
+        hipLaunchKernelGGL((k_reach<true, true>), grid, block, set_bytes, c.stream, d, a, (const float4*)src, hist, last);
     else
-        hipLaunchKernelGGL(k_reach<true>, dim3(a.n_fields), dim3(REACH_TPB), set_bytes, c.stream, d, a, (const float4*)src);
+        hipLaunchKernelGGL((k_reach<true, false>), grid, block, set_bytes, c.stream, d, a, (const float4*)src, hist, last);
 }
 
 void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const dspmap_reach_point* start, int* steps_out, int* cells_out) {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_reach_paths, dim3((unsigned)(((long long)n + REACH_PATH_TPB - 1) / REACH_PATH_TPB)), dim3(REACH_PATH_TPB), 0, c.stream,
                        c.d, a, n, (const float4*)start, steps_out, cells_out);
+}
+
+void launch_reach_timeline_paths(const LaunchCtx& c, const ReachTimelinePathArgs& a, int n, const dspmap_reach_point* start, int* steps_out,
+                                 int* cells_out) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_reach_timeline_paths, dim3((unsigned)(((long long)n + REACH_PATH_TPB - 1) / REACH_PATH_TPB)), dim3(REACH_PATH_TPB), 0,
+                       c.stream, c.d, a, n, (const float4*)start, steps_out, cells_out);
 }

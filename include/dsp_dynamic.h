@@ -298,6 +298,21 @@ public:
     int reachPaths(int n, const dspmap_reach_point* starts, int max_len, int* steps, int* cells, bool world = false) {
         return dspmap_reach_paths(h_, n, starts, max_len, world ? DSPMAP_QUERY_WORLD : 0, steps, cells);
     }
+    /* extension: space-time paths (dspmap_build_reach_timeline in dspmap.h): buildReachTimeline grows the same fields as buildReachFields and
+     * keeps every step's reached set, getReachSets copies n_steps of them (nz * ny * W words each, the cast grid's layer layout) and
+     * reachTimelinePaths walks backwards through them -- also where the tested layer changed during the steps, which reachPaths refuses:
+     * cells[i * max_len + j] = the voxel occupied at step steps[i] - j, waits included.  Return DSPMAP_OK or a negative error code. */
+    int buildReachTimeline(int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds, int max_steps,
+                           bool world = false, bool with_current = false) {
+        return dspmap_build_reach_timeline(h_, n_fields, n_src, src, t_start, step_seconds, max_steps,
+                                           (world ? DSPMAP_QUERY_WORLD : 0) | (with_current ? DSPMAP_REACH_WITH_CURRENT : 0));
+    }
+    int getReachSets(int field, int first_step, int n_steps, unsigned long long* words) {
+        return dspmap_get_reach_sets(h_, field, first_step, n_steps, words);
+    }
+    int reachTimelinePaths(int n, const dspmap_reach_point* starts, int max_len, int* steps, int* cells, bool world = false) {
+        return dspmap_reach_timeline_paths(h_, n, starts, max_len, world ? DSPMAP_QUERY_WORLD : 0, steps, cells);
+    }
     /* extension: occupancy forecast at times of the caller's choosing (dspmap_build_forecast in dspmap.h): layer j = the mass of every live
      * particle, newborns included, rolled out to times[j] seconds after the last update() -- strictly ascending, at most
      * DSPMAP_FORECAST_MAX_TIMES.  Read-only towards the map; a snapshot that goes stale with the next update().  getForecast copies one

@@ -557,6 +557,63 @@ int dspmap_reach_paths(dspmap_t* m, int n, const dspmap_reach_point* start_host,
 int dspmap_reach_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start_dev, int max_len, int flags, int* steps_out_dev, int* cells_out_dev);
 /* diagnostic: out[0] / out[1] = the fields of the last build whose wave sets lived in LDS / in device memory */
 int dspmap_debug_reach_storage(dspmap_t* m, long long out[2]);
+
+/* ---- space-time paths: the wavefront's sets kept per step, and paths traced backwards through them (no counterpart in the reference).
+ * dspmap_reach_paths refuses every build in which the tested layer changed -- the builds a dynamic map is for: a gap that opens behind a
+ * passing object, a door that closes at horizon 2.  For those the first arrivals say "can I get there, and when?" but not "how?".  The
+ * missing piece is exact: keep every step's set R_n where the wavefront computes it, then walk backwards through the sets.
+ *
+ *  - build: dspmap_build_reach_timeline* has the arguments, flags (DSPMAP_QUERY_WORLD | DSPMAP_REACH_WITH_CURRENT |
+ *    DSPMAP_REACH_DEVICE_SETS), checks and check order of dspmap_build_reach_fields* and produces exactly that function's fields:
+ *    dspmap_get_reach_field, dspmap_reach_fields_device, dspmap_debug_reach_storage and dspmap_reach_paths behave after it as after a plain
+ *    build (dspmap_reach_paths works if the build is time-invariant and is DSPMAP_E_STATE otherwise).  In addition it keeps R_n of every
+ *    step it executes, step 0 included: one row per step in the cast grid's layer layout, nz * ny * W words, bit x & 63 of word x >> 6,
+ *    bits at x >= nx are 0; rows [n_fields][max_steps + 1].
+ *  - one more argument check, after the existing ones and before the device is touched: n_fields * (max_steps + 1) * nz * ny * W * 8 bytes
+ *    above DSPMAP_REACH_TIMELINE_MAX_BYTES is DSPMAP_E_ARG with a text that names both numbers.  The cap is a condition, not a measurement:
+ *    a quarter of a percent of the card; a single field at the largest max_steps still fits on 132 x 132 x 60 (779 MB), the 64-field batch
+ *    on 66 x 66 x 40 (5 280 words a step) up to max_steps 396.
+ *  - early exit, last[f]: the wavefront stops a field early when its set is empty (it stays empty) or when a step changed nothing and the
+ *    layer never changes again.  last[f] is the last step the field executed; for n > last[f], R_n = R_last[f] -- for both exits, because
+ *    an extinguished field's last row is empty.  Rows behind last[f] are never written; dspmap_get_reach_sets serves a step in
+ *    (last[f], max_steps] from row last[f], a reader of dspmap_reach_timeline_device does the same with dspmap_reach_last_steps.
+ *  - dspmap_get_reach_sets copies n_steps rows from step first_step on.  DSPMAP_E_ARG: a `field` outside the build's fields,
+ *    first_step < 0, n_steps < 0, first_step + n_steps > max_steps + 1, a NULL output with n_steps > 0.
+ *  - timeline paths: start validity, frame, the steps_out codes (-3 invalid, -2 outside the map, -1 DSPMAP_REACH_UNREACHED) and the
+ *    max_len rules are those of dspmap_reach_paths; otherwise steps_out[i] = v, the start cell's first arrival.  cells_out[i * max_len + j]
+ *    is the cell occupied at step v - j; j = 0 is the start's cell.  Given cell c_j with v - j > 0, let P = R_{v-j-1} of the start's
+ *    field: c_{j+1} = c_j if c_j is in P (a wait), otherwise the FIRST face neighbour inside the map, in the order -x, +x, -y, +y, -z,
+ *    +z, that is in P.  One such neighbour always exists, because R_n is a subset of R_{n-1} u N6(R_{n-1}); should none qualify the path
+ *    stops and the rest is -1: no loop is unbounded.  The path has v + 1 cells, one per step; it ends in a free source cell at step 0 or
+ *    after max_len cells, and entries behind the end are -1.  Path flags other than DSPMAP_QUERY_WORLD are DSPMAP_E_ARG.
+ *  - consequence: on a time-invariant build the sets are monotone, a chosen cell's value is exactly v - j, so the path never waits and
+ *    equals dspmap_reach_paths' int for int.
+ *  - state: the timeline goes stale with everything that makes the arrival fields stale, and with every plain
+ *    dspmap_build_reach_fields*, which replaces the fields it belongs to.  On no timeline or a stale one the accessors and the paths are
+ *    DSPMAP_E_STATE with a text naming dspmap_build_reach_timeline, and dspmap_reach_timeline_device returns NULL.  A slab handle is
+ *    DSPMAP_E_STATE; without a device a valid build is DSPMAP_E_DEVICE.  READ-ONLY towards the map and the grid like the rest of the family.
+ *    The buffers are allocated by the first timeline build, grown by a larger one after the stream has drained, and freed with the device
+ *    state; a handle that never builds one allocates nothing.
+ *  - not offered: arriving at a chosen step instead of the first one, more than one workgroup per field, compressing waits out of a path. */
+#define DSPMAP_REACH_TIMELINE_MAX_BYTES (1ull << 30)
+/* grow the fields AND keep every step's set; synchronous */
+int dspmap_build_reach_timeline(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src_host, float t_start, float step_seconds,
+                                int max_steps, int flags);
+/* the same on a device array (src_dev: n_src x 16 B); enqueued on the handle's stream, no synchronisation */
+int dspmap_build_reach_timeline_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src_dev, float t_start,
+                                       float step_seconds, int max_steps, int flags);
+/* device address of the rows [n_fields][max_steps + 1][nz][ny][W] of the last timeline build; NULL if there is none or it is stale */
+const unsigned long long* dspmap_reach_timeline_device(dspmap_t* m);
+/* out_host[0 .. n_fields) = the last step each field of the last timeline build executed; synchronous */
+int dspmap_reach_last_steps(dspmap_t* m, int* out_host);
+/* out_host = n_steps rows of nz * ny * W words: R_first_step .. of one field; synchronous */
+int dspmap_get_reach_sets(dspmap_t* m, int field, int first_step, int n_steps, unsigned long long* out_host);
+/* paths of n starts backwards through the kept sets: steps_out[n], cells_out[n * max_len] (may be NULL when max_len == 0); synchronous */
+int dspmap_reach_timeline_paths(dspmap_t* m, int n, const dspmap_reach_point* start_host, int max_len, int flags, int* steps_out_host,
+                                int* cells_out_host);
+/* the same on device arrays; enqueued on the handle's stream (behind the build: the kernel boundary orders them), no synchronisation */
+int dspmap_reach_timeline_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start_dev, int max_len, int flags, int* steps_out_dev,
+                                       int* cells_out_dev);
 /* test hook: replace all L layers ([L][nz][ny][W] words) of the VALID cast grid.  A NULL pointer or a set bit at x >= nx is DSPMAP_E_ARG, no
  * valid grid DSPMAP_E_STATE.  The grid stays valid; arrival fields built before the call are stale.  Synchronous. */
 int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long* words_host);
