@@ -219,6 +219,7 @@ SIGNATURES = {
     "dspmap_debug_estimator_queue": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_frame_branches": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_resample_split_frames": (C.c_longlong, [_P]),
+    "dspmap_debug_plain_frames": (C.c_longlong, [_P]),
     "dspmap_debug_estimator_path": (_i, [_P]),
     "dspmap_debug_tile_count": (_i, [_P]),
     "dspmap_debug_tile_of_voxels": (_i, [_P, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -416,6 +417,10 @@ class DSPMap:
     def resample_split_frames(self):
         """frames whose resampling stage ran as two launches -- DSPMAP_P_RESAMPLE_SPLIT"""
         return int(self.L.dspmap_debug_resample_split_frames(self.h))
+
+    def plain_frames(self):
+        """frames queued as plain launches with their parameter block in the pinned ring -- DSPMAP_P_USE_GRAPH"""
+        return int(self.L.dspmap_debug_plain_frames(self.h))
 
     def estimator_path(self):
         """where the last device-estimator frame ran the estimator: 'own_stream', 'forked_shared_queue' (the fallback), 'forked', or None"""

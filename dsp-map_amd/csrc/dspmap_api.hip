@@ -179,7 +179,7 @@ extern "C" dspmap_t* dspmap_create(const dspmap_config* cfg) {
     m->vel.configure(cfg->half_fov_h, cfg->half_fov_v, cfg->angle_resolution);
     if (const char* e = getenv("DSPMAP_PLACE_SPLIT_TILES")) { const long v = atol(e); if (v > 0) m->place_split_tiles = (int)std::min(v, 2000000000l); }
     if (const char* e = getenv("DSPMAP_SWEEP_ALTERNATE")) m->sweep_alt = atoi(e) < 0 ? -1 : (atoi(e) >= 2 ? 2 : (atoi(e) != 0 ? 1 : 0));
-    if (const char* e = getenv("DSPMAP_USE_GRAPH")) { m->use_graph = atoi(e) == 1; m->direct_ring = atoi(e) == 2; }
+    if (const char* e = getenv("DSPMAP_USE_GRAPH")) { const int v = atoi(e); m->graph_mode = v >= 1 && v <= 3 ? v : 0; m->use_graph = m->graph_mode == 1 || m->graph_mode == 3; m->direct_ring = m->graph_mode == 2; }
     if (const char* e = getenv("DSPMAP_ESTIMATOR_QUEUE")) m->est_queue = atoi(e) != 0;
     if (const char* e = getenv("DSPMAP_XQ_TEST_DELAY_US")) m->xq_test_delay_us = std::max(0, std::min(atoi(e), 100000));
     m->xq_test_break = getenv("DSPMAP_XQ_TEST_BREAK") != nullptr;   // (test hooks are read HERE, once: never in a frame)
@@ -625,7 +625,9 @@ extern "C" int dspmap_set_param(dspmap_t* m, int key, double v) {
         case DSPMAP_P_VELOCITY_ESTIMATOR:
             if (v != 0 && v != 1 && v != 2) return dspmap_fail(m, DSPMAP_E_ARG, "velocity estimator: 0 off, 1 host stage, 2 device");
             m->use_vel_est = (int)v; break;
-        case DSPMAP_P_USE_GRAPH: m->use_graph = v == 1; m->direct_ring = v == 2; break;
+        case DSPMAP_P_USE_GRAPH:
+            m->graph_mode = (v == 1 || v == 2 || v == 3) ? (int)v : 0;   // (1: graph, or plain launches by map size; 2: plain launches; 3: graph; anything else: plain launches + copied parameters)
+            m->use_graph = v == 1 || v == 3; m->direct_ring = v == 2; break;
         case DSPMAP_P_HOST_CLOUD_DIRECT: m->host_direct = v != 0; break;
         case DSPMAP_P_ESTIMATOR_QUEUE:   // (part of the captured frame's key)
             m->est_queue = v != 0;
@@ -704,7 +706,7 @@ extern "C" double dspmap_get_param(const dspmap_t* m, int key) {
         case DSPMAP_P_VIEW_CHUNKS: return (float)m->vw_chunks;
         case DSPMAP_P_FRONTIER_MERGE: return m->fr_merge ? 1.f : 0.f;
         case DSPMAP_P_TILING: return m->d.tiling;
-        case DSPMAP_P_USE_GRAPH: return m->use_graph ? 1 : (m->direct_ring ? 2 : 0);
+        case DSPMAP_P_USE_GRAPH: return m->graph_mode;
         default: return 0;
     }
 }
@@ -2423,6 +2425,7 @@ extern "C" int dspmap_debug_frame_branches(dspmap_t* m, long long out[5]) {
     return DSPMAP_OK;
 }
 extern "C" long long dspmap_debug_resample_split_frames(dspmap_t* m) { return m ? m->rsplit_frames : 0; }
+extern "C" long long dspmap_debug_plain_frames(dspmap_t* m) { return m ? m->plain_frames : 0; }
 extern "C" int dspmap_get_pyramid_counts(dspmap_t* m, int* out) {
     READY(m);
     if (!out) return DSPMAP_E_ARG;

@@ -602,7 +602,16 @@ int dspmap_device_frame(dspmap* m, int n_points, const float* points_dev, int n_
     // kernels on one of its internal streams, profiles/r06_*_timeline*), and at this size (0.4 - 5 ms per frame) the ~0.1 ms of host time its
     // fifteen launches take is hidden behind the device
     const bool two = frame_runs_two_branches(m, c);
-    if (m->use_graph && !m->prof && !two) {
+    // A SMALL map's single-chain frame is queued as plain launches too, by default (DSPMAP_P_USE_GRAPH = 1; 3 keeps the graph): its frame is a
+    // serial chain of nine 7 - 29 us kernels, and a replayed linear graph ends with 8.7 us of nothing before the next replay's first kernel --
+    // as plain launches (same kernels, parameter block through the same ring, grids sized for the frame's cloud instead of the capacity)
+    // k_resample_wg's end is the next k_obs_points' start.  "Single chain": nothing but kernels on the handle's stream (no split placement, no
+    // second branch; the estimator on its own queue or absent).  "Small": fewer than DSPMAP_PLAIN_TILES tiles -- larger maps gain 1 % or
+    // lose.  NOT the host-pointer update(): its caller pays the launches' host time (~0.1 ms per frame when the queue
+    // is deep) in the loop that also copies the cloud, and has been measured host-bound that way; it keeps the one graph launch.
+    const bool chain = m->frame_ring && !two && !frame_splits_placement(m, c) && (mode != 2 || xq);
+    const bool plain_small = m->graph_mode == 1 && chain && c.k.ntiles < DSPMAP_PLAIN_TILES && !m->host_cloud;
+    if (m->use_graph && !m->prof && !two && !plain_small) {
         // the kernel arguments of a frame are constant (per-frame values live in s.fpar): capture once, replay
         const unsigned long long key = ((unsigned long long)m->graph_epoch << 8) | (has_vz ? 1u : 0u) | ((unsigned)mode << 1) | (c.sparse ? 8u : 0u) | (c.ro_inline ? 16u : 0u) | (xq ? 32u : 0u);
         const int gi = c.sweep_rev ? 1 : 0;   // (one executable graph per sweep direction: the direction is a kernel argument)
@@ -633,6 +642,7 @@ int dspmap_device_frame(dspmap* m, int n_points, const float* points_dev, int n_
         m->branch_pending = false;
         enqueue_frame(m, c, n_points, nb_grid, mode == 1, mode == 2);
         if (m->branch_pending) ++m->branch_frames;
+        if (m->frame_ring) ++m->plain_frames;
         if (m->rsplit_enq) ++m->rsplit_frames;
     }
     if (m->frame_ring) { rc = dspmap_ring_pushed(m); if (rc != DSPMAP_OK) return rc; }

@@ -12,6 +12,7 @@
 #define DSPMAP_PTS_RING 4  // pinned cloud staging buffers in rotation
 #define DSPMAP_RING 1024   // slots of the pinned frame-parameter ring (power of two)
 #define DSPMAP_XQ_LIST 65536   // workgroups of the first birth kernel the estimator queue's deferral list holds (DevState::xq; 16 birth sources each)
+#define DSPMAP_PLAIN_TILES 8192 // maps with fewer tiles queue their single-chain frames as plain launches by default (include/dspmap.h, DSPMAP_P_USE_GRAPH)
 #define DSPMAP_CLOUD_RING 64   // slots of the pinned, device-mapped CLOUD ring of the host-pointer update() (divides DSPMAP_RING)
 struct dspmap {
     dspmap_config cfg;
@@ -87,6 +88,9 @@ struct dspmap {
     // HIP graph of the device-resident frame (dspmap_update_device)
     bool use_graph = true;
     bool direct_ring = false;        // DSPMAP_P_USE_GRAPH = 2: plain launches, the frame's parameter block through the pinned ring like a replayed frame's
+    int graph_mode = 1;              // DSPMAP_P_USE_GRAPH as set (0 .. 3); use_graph = 1 or 3, direct_ring = 2.  1: a small map's single-chain frames go out as
+                                     // plain launches like 2's (dspmap_device_frame), everything else as the graph; 3: the graph wherever it can be used
+    long long plain_frames = 0;      // frames queued as plain launches with the parameter block through the ring (dspmap_debug_plain_frames)
     bool est_queue = true;           // DSPMAP_P_ESTIMATOR_QUEUE: the device estimator's kernels on a queue of their own, tied to the captured frame through xq_dev
     unsigned long long api_seq = 0;  // entry points called on this handle (READY; the harmless ones take themselves off again: BENIGN)
     unsigned long long xq_chain_api = ~0ull;   // api_seq of the last frame whose estimator ran on its own queue: when the next such frame is the very

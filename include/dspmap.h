@@ -112,11 +112,16 @@ enum dspmap_param {
                                        with the kernels (velocity_estimator.cpp); 0 = births use the caller's cloud, or tag every
                                        point in view as a static source */
     DSPMAP_P_REGENERATE_TABLES = 10,/* 1 = setPredictionVariance regenerates the Gaussian tables (:359) */
-    DSPMAP_P_USE_GRAPH = 11,        /* 1 (default) = dspmap_update / dspmap_update_device replay the frame as a captured HIP graph (one launch, ~18 us of host time per
-                                       frame); 2 = the same kernels as plain launches, parameter block through the same pinned ring: no graph boundary between two
-                                       frames (it costs 8.7 us on this runtime: 66x66x40 0.151 -> 0.144 ms, -4.4 .. -5.9 % in-process; larger maps +-1 %) but ~100 us of
-                                       host time per frame for its twelve launches (the host-pointer update() becomes host-bound: 4 800 frames/s), which is why it
-                                       is not the default; 0 = plain launches with a copied parameter block (rounds 1-2; what stage profiling uses).  Same result */
+    DSPMAP_P_USE_GRAPH = 11,        /* how dspmap_update / dspmap_update_device queue a frame.  2 = its kernels as plain launches, parameter block through the pinned
+                                       ring: no graph boundary between two frames (8.7 us on this runtime: 66x66x40 0.151 -> 0.142 ms) but twelve launches of host
+                                       time per frame (2.5 - 3 us each; ~100 us per frame once the caller runs hundreds of launches ahead of the device).  3 = the
+                                       frame replayed as a captured HIP graph wherever it can be captured (one launch, ~18 us of host time per frame).  1 (default) =
+                                       2 for the device-resident frames (dspmap_update_device, dspmap_update_depth*) of maps with fewer than 8 192 tiles of 64 voxels
+                                       whose chain is one stream's kernels (estimator on its own queue, or none; no split placement): A -4.4 %, B -5.8 % against
+                                       the graph in process -- and 3 for everything else: larger maps (132x132x60 filled by the depth stream -2 % with overlapping
+                                       ranges, 264x264x80 -0.8 %, saturated ones +0.4 % or never eligible) and every host-pointer dspmap_update, whose caller
+                                       would pay the launches (measured host-bound at 4 800 frames/s).  0 = plain launches with a copied parameter block (rounds
+                                       1-2; what stage profiling uses).  Same result whichever way, bit for bit */
     DSPMAP_P_OCCLUSION_MARGIN = 12, /* obstacle_thickness_for_occlusion :70 (0.3 m); the reference's two other headers use VOXEL_RESOLUTION */
     DSPMAP_P_UPDATE_TIME = 14,      /* read-only: update_time, the sum of the accepted frames' delt_t (:634) */
     DSPMAP_P_UPDATE_COUNTER = 15,   /* read-only: update_counter, the number of predictions run (:635) */
@@ -930,6 +935,9 @@ int dspmap_debug_estimator_path(dspmap_t* m);
 int dspmap_debug_frame_branches(dspmap_t* m, long long out[5]);
 /* frames of this handle whose resampling stage ran as two launches (DSPMAP_P_RESAMPLE_SPLIT) */
 long long dspmap_debug_resample_split_frames(dspmap_t* m);
+/* frames of this handle that were queued as plain launches with their parameter block in the pinned ring: every device-resident frame under
+ * DSPMAP_P_USE_GRAPH = 2, the small maps' single-chain frames (and two-branch frames) under the default */
+long long dspmap_debug_plain_frames(dspmap_t* m);
 /* test hooks of dspmap_mgpu_comm_init_from_env's rendezvous file (no device, no RCCL): what rank 0 publishes / what a rank != 0
  * waits for (this launch's nonce: DSPMAP_RDZV_NONCE or TORCHELASTIC_RUN_ID + the parent's pid).  1 = written / found, 0 = not */
 int dspmap_debug_rdzv_publish(const char* path, const char id[128]);
