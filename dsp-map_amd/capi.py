@@ -216,6 +216,8 @@ SIGNATURES = {
     "dspmap_debug_tile_view": (_i, [_P, C.POINTER(C.c_int), _i]),
     "dspmap_debug_rollout_paths": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_rollout_plan": (_i, [_P, _ip, _ip]),
+    "dspmap_debug_pair_items": (_i, [_P, _ip]),
+    "dspmap_debug_weight_variant": (_i, [_P]),
     "dspmap_debug_estimator_queue": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_frame_branches": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_resample_split_frames": (C.c_longlong, [_P]),
@@ -400,6 +402,16 @@ class DSPMap:
         cells = C.c_int()
         n = self._chk(self.L.dspmap_debug_rollout_plan(self.h, halo, C.byref(cells)))
         return [int(halo[t]) for t in range(n)], cells.value
+
+    def pair_items(self):
+        """(work items of k_ck_partial, work items of k_weight, particles per k_ck_partial item) of the last weight update"""
+        out = (C.c_int * 3)()
+        self._chk(self.L.dspmap_debug_pair_items(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def weight_variant(self):
+        """which k_weight the last weight update launched: 'mask' (every pair evaluated), 'skip' (far pairs branched over), or None"""
+        return {0: None, 1: "mask", 2: "skip"}.get(self.L.dspmap_debug_weight_variant(self.h))
 
     def estimator_queue(self):
         """(frames whose estimator ran on a queue of its own, hand-over word 0, hand-over word 1, give-ups, frames whose first birth kernel

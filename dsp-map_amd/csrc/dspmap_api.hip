@@ -482,7 +482,7 @@ extern "C" int dspmap_init_device(dspmap_t* m) {
     kernels_init_device();
     HIPCHK(m, dalloc(&k.omask, W));
     HIPCHK(m, hipMemset(k.omask, 0, sizeof(u64) * W));
-    HIPCHK(m, dalloc(&k.ck_items, (size_t)d.np * ((d.capp + 63) / 64 + 1)));
+    HIPCHK(m, dalloc(&k.ck_items, (size_t)d.np * ((d.capp + 31) / 32 + 1)));   // (items of 32 particles up to CK_SMALL_FOV in view: a small map with every list past 128 has more than capp / 64 + 1 per pyramid)
     HIPCHK(m, dalloc(&k.wu_items, (size_t)d.np * ((d.capp + 31) / 32 + 1)));
     HIPCHK(m, dalloc(&k.n_items, (size_t)4));
     HIPCHK(m, dalloc(&k.nb_tab, (size_t)d.np * NB_TAB_STRIDE));
@@ -2401,6 +2401,17 @@ extern "C" int dspmap_debug_rollout_paths(dspmap_t* m, long long out[3]) {
         for (size_t g = 0; g < ng; ++g) { out[1] += st[2 * g]; out[2] += st[2 * g + 1]; }
     }
     return DSPMAP_OK;
+}
+extern "C" int dspmap_debug_pair_items(dspmap_t* m, int out[3]) {
+    READY(m);
+    if (!out) return DSPMAP_E_ARG;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    HIPCHK(m, hipMemcpy(out, m->k.n_items, sizeof(int) * 3, hipMemcpyDeviceToHost));
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_debug_weight_variant(dspmap_t* m) {
+    if (!m) return DSPMAP_E_ARG;
+    return m->last_weight_variant;
 }
 extern "C" int dspmap_debug_rollout_plan(dspmap_t* m, int halo_out[DSPMAP_MAX_PRED_TIMES], int* lds_cells_out) {
     if (!m || !halo_out) return DSPMAP_E_ARG;   // (host state only: no device needed)

@@ -190,7 +190,7 @@ static void enqueue_frame(dspmap* m, LaunchCtx& c, int pts_grid, int birth_grid,
         launch_claim(c, early_birth ? birth_grid : 0, 0, 0, 0, -1, TILE_Q);
         launch_pyr_prepare(c);
         launch_ck_partial(c, true);
-        launch_weight_update(c);
+        m->last_weight_variant = launch_weight_update(c);
         if (with_est) {
             (void)hipStreamWaitEvent(m->stream, m->ev_join, 0);
             launch_birth_late(c, birth_grid, false, false);
@@ -288,7 +288,7 @@ static void enqueue_frame(dspmap* m, LaunchCtx& c, int pts_grid, int birth_grid,
     launch_ck_partial(c, split);
     side_place(0);
     dspmap_prof_mark(m, 4);
-    launch_weight_update(c);
+    m->last_weight_variant = launch_weight_update(c);
     dspmap_prof_mark(m, 5);
     if (with_est ? est_branch : split) (void)hipStreamWaitEvent(m->stream, m->ev_join, 0);   // the side stream's last kernel before the births
     if (!with_est && birth_grid <= 0) launch_ck_finalize(c);   // otherwise k_birth_rank reduces the 1/Ck sums (one launch less)
@@ -389,7 +389,7 @@ static int frame_with_host_stages(dspmap* m, int np, const float* pts_dev, const
     launch_setup_and_bin(c, np, false);
     launch_predict(c, true);
     launch_ck_partial(c);
-    launch_weight_update(c);
+    m->last_weight_variant = launch_weight_update(c);
     int nb = nb_static_grid;
     if (m->use_vel_est != 0 && !m->cfg.static_model) {
         if (pts_ready) HIPCHK(m, hipEventSynchronize(pts_ready));
@@ -839,7 +839,7 @@ extern "C" int dspmap_stage_update(dspmap_t* m) {
     dspmap_snapshots_stale(m);
     LaunchCtx c = dspmap_ctx_of(m);
     launch_ck_partial(c);
-    launch_weight_update(c);
+    m->last_weight_variant = launch_weight_update(c);
     launch_ck_finalize(c);
     HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;

@@ -148,6 +148,7 @@ struct dspmap {
                                      // on the side stream, beside the pair kernels (DSPMAP_P_PLACE_SPLIT_TILES)
     int resample_wg_tiles = 8192;    // one-word maps with fewer tiles (and sparse ones of any size) run the four-waves-per-tile resampler (DSPMAP_P_RESAMPLE_WG_TILES)
     int last_resample_variant = 0;   // resample_variant() of the last frame / stage (dspmap_debug_rollout_paths)
+    int last_weight_variant = 0;     // what launch_weight_update returned for the last frame / stage (dspmap_debug_weight_variant)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec[2] = {nullptr, nullptr};   // the captured frame, one per sweep direction (LaunchCtx::sweep_rev is a kernel argument)
     unsigned long long graph_key[2] = {~0ull, ~0ull};

@@ -26,9 +26,9 @@ struct KernelScratch {
     int* part_resample; // [ntiles rounded up to 4] live particles per tile after resampling
     int* vb_cnt;        // [v_loc] children per destination voxel this frame (birth ordering)
     int* vb_idx;        // [v_loc*128] their birth indices
-    int* ck_items;      // [np * ceil(capp/128)] work items of k_ck_partial (pyramid<<12 | chunk)
+    int* ck_items;      // [np * (ceil(capp/32)+1)] work items of k_ck_partial (pyramid<<12 | chunk)
     int* wu_items;      // [np * (ceil(capp/256)+1)] work items of k_weight
-    int* n_items;       // [2]
+    int* n_items;       // [3] Ck items, weight items, particles per Ck item (dspmap_debug_pair_items)
     int* nb_tab;        // [NB_TAB_STRIDE][np] neighbourhood of every pyramid: bins (h-major, -1 padded) + exclusive offsets of
                         // their observation counts, written by k_pyr_items once per frame
     int* part_birth;    // [ceil(birth_cap*32/256)*2] per-block {born, dropped} of k_birth_insert
@@ -110,7 +110,7 @@ void launch_pyr_kept(const LaunchCtx& c, const int* kstar, int* kept);   // afte
 void launch_pyr_prepare(const LaunchCtx& c);   // range sort + full-list selection of the pyramid lists, work items (idempotent)
 void launch_ck_partial(const LaunchCtx& c, bool prepared = false, bool with_fix = true);   // with_fix: the first workgroups run k_place_fix's pass     // launch_pyr_prepare (unless already queued) + the Ck pass
 void launch_ck_finalize(const LaunchCtx& c);
-void launch_weight_update(const LaunchCtx& c);
+int launch_weight_update(const LaunchCtx& c);   // returns which k_weight it launched: 1 = <false> (every pair evaluated, far ones masked), 2 = <true> (far pairs branched over)
 // mapAddNewBornParticlesByObservation (:796-921)
 void launch_birth(const LaunchCtx& c, int n_birth, bool in_frame, bool all_static);  // in_frame: between k_weight and k_resample of a whole frame
 void launch_birth_split(const LaunchCtx& c, int n_birth);

@@ -1634,11 +1634,12 @@ void launch_ck_partial(const LaunchCtx& c, bool prepared, bool with_fix) {
 void launch_ck_finalize(const LaunchCtx& c) {  // after launch_weight_update: reduces the per-pyramid 1/Ck sums
     hipLaunchKernelGGL(k_ck_sum, dim3(1), dim3(512), 0, c.stream, c.d, c.s, c.fp);
 }
-void launch_weight_update(const LaunchCtx& c) {  // after launch_ck_partial (which also builds the item lists)
+int launch_weight_update(const LaunchCtx& c) {  // after launch_ck_partial (which also builds the item lists); returns the instantiation it launched
     const bool skip = weight_culls(c);
     const size_t lds = (sizeof(float4) + sizeof(float)) * (size_t)c.d.nbins * DSP_OBS_CAP;
     if (skip) hipLaunchKernelGGL(k_weight<true>, dim3(4096), dim3(WU_TPB), lds, c.stream, c.d, c.s, c.fp, c.k.wu_items, c.k.n_items, c.k.nb_tab);
     else hipLaunchKernelGGL(k_weight<false>, dim3(4096), dim3(WU_TPB), lds, c.stream, c.d, c.s, c.fp, c.k.wu_items, c.k.n_items, c.k.nb_tab);
+    return skip ? 2 : 1;
 }
 
 // n_birth_grid sizes the launches (>= the frame's n_birth, which the kernels read from FrameParams)

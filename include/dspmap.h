@@ -914,6 +914,14 @@ int dspmap_debug_tile_moving(dspmap_t* m, int* out, int cap);
  * out[0] = bit 0: four-waves-per-tile resampler; bits 1-2: rollout 0 inside the resampler, 1 k_rollout without LDS windows,
  * 2 k_rollout with LDS windows, 3 none; out[1] / out[2] = contributions k_rollout sent through its windows / as single atomics */
 int dspmap_debug_rollout_paths(dspmap_t* m, long long out[3]);
+/* diagnostics: the work items the last weight update (a frame's or dspmap_stage_update's) was split into: out[0] = items of k_ck_partial
+ * (chunks of out[2] particles of the lists of pyramids with an observation in their neighbourhood), out[1] = items of k_weight
+ * (256 / lanes-per-particle particles each, at least one per pyramid), out[2] = particles per k_ck_partial item (32 or 64).  Syncs */
+int dspmap_debug_pair_items(dspmap_t* m, int out[3]);
+/* which instantiation of k_weight the last weight update launched: 1 = every pair of a neighbourhood evaluated and the far ones masked,
+ * 2 = only the observations within range of the item staged and far pairs branched over (maps whose corner is farther than 12 cull
+ * radii), 0 = none yet.  Both add the same terms (DSPMAP_P_PAIR_CULL_SIGMAS) */
+int dspmap_debug_weight_variant(dspmap_t* m);
 /* diagnostics: the window plan k_rollout gets on this handle (a function of the configuration and the storage order alone; no device
  * needed): halo_out[t] = rows of the grid horizon t's LDS window reaches beyond its group of tiles, either side (-1 past the last
  * horizon), *lds_cells_out = 32-bit cells of all windows together (may be NULL).  All halos 0 = the collapsed plan of a grid too wide

@@ -150,6 +150,23 @@ def test_parameter_ids_of_the_binding_match_the_header(dsp):
     m.close()
 
 
+def test_pair_path_readbacks_are_declared_bound_and_check_their_arguments(dsp):
+    """dspmap_debug_pair_items / dspmap_debug_weight_variant (which pair-kernel path the last weight update took): in the header, in the
+    binding, NULL handles and NULL outputs are argument errors, and a handle that has not run a weight update reports no variant"""
+    assert {"dspmap_debug_pair_items", "dspmap_debug_weight_variant"} <= set(declared_symbols()) & set(dsp.capi.SIGNATURES)
+    L = dsp.load_library()
+    out = (C.c_int * 3)()
+    assert L.dspmap_debug_pair_items(None, out) == -1 and L.dspmap_debug_weight_variant(None) == -1
+    m = dsp.DSPMap(dsp.make_config(ppv=24))
+    assert m.weight_variant() is None
+    import torch
+    if torch.cuda.is_available():
+        assert L.dspmap_debug_pair_items(m.h, None) == -1
+    else:
+        assert L.dspmap_debug_pair_items(m.h, out) < 0 and b"no HIP device" in L.dspmap_last_error(m.h)
+    m.close()
+
+
 def test_rendezvous_file_is_matched_by_its_nonce_string(dsp, tmp_path, monkeypatch):
     """dspmap_mgpu_comm_init_from_env (the drop-in class's sharded start-up, -DDSPMAP_WORLD): a rank != 0 accepts exactly the record
     whose nonce STRING is this launch's -- whatever follows the string's NUL in the 120-byte field (rank 0's stack residue before
