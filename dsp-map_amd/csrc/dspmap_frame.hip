@@ -813,7 +813,7 @@ extern "C" int dspmap_stage_bin_points(dspmap_t* m, int n, int stride, const flo
 extern "C" int dspmap_set_current_position(dspmap_t* m, float x, float y, float z) {
     if (!m) return DSPMAP_E_ARG;
     m->cur_pos[0] = x; m->cur_pos[1] = y; m->cur_pos[2] = z;
-    m->fr_valid = false;   // (frontiers are found in the known-space window of the position they were built at)
+    dspmap_layers_stale(m->ly, LAYERS_POSITION_CHANGED);   // (frontiers are found in the known-space window of the position they were built at)
     return DSPMAP_OK;
 }
 extern "C" int dspmap_stage_predict(dspmap_t* m, float dx, float dy, float dz, float dt) {

@@ -1,7 +1,8 @@
-// dspmap_internal.h -- the handle behind dspmap_t and helpers shared by dspmap_api.hip / dspmap_frame.hip / dspmap_mgpu.hip
+// dspmap_internal.h -- the handle behind dspmap_t and helpers shared by dspmap_api.hip / dspmap_layers.hip / dspmap_frame.hip / dspmap_mgpu.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -14,6 +15,94 @@
 #define DSPMAP_XQ_LIST 65536   // workgroups of the first birth kernel the estimator queue's deferral list holds (DevState::xq; 16 birth sources each)
 #define DSPMAP_PLAIN_TILES 8192 // maps with fewer tiles queue their single-chain frames as plain launches by default (include/dspmap.h, DSPMAP_P_USE_GRAPH)
 #define DSPMAP_CLOUD_RING 64   // slots of the pinned, device-mapped CLOUD ring of the host-pointer update() (divides DSPMAP_RING)
+// the planning layers' host state (dspmap_layers.hip): staging, snapshots of the map and the known-space layer
+struct LayerState {
+    // point / trajectory queries (dspmap_query_occupancy*, dspmap_trajectory_risk*): device staging of the host variants' samples and
+    // results and of the risk's per-sample values; grown on demand (after the stream has drained), freed with the device state
+    void* q_buf = nullptr; size_t q_buf_bytes = 0;
+    // distance fields (dspmap_build_distance_field): the field [L][V] and the two passes' scratch, allocated by the first build, freed with the
+    // device state.  df_valid: the field is a snapshot of the map as it is -- cleared by everything that computes a frame or replaces state
+    float* df_field = nullptr; unsigned char* df_g8 = nullptr; unsigned short* df_h16 = nullptr;
+    bool df_valid = false;
+    // cast grid (dspmap_build_cast_grid): one bit per voxel, [L][nz][ny][W] words, and the inflation's scratch grid of the same size; allocated
+    // by the first build, freed with the device state.  cg_valid: the life cycle of df_valid (dspmap_snapshots_stale)
+    u64* cg_bits = nullptr; u64* cg_tmp = nullptr;
+    bool cg_valid = false;
+    // arrival-time fields (dspmap_build_reach_fields): the values [rf_n][V] uint16 and, where the wave sets do not fit in LDS, their device
+    // scratch [rf_n][2][nz * ny * W]; allocated (and grown) by a build, freed with the device state.  rf_valid: a snapshot of the cast grid --
+    // cleared with cg_valid, by every dspmap_build_cast_grid and by dspmap_debug_set_cast_grid
+    unsigned short* rf_field = nullptr; size_t rf_field_cells = 0;
+    u64* rf_sets = nullptr; size_t rf_sets_words = 0;
+    bool rf_valid = false;
+    int rf_n = 0;                    // fields of the last build
+    bool rf_invariant = false;       // ... whose tested layer never changed: paths exist
+    long long rf_storage[2] = {0, 0};   // ... whose sets lived in LDS / in device memory (dspmap_debug_reach_storage)
+    // their timeline (dspmap_build_reach_timeline): every step's set [rf_n][tl_max_steps + 1][nz * ny * W] and the last step each field
+    // executed [DSPMAP_REACH_MAX_FIELDS]; allocated by the first timeline build (grown by a larger one), freed with the device state.
+    // tl_valid: the fields of the last build came with a timeline -- cleared wherever rf_valid is, and by every plain build
+    u64* tl_hist = nullptr; size_t tl_hist_words = 0;
+    int* tl_last = nullptr;
+    bool tl_valid = false;
+    int tl_max_steps = 0;            // max_steps of the build that wrote it
+    // occupancy forecast (dspmap_build_forecast): the layers [fc_n][V] floats and the sweep's accumulators [fc_n + 1][v_loc] (the moving
+    // particles' per layer, then the static sums); allocated (and grown) by a build, freed with the device state.  fc_valid: the life cycle
+    // of df_valid (dspmap_snapshots_stale)
+    float* fc_field = nullptr; u64* fc_acc = nullptr; int fc_cap = 0;   // fc_cap: layers the two buffers hold
+    bool fc_valid = false;
+    int fc_n = 0;                    // layers of the last build ...
+    float fc_t[DSPMAP_FORECAST_MAX_TIMES] = {};   // ... and their times
+    // known-space layer (dspmap_known_integrate): one stamp per world lattice cell of the window, toroidal slots [nz][ny][nx]; allocated by the
+    // first integration, freed with the device state.  NOT a snapshot: it lives through frames.  kn_k0: the window (lattice index of map
+    // voxel 0 per axis) the slots were last synchronised to -- every entry point synchronises before it reads or writes (dspmap_known_sync
+    // in dspmap_layers.hip); kn_integrated: some frame has been integrated since the layer was last reset
+    unsigned* kn_stamp = nullptr;
+    long long kn_k0[3] = {0, 0, 0};
+    bool kn_integrated = false;
+    // viewpoint scores (dspmap_score_views): the unrotated central direction of every pyramid, [np][3]; uploaded by the first call, freed
+    // with the device state.  vw_chunks: DSPMAP_P_VIEW_CHUNKS
+    float* vw_dirs0 = nullptr;
+    int vw_chunks = 0;
+    // frontiers (dspmap_build_frontiers): the bit grid [nz][ny][W], the cell list [V], the counts {n_cells, n_blocks, n_free} and the
+    // per-word free counts, allocated by the first build; the blocks' accumulators and records [fr_nb_cap] each and the compaction's tile
+    // scratch, allocated by the first build and again when a smaller block needs more; all freed with the device state.  fr_valid: a
+    // snapshot of the cast grid AND of the known-space layer -- cleared with cg_valid (dspmap_snapshots_stale), by every call that changes
+    // the grid or the layer, and by dspmap_set_current_position
+    u64* fr_grid = nullptr; int* fr_cells = nullptr; long long* fr_counts = nullptr; int* fr_item_free = nullptr;
+    dspmap_frontier_block* fr_dense = nullptr; dspmap_frontier_block* fr_blocks = nullptr; int* fr_tiles = nullptr;
+    size_t fr_nb_cap = 0;
+    bool fr_valid = false;
+    bool fr_merge = true;            // DSPMAP_P_FRONTIER_MERGE
+};
+// What a change makes stale.  The snapshots depend on each other like this:
+//     map -> distance field, forecast, cast grid;   cast grid -> arrival fields, frontiers;   arrival fields -> timeline;
+//     known-space layer -> frontiers;               position -> frontiers
+// LAYERS_x_CHANGED: x has changed under the snapshots taken of it.  LAYERS_x_REBUILD: a build of x starts -- x itself is stale too, until the
+// build sets its flag behind its launch.  dspmap_layers_stale is the ONLY place that clears a *_valid flag, so a reader tests its own flag alone.
+enum LayerChange {
+    LAYERS_MAP_CHANGED,         // a frame, or state replaced (dspmap_snapshots_stale)
+    LAYERS_CAST_GRID_REBUILD,
+    LAYERS_CAST_GRID_CHANGED,   // masked or replaced in place: the grid itself stays valid
+    LAYERS_REACH_REBUILD,       // with or without a timeline: the build that keeps one sets tl_valid again
+    LAYERS_KNOWN_CHANGED,
+    LAYERS_POSITION_CHANGED,
+    LAYERS_FRONTIERS_REBUILD,
+    LAYERS_DISTANCE_REBUILD,
+    LAYERS_FORECAST_REBUILD
+};
+inline void dspmap_layers_stale(LayerState& l, LayerChange c) {
+    switch (c) {   // (the first four cases are one chain: each falls through to what depends on it)
+    case LAYERS_MAP_CHANGED: l.df_valid = false; l.fc_valid = false; [[fallthrough]];
+    case LAYERS_CAST_GRID_REBUILD: l.cg_valid = false; [[fallthrough]];
+    case LAYERS_CAST_GRID_CHANGED: l.fr_valid = false; [[fallthrough]];
+    case LAYERS_REACH_REBUILD: l.rf_valid = false; l.tl_valid = false; break;
+    case LAYERS_KNOWN_CHANGED:
+    case LAYERS_POSITION_CHANGED:
+    case LAYERS_FRONTIERS_REBUILD: l.fr_valid = false; break;
+    case LAYERS_DISTANCE_REBUILD: l.df_valid = false; break;
+    case LAYERS_FORECAST_REBUILD: l.fc_valid = false; break;
+    }
+}
+
 struct dspmap {
     dspmap_config cfg;
     MapDims d;
@@ -176,61 +265,7 @@ struct dspmap {
     int* mgpu_count = nullptr;
     BirthSrc* mgpu_birth = nullptr;
     int last_exp[2] = {0, 0};   // particles exported down / up in the last frame
-    // point / trajectory queries (dspmap_query_occupancy*, dspmap_trajectory_risk*): device staging of the host variants' samples and
-    // results and of the risk's per-sample values; grown on demand (after the stream has drained), freed with the device state
-    void* q_buf = nullptr; size_t q_buf_bytes = 0;
-    // distance fields (dspmap_build_distance_field): the field [L][V] and the two passes' scratch, allocated by the first build, freed with the
-    // device state.  df_valid: the field is a snapshot of the map as it is -- cleared by everything that computes a frame or replaces state
-    float* df_field = nullptr; unsigned char* df_g8 = nullptr; unsigned short* df_h16 = nullptr;
-    bool df_valid = false;
-    // cast grid (dspmap_build_cast_grid): one bit per voxel, [L][nz][ny][W] words, and the inflation's scratch grid of the same size; allocated
-    // by the first build, freed with the device state.  cg_valid: the life cycle of df_valid (dspmap_snapshots_stale)
-    u64* cg_bits = nullptr; u64* cg_tmp = nullptr;
-    bool cg_valid = false;
-    // arrival-time fields (dspmap_build_reach_fields): the values [rf_n][V] uint16 and, where the wave sets do not fit in LDS, their device
-    // scratch [rf_n][2][nz * ny * W]; allocated (and grown) by a build, freed with the device state.  rf_valid: a snapshot of the cast grid --
-    // cleared with cg_valid, by every dspmap_build_cast_grid and by dspmap_debug_set_cast_grid
-    unsigned short* rf_field = nullptr; size_t rf_field_cells = 0;
-    u64* rf_sets = nullptr; size_t rf_sets_words = 0;
-    bool rf_valid = false;
-    int rf_n = 0;                    // fields of the last build
-    bool rf_invariant = false;       // ... whose tested layer never changed: paths exist
-    long long rf_storage[2] = {0, 0};   // ... whose sets lived in LDS / in device memory (dspmap_debug_reach_storage)
-    // their timeline (dspmap_build_reach_timeline): every step's set [rf_n][tl_max_steps + 1][nz * ny * W] and the last step each field
-    // executed [DSPMAP_REACH_MAX_FIELDS]; allocated by the first timeline build (grown by a larger one), freed with the device state.
-    // tl_valid: the fields of the last build came with a timeline -- cleared wherever rf_valid is, and by every plain build
-    u64* tl_hist = nullptr; size_t tl_hist_words = 0;
-    int* tl_last = nullptr;
-    bool tl_valid = false;
-    int tl_max_steps = 0;            // max_steps of the build that wrote it
-    // occupancy forecast (dspmap_build_forecast): the layers [fc_n][V] floats and the sweep's accumulators [fc_n + 1][v_loc] (the moving
-    // particles' per layer, then the static sums); allocated (and grown) by a build, freed with the device state.  fc_valid: the life cycle
-    // of df_valid (dspmap_snapshots_stale)
-    float* fc_field = nullptr; u64* fc_acc = nullptr; int fc_cap = 0;   // fc_cap: layers the two buffers hold
-    bool fc_valid = false;
-    int fc_n = 0;                    // layers of the last build ...
-    float fc_t[DSPMAP_FORECAST_MAX_TIMES] = {};   // ... and their times
-    // known-space layer (dspmap_known_integrate): one stamp per world lattice cell of the window, toroidal slots [nz][ny][nx]; allocated by the
-    // first integration, freed with the device state.  NOT a snapshot: it lives through frames.  kn_k0: the window (lattice index of map
-    // voxel 0 per axis) the slots were last synchronised to -- every entry point synchronises before it reads or writes (dspmap_known_sync
-    // in dspmap_api.hip); kn_integrated: some frame has been integrated since the layer was last reset
-    unsigned* kn_stamp = nullptr;
-    long long kn_k0[3] = {0, 0, 0};
-    bool kn_integrated = false;
-    // viewpoint scores (dspmap_score_views): the unrotated central direction of every pyramid, [np][3]; uploaded by the first call, freed
-    // with the device state.  vw_chunks: DSPMAP_P_VIEW_CHUNKS
-    float* vw_dirs0 = nullptr;
-    int vw_chunks = 0;
-    // frontiers (dspmap_build_frontiers): the bit grid [nz][ny][W], the cell list [V], the counts {n_cells, n_blocks, n_free} and the
-    // per-word free counts, allocated by the first build; the blocks' accumulators and records [fr_nb_cap] each and the compaction's tile
-    // scratch, allocated by the first build and again when a smaller block needs more; all freed with the device state.  fr_valid: a
-    // snapshot of the cast grid AND of the known-space layer -- cleared with cg_valid (dspmap_snapshots_stale), by every call that changes
-    // the grid or the layer, and by dspmap_set_current_position
-    u64* fr_grid = nullptr; int* fr_cells = nullptr; long long* fr_counts = nullptr; int* fr_item_free = nullptr;
-    dspmap_frontier_block* fr_dense = nullptr; dspmap_frontier_block* fr_blocks = nullptr; int* fr_tiles = nullptr;
-    size_t fr_nb_cap = 0;
-    bool fr_valid = false;
-    bool fr_merge = true;            // DSPMAP_P_FRONTIER_MERGE
+    LayerState ly;                   // the planning layers' host state (dspmap_layers.hip)
     // cloud pre-processing scratch (dspmap_preprocess.hip)
     void* pp_box = nullptr;
     void* pp_acc = nullptr;
@@ -259,9 +294,11 @@ struct dspmap {
 
 // everything that computes a frame or replaces state calls this: the distance field, the cast grid, the arrival fields grown in it, the
 // frontiers found in it and the forecast are snapshots of the map before it
-inline void dspmap_snapshots_stale(dspmap* m) {
-    m->df_valid = false; m->cg_valid = false; m->rf_valid = false; m->tl_valid = false; m->fc_valid = false; m->fr_valid = false;
-}
+inline void dspmap_snapshots_stale(dspmap* m) { dspmap_layers_stale(m->ly, LAYERS_MAP_CHANGED); }
+// dspmap_layers.hip: everything the known-space layer holds forgotten (a new state: dspmap_clear_state, dspmap_load_checkpoint), and the
+// layers' device buffers released (free_dev; chk reports a failed call)
+int dspmap_known_forget(dspmap* m);
+void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const char*)>& chk);
 int dspmap_fail(dspmap* m, int code, const char* fmt, ...);
 void dspmap_prof_mark(dspmap* m, int i);
 void dspmap_prof_collect(dspmap* m);

@@ -1,0 +1,1222 @@
+// dspmap_layers.hip -- host side of the planning layers that read the map: point and trajectory queries, distance fields, the cast grid with
+// segment casts and free boxes, arrival-time fields with timeline and paths, the forecast, the known-space layer, view scores and frontiers.
+// Their kernels are in a file each (named per section); their state is LayerState (dspmap_internal.h), and what makes a snapshot stale is
+// decided in ONE place, dspmap_layers_stale next to it.  An entry point that takes host arrays is: check -> stage -> enqueue -> read back,
+// around the same *_enqueue its _device twin calls.  Checks fire in this order: arguments, slab and state, then the device.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
+#include "dspmap_internal.h"
+
+// --------------------------------------------------- checks and argument fills every layer repeats
+// these layers need the whole map: `why` is the layer's own sentence (may be empty)
+static int whole_map_check(dspmap* m, const char* what, const char* why) {
+    if (m->d.z_lo != 0 || m->d.z_hi != m->d.nz)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: a slab handle holds part of the map%s%s", what, *why ? "; " : "", why);
+    return DSPMAP_OK;
+}
+// n items (`noun`) in one array, as many results in another
+static int samples_check(dspmap* m, const char* what, const char* noun, long long n, const void* in, const void* out) {
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative %s count %lld", what, noun, n);
+    if (n > 0 && (!in || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL %s or output array", what, noun);
+    return DSPMAP_OK;
+}
+static int flags_check(dspmap* m, const char* what, int flags, int allowed) {
+    if (flags & ~allowed) return dspmap_fail(m, DSPMAP_E_ARG, "%s: unknown flags 0x%x", what, flags);
+    return DSPMAP_OK;
+}
+// a snapshot's readers: stale or never built is a state error with the layer's sentence `missing`; the handle's device is made current
+// (these entry points queue work without going through READY)
+static int snapshot_ready(dspmap* m, bool valid, const char* what, const char* missing) {
+    if (!valid) return dspmap_fail(m, DSPMAP_E_STATE, "%s: %s", what, missing);
+    if (m->device >= 0) (void)hipSetDevice(m->device);
+    return DSPMAP_OK;
+}
+// the origin of the samples' coordinates: the sensor position of the last update when DSPMAP_QUERY_WORLD is set (QueryArgs::ox)
+// (every kernel argument block that takes samples starts with this quartet; the blocks are separate types, hence the template)
+template <class Args> static void origin_fill(const dspmap* m, int flags, Args* a) {
+    a->world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
+    a->ox = m->cur_pos[0]; a->oy = m->cur_pos[1]; a->oz = m->cur_pos[2];
+}
+
+// --------------------------------------------------- staging of the host variants' arrays (LayerState::q_buf)
+static size_t q_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// the handle's query staging: at least `bytes`; grown only after the stream has drained (an earlier query may still use it)
+static int query_buf(dspmap* m, size_t bytes) {
+    if (bytes <= m->ly.q_buf_bytes) return DSPMAP_OK;
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    if (m->ly.q_buf) { HIPCHK(m, hipFree(m->ly.q_buf)); m->ly.q_buf = nullptr; m->ly.q_buf_bytes = 0; }
+    const size_t cap = bytes + bytes / 2;
+    HIPCHK(m, hipMalloc(&m->ly.q_buf, cap));
+    m->ly.q_buf_bytes = cap;
+    return DSPMAP_OK;
+}
+// one section of the staging buffer, 256-byte aligned: `in` is copied into it before the launches, it is copied to `out` behind them; either
+// may be NULL (scratch, or an output the caller did not ask for).  dev: where it lies, NULL for a section of no bytes
+struct StageSec { const void* in; void* out; size_t bytes; void* dev; };
+// reserves the sections in their order, grows the buffer and queues the copies in
+static int stage_begin(dspmap* m, StageSec* s, int n_sec) {
+    size_t end = 0;
+    for (int i = 0; i < n_sec; ++i) if (s[i].bytes) end = q_align(end) + s[i].bytes;
+    const int rc = query_buf(m, end);
+    if (rc != DSPMAP_OK) return rc;
+    end = 0;
+    for (int i = 0; i < n_sec; ++i) {
+        s[i].dev = nullptr;
+        if (!s[i].bytes) continue;
+        s[i].dev = (char*)m->ly.q_buf + q_align(end);
+        end = q_align(end) + s[i].bytes;
+        if (s[i].in) HIPCHK(m, hipMemcpyAsync(s[i].dev, s[i].in, s[i].bytes, hipMemcpyHostToDevice, m->stream));
+    }
+    return DSPMAP_OK;
+}
+// a result the device already holds: copied out, and the stream waited for
+static int read_back(dspmap* m, void* out, const void* dev, size_t bytes) {
+    HIPCHK(m, hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+// queues the copies out in the sections' order and waits for the stream
+static int stage_end(dspmap* m, const StageSec* s, int n_sec) {
+    for (int i = 0; i < n_sec; ++i)
+        if (s[i].bytes && s[i].out) HIPCHK(m, hipMemcpyAsync(s[i].out, s[i].dev, s[i].bytes, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+
+// --------------------------------------------------- point / trajectory queries (dspmap_query.hip; semantics in include/dspmap.h)
+// argument checks of every query entry point: before READY, so that they hold without a device
+static int query_check(dspmap* m, long long n, const void* in, const void* out, float r, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, "query", "sample", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if (!(r >= 0.f && r <= 8.f * m->d.res)) return dspmap_fail(m, DSPMAP_E_ARG, "query: radius %g outside [0, 8 * voxel_resolution]", (double)r);
+    if ((rc = flags_check(m, "query", flags, DSPMAP_QUERY_WORLD)) != DSPMAP_OK) return rc;
+    if (outside != outside) return dspmap_fail(m, DSPMAP_E_ARG, "query: outside_value is NaN");
+    return DSPMAP_OK;
+}
+static QueryArgs query_args(const dspmap* m, float r, int flags, float outside) {
+    const MapDims& d = m->d;
+    QueryArgs a;
+    origin_fill(m, flags, &a);
+    a.r2 = r * r;
+    a.K = r > 0.f ? (int)ceilf(r / d.res) + 1 : 0;   // (a superset of the footprint: one lattice step of margin for the rounding)
+    a.outside = outside;
+    a.fut_zero = m->fut_clear_pending ? 1 : 0;       // read, never changed: the clear stays with the next frame / reader
+    a.cx = -d.half_x + d.res * 0.5f; a.cy = -d.half_y + d.res * 0.5f; a.cz = -d.half_z + d.res * 0.5f;   // dspmap_voxel_center
+    return a;
+}
+static int risk_check(dspmap* m, int n_traj, int n_samples, const void* in, const void* out, float r, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n_traj < 0) return dspmap_fail(m, DSPMAP_E_ARG, "trajectory risk: negative trajectory count %d", n_traj);
+    if (n_traj > 0 && n_samples <= 0) return dspmap_fail(m, DSPMAP_E_ARG, "trajectory risk: %d samples per trajectory", n_samples);
+    const long long n = (long long)n_traj * (n_traj > 0 ? n_samples : 0);
+    if (n > 0x7fffffffll) return dspmap_fail(m, DSPMAP_E_ARG, "trajectory risk: %d x %d samples exceed INT_MAX", n_traj, n_samples);
+    const int rc = query_check(m, n, in, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    return whole_map_check(m, "trajectory risk", "query every slab and merge with max");
+}
+
+static int query_enqueue(dspmap* m, int n, const float4* dq, float r, int flags, float outside, float* dout) {
+    launch_query(dspmap_ctx_of(m), query_args(m, r, flags, outside), n, dq, dout, nullptr);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_occupancy(dspmap_t* m, int n, const dspmap_query* q, float r, int flags, float outside, float* out) {
+    int rc = query_check(m, n, q, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[2] = {{q, nullptr, sizeof(dspmap_query) * (size_t)n}, {nullptr, out, sizeof(float) * (size_t)n}};
+    if ((rc = stage_begin(m, s, 2)) != DSPMAP_OK) return rc;
+    if ((rc = query_enqueue(m, n, (const float4*)s[0].dev, r, flags, outside, (float*)s[1].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 2);
+}
+extern "C" int dspmap_query_occupancy_device(dspmap_t* m, int n, const dspmap_query* q, float r, int flags, float outside, float* out) {
+    const int rc = query_check(m, n, q, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    return query_enqueue(m, n, (const float4*)q, r, flags, outside, out);
+}
+// values + flags of the n_traj x n_samples samples in the staging buffer at `vals`, then one dspmap_risk per trajectory into `out`
+static int risk_enqueue(dspmap* m, int n_traj, int n_samples, const float4* dq, float* vals, float r, int flags, float outside,
+                        float thr, dspmap_risk* out) {
+    const int n = n_traj * n_samples;
+    const LaunchCtx c = dspmap_ctx_of(m);
+    unsigned char* fl = (unsigned char*)((char*)vals + q_align(sizeof(float) * (size_t)n));
+    launch_query(c, query_args(m, r, flags, outside), n, dq, vals, fl);
+    launch_risk_reduce(c, n_traj, n_samples, vals, fl, thr, out);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+static size_t risk_scratch_bytes(long long n) { return q_align(sizeof(float) * (size_t)n) + q_align((size_t)n); }
+extern "C" int dspmap_trajectory_risk(dspmap_t* m, int n_traj, int n_samples, const dspmap_query* q, float r, int flags, float outside,
+                                      float thr, dspmap_risk* out) {
+    int rc = risk_check(m, n_traj, n_samples, q, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n_traj == 0) return DSPMAP_OK;
+    const int n = n_traj * n_samples;
+    StageSec s[3] = {{q, nullptr, sizeof(dspmap_query) * (size_t)n}, {nullptr, nullptr, risk_scratch_bytes(n)},
+                     {nullptr, out, sizeof(dspmap_risk) * (size_t)n_traj}};
+    if ((rc = stage_begin(m, s, 3)) != DSPMAP_OK) return rc;
+    if ((rc = risk_enqueue(m, n_traj, n_samples, (const float4*)s[0].dev, (float*)s[1].dev, r, flags, outside, thr, (dspmap_risk*)s[2].dev)) != DSPMAP_OK)
+        return rc;
+    return stage_end(m, s, 3);
+}
+extern "C" int dspmap_trajectory_risk_device(dspmap_t* m, int n_traj, int n_samples, const dspmap_query* q, float r, int flags,
+                                             float outside, float thr, dspmap_risk* out) {
+    int rc = risk_check(m, n_traj, n_samples, q, out, r, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n_traj == 0) return DSPMAP_OK;
+    const int n = n_traj * n_samples;
+    if ((rc = query_buf(m, risk_scratch_bytes(n))) != DSPMAP_OK) return rc;
+    return risk_enqueue(m, n_traj, n_samples, (const float4*)q, (float*)m->ly.q_buf, r, flags, outside, thr, out);
+}
+
+// --------------------------------------------------- distance fields (dspmap_distance.hip; semantics in include/dspmap.h)
+extern "C" int dspmap_build_distance_field(dspmap_t* m, float thr, int max_voxels, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (thr != thr) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: threshold is NaN");
+    if (max_voxels < 1 || max_voxels > 64) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: max_voxels %d outside [1, 64]", max_voxels);
+    if (flags & ~DSPMAP_DIST_OUTSIDE_OCCUPIED) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: unknown flags 0x%x", flags);
+    const int rc = whole_map_check(m, "distance field", "distances cross slabs");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    const MapDims& d = m->d;
+    const size_t cells = (size_t)(d.T + 1) * d.v_glob;
+    dspmap_layers_stale(m->ly, LAYERS_DISTANCE_REBUILD);
+    if (!m->ly.df_field) {
+        HIPCHK(m, hipMalloc(&m->ly.df_field, sizeof(float) * cells));
+        HIPCHK(m, hipMalloc(&m->ly.df_g8, cells));
+        HIPCHK(m, hipMalloc(&m->ly.df_h16, sizeof(unsigned short) * cells));
+    }
+    DistArgs a;
+    a.thr = thr; a.R = max_voxels; a.outside_occ = (flags & DSPMAP_DIST_OUTSIDE_OCCUPIED) ? 1 : 0;
+    a.fut_zero = m->fut_clear_pending ? 1 : 0;   // read, never changed (as the queries)
+    a.L = d.T + 1;
+    a.g8 = m->ly.df_g8; a.h16 = m->ly.df_h16; a.field = m->ly.df_field;
+    launch_distance_field(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    m->ly.df_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" const float* dspmap_distance_field_device(dspmap_t* m) { return (m && m->ly.df_valid) ? m->ly.df_field : nullptr; }
+static int dist_field_ready(dspmap* m, const char* what) {
+    return snapshot_ready(m, m->ly.df_valid, what, "no distance field, or the map has changed since it was built (dspmap_build_distance_field)");
+}
+extern "C" int dspmap_get_distance_field(dspmap_t* m, int layer, float* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: NULL output array");
+    if (layer < 0 || layer > m->d.T) return dspmap_fail(m, DSPMAP_E_ARG, "distance field: layer %d outside [0, %d)", layer, m->d.T + 1);
+    const int rc = dist_field_ready(m, "dspmap_get_distance_field");
+    if (rc != DSPMAP_OK) return rc;
+    const size_t V = (size_t)m->d.v_glob;
+    return read_back(m, out, m->ly.df_field + V * layer, sizeof(float) * V);
+}
+static int dist_query_check(dspmap* m, int n, const void* in, const void* out, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, "distance query", "sample", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = flags_check(m, "distance query", flags, DSPMAP_QUERY_WORLD)) != DSPMAP_OK) return rc;
+    if (outside != outside) return dspmap_fail(m, DSPMAP_E_ARG, "distance query: outside_value is NaN");
+    return dist_field_ready(m, "dspmap_query_distance");
+}
+static DistQueryArgs dist_query_args(const dspmap* m, int flags, float outside) {
+    DistQueryArgs a;
+    origin_fill(m, flags, &a);
+    a.outside = outside;
+    a.field = m->ly.df_field;
+    return a;
+}
+static int dist_query_enqueue(dspmap* m, int n, const float4* dq, int flags, float outside, float* dd, float* dg) {
+    launch_distance_query(dspmap_ctx_of(m), dist_query_args(m, flags, outside), n, dq, dd, dg);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_distance(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, float* dist, float* grad) {
+    int rc = dist_query_check(m, n, q, dist, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[3] = {{q, nullptr, sizeof(dspmap_query) * (size_t)n}, {nullptr, dist, sizeof(float) * (size_t)n},
+                     {nullptr, grad, grad ? sizeof(float) * 3 * (size_t)n : 0}};   // (no grad: no section, the kernel gets NULL)
+    if ((rc = stage_begin(m, s, 3)) != DSPMAP_OK) return rc;
+    if ((rc = dist_query_enqueue(m, n, (const float4*)s[0].dev, flags, outside, (float*)s[1].dev, (float*)s[2].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 3);
+}
+extern "C" int dspmap_query_distance_device(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, float* dist, float* grad) {
+    const int rc = dist_query_check(m, n, q, dist, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    return dist_query_enqueue(m, n, (const float4*)q, flags, outside, dist, grad);
+}
+
+// --------------------------------------------------- segment casts (dspmap_cast.hip; semantics in include/dspmap.h)
+static size_t cast_layer_words(const MapDims& d) { return (size_t)d.nz * d.ny * (size_t)((d.nx + 63) >> 6); }
+extern "C" int dspmap_build_cast_grid(dspmap_t* m, float thr, int inflate_voxels, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (thr != thr) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: threshold is NaN");
+    if (inflate_voxels < 0 || inflate_voxels > DSPMAP_CAST_MAX_INFLATE)
+        return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: inflate_voxels %d outside [0, %d]", inflate_voxels, DSPMAP_CAST_MAX_INFLATE);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: unknown flags 0x%x", flags);
+    const int rc = whole_map_check(m, "cast grid", "casts cross slabs");
+    if (rc != DSPMAP_OK) return rc;
+    const MapDims& d = m->d;
+    const size_t words = (size_t)(d.T + 1) * cast_layer_words(d);
+    if (words > 0x7fffffffull) return dspmap_fail(m, DSPMAP_E_STATE, "cast grid: %zu words exceed INT_MAX", words);
+    READY(m);
+    BENIGN(m);
+    dspmap_layers_stale(m->ly, LAYERS_CAST_GRID_REBUILD);   // (with the arrival fields grown and the frontiers found in the grid this build replaces)
+    if (!m->ly.cg_bits) {
+        HIPCHK(m, hipMalloc(&m->ly.cg_bits, sizeof(u64) * words));
+        HIPCHK(m, hipMalloc(&m->ly.cg_tmp, sizeof(u64) * words));
+    }
+    CastGridArgs a;
+    a.thr = thr; a.r = inflate_voxels;
+    a.fut_zero = m->fut_clear_pending ? 1 : 0;   // read, never changed (as the queries)
+    a.L = d.T + 1;
+    a.bits = m->ly.cg_bits; a.tmp = m->ly.cg_tmp;
+    launch_cast_grid(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    m->ly.cg_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" const unsigned long long* dspmap_cast_grid_device(dspmap_t* m) { return (m && m->ly.cg_valid) ? m->ly.cg_bits : nullptr; }
+static int cast_grid_ready(dspmap* m, const char* what) {
+    return snapshot_ready(m, m->ly.cg_valid, what, "no cast grid, or the map has changed since it was built (dspmap_build_cast_grid)");
+}
+extern "C" int dspmap_get_cast_grid(dspmap_t* m, int layer, unsigned long long* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: NULL output array");
+    if (layer < 0 || layer > m->d.T) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: layer %d outside [0, %d)", layer, m->d.T + 1);
+    const int rc = cast_grid_ready(m, "dspmap_get_cast_grid");
+    if (rc != DSPMAP_OK) return rc;
+    const size_t lw = cast_layer_words(m->d);
+    return read_back(m, out, m->ly.cg_bits + lw * layer, sizeof(u64) * lw);
+}
+static int cast_check(dspmap* m, int n, const void* in, const void* out, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, "cast", "segment", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = flags_check(m, "cast", flags, DSPMAP_QUERY_WORLD)) != DSPMAP_OK) return rc;
+    return cast_grid_ready(m, "dspmap_cast_segments");
+}
+static CastArgs cast_args(const dspmap* m, int flags) {
+    CastArgs a;
+    origin_fill(m, flags, &a);
+    a.bits = m->ly.cg_bits;
+    return a;
+}
+static int cast_enqueue(dspmap* m, int n, const dspmap_segment* ds, int flags, dspmap_cast_hit* dh) {
+    launch_cast(dspmap_ctx_of(m), cast_args(m, flags), n, ds, dh);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_cast_segments(dspmap_t* m, int n, const dspmap_segment* seg, int flags, dspmap_cast_hit* out) {
+    int rc = cast_check(m, n, seg, out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[2] = {{seg, nullptr, sizeof(dspmap_segment) * (size_t)n}, {nullptr, out, sizeof(dspmap_cast_hit) * (size_t)n}};
+    if ((rc = stage_begin(m, s, 2)) != DSPMAP_OK) return rc;
+    if ((rc = cast_enqueue(m, n, (const dspmap_segment*)s[0].dev, flags, (dspmap_cast_hit*)s[1].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 2);
+}
+extern "C" int dspmap_cast_segments_device(dspmap_t* m, int n, const dspmap_segment* seg, int flags, dspmap_cast_hit* out) {
+    const int rc = cast_check(m, n, seg, out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    return cast_enqueue(m, n, seg, flags, out);
+}
+
+// --------------------------------------------------- free boxes in the cast grid (dspmap_corridor.hip; semantics in include/dspmap.h)
+static int box_check(dspmap* m, int n, const void* in, const int* max_grow, int flags, const void* out) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, "grow boxes", "seed", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if (!max_grow) return dspmap_fail(m, DSPMAP_E_ARG, "grow boxes: NULL max_grow");
+    for (int k = 0; k < 3; ++k)
+        if (max_grow[k] < 0 || max_grow[k] > DSPMAP_BOX_MAX_GROW)
+            return dspmap_fail(m, DSPMAP_E_ARG, "grow boxes: max_grow[%d] = %d outside [0, %d]", k, max_grow[k], DSPMAP_BOX_MAX_GROW);
+    if ((rc = flags_check(m, "grow boxes", flags, DSPMAP_QUERY_WORLD | DSPMAP_BOX_WITH_CURRENT)) != DSPMAP_OK) return rc;
+    if ((rc = whole_map_check(m, "grow boxes", "boxes cross slabs")) != DSPMAP_OK) return rc;
+    return cast_grid_ready(m, "dspmap_grow_boxes");
+}
+static BoxArgs box_args(const dspmap* m, const int* max_grow, int flags) {
+    BoxArgs a;
+    origin_fill(m, flags, &a);
+    a.with_current = (flags & DSPMAP_BOX_WITH_CURRENT) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) a.grow[k] = max_grow[k];
+    a.bits = m->ly.cg_bits;
+    return a;
+}
+static int box_enqueue(dspmap* m, int n, const dspmap_segment* ds, const int* max_grow, int flags, dspmap_box* db) {
+    launch_grow_boxes(dspmap_ctx_of(m), box_args(m, max_grow, flags), n, ds, db);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_grow_boxes(dspmap_t* m, int n, const dspmap_segment* seed, const int max_grow[3], int flags, dspmap_box* out) {
+    int rc = box_check(m, n, seed, max_grow, flags, out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[2] = {{seed, nullptr, sizeof(dspmap_segment) * (size_t)n}, {nullptr, out, sizeof(dspmap_box) * (size_t)n}};
+    if ((rc = stage_begin(m, s, 2)) != DSPMAP_OK) return rc;
+    if ((rc = box_enqueue(m, n, (const dspmap_segment*)s[0].dev, max_grow, flags, (dspmap_box*)s[1].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 2);
+}
+extern "C" int dspmap_grow_boxes_device(dspmap_t* m, int n, const dspmap_segment* seed, const int max_grow[3], int flags, dspmap_box* out) {
+    const int rc = box_check(m, n, seed, max_grow, flags, out);
+    if (rc != DSPMAP_OK) return rc;
+    return box_enqueue(m, n, seed, max_grow, flags, out);
+}
+
+// --------------------------------------------------- arrival-time fields (dspmap_reach.hip; semantics in include/dspmap.h)
+// the layer step n tests: the host twin of reach_layer (dspmap_reach.hip) -- the same fp32 operations, the k(t) of q_horizon
+static int reach_layer_host(const MapDims& d, bool timed, float t_start, float step_seconds, int n) {
+    if (!timed) return 0;
+    volatile float prod = (float)n * step_seconds;   // (volatile: two roundings, whatever the host compiler would like to fuse)
+    volatile float t = t_start + prod;
+    const float tt = t;
+    int k = d.T - 1;
+    for (int j = d.T - 1; j >= 0; --j)
+        if (d.pred_t[j] >= tt) k = j;
+    return k + 1;
+}
+// the checks of both builds; `timeline`: dspmap_build_reach_timeline*, which adds the cap on the kept sets behind the other arguments
+static int reach_build_check(dspmap* m, int n_fields, int n_src, const void* src, float t_start, float step_seconds, int max_steps, int flags,
+                             bool timeline = false) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n_fields < 1 || n_fields > DSPMAP_REACH_MAX_FIELDS)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: n_fields %d outside [1, %d]", n_fields, DSPMAP_REACH_MAX_FIELDS);
+    if (n_src < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: negative source count %d", n_src);
+    if (n_src > 0 && !src) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: NULL source array");
+    if (t_start != t_start) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: t_start is NaN");
+    if (!(step_seconds >= 0.f && step_seconds < INFINITY))
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: step_seconds %g is NaN, negative or infinite", (double)step_seconds);
+    if (max_steps < 1 || max_steps > DSPMAP_REACH_MAX_STEPS)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: max_steps %d outside [1, %d]", max_steps, DSPMAP_REACH_MAX_STEPS);
+    if (flags & ~(DSPMAP_QUERY_WORLD | DSPMAP_REACH_WITH_CURRENT | DSPMAP_REACH_DEVICE_SETS))
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: unknown flags 0x%x", flags);
+    const unsigned long long cells = (unsigned long long)n_fields * (unsigned long long)m->d.v_glob;
+    if (cells > 0x80000000ull) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: %d fields of %d cells exceed 2^31 cells", n_fields, m->d.v_glob);
+    if (timeline) {   // (n_fields <= 64, max_steps + 1 <= 4097, a layer's words < 2^31: no overflow in 64 bits)
+        const unsigned long long bytes = (unsigned long long)n_fields * (unsigned long long)(max_steps + 1) * cast_layer_words(m->d) * sizeof(u64);
+        if (bytes > DSPMAP_REACH_TIMELINE_MAX_BYTES)
+            return dspmap_fail(m, DSPMAP_E_ARG, "reach timeline: the sets of %d fields and %d steps take %llu bytes, more than "
+                                                "DSPMAP_REACH_TIMELINE_MAX_BYTES = %llu", n_fields, max_steps + 1, bytes,
+                               (unsigned long long)DSPMAP_REACH_TIMELINE_MAX_BYTES);
+    }
+    const int rc = whole_map_check(m, "reach fields", "a wavefront crosses slabs");
+    if (rc != DSPMAP_OK) return rc;
+    return cast_grid_ready(m, timeline ? "dspmap_build_reach_timeline" : "dspmap_build_reach_fields");
+}
+// the launch behind all four build entry points; src_dev may be NULL with n_src == 0.  keep: the timeline build, which also stores every
+// step's set (a plain build replaces the fields a timeline belongs to, so it leaves none)
+static int reach_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_point* src_dev, float t_start, float step_seconds, int max_steps,
+                       int flags, bool keep = false) {
+    const MapDims& d = m->d;
+    dspmap_layers_stale(m->ly, LAYERS_REACH_REBUILD);
+    const size_t cells = (size_t)n_fields * d.v_glob, lw = cast_layer_words(d);
+    const bool lds = 2 * sizeof(u64) * lw <= (size_t)REACH_LDS_BYTES && !(flags & DSPMAP_REACH_DEVICE_SETS);
+    const size_t set_words = lds ? 0 : 2 * lw * (size_t)n_fields;
+    const size_t hist_words = keep ? (size_t)n_fields * ((size_t)max_steps + 1) * lw : 0;
+    if (cells > m->ly.rf_field_cells || set_words > m->ly.rf_sets_words || hist_words > m->ly.tl_hist_words || (keep && !m->ly.tl_last)) {   // grown only after the stream has drained (an earlier call may still read them)
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        if (!m->ly.rf_field) reach_init_device();
+        if (cells > m->ly.rf_field_cells) {
+            if (m->ly.rf_field) { HIPCHK(m, hipFree(m->ly.rf_field)); m->ly.rf_field = nullptr; m->ly.rf_field_cells = 0; }
+            HIPCHK(m, hipMalloc(&m->ly.rf_field, sizeof(unsigned short) * cells));
+            m->ly.rf_field_cells = cells;
+        }
+        if (set_words > m->ly.rf_sets_words) {
+            if (m->ly.rf_sets) { HIPCHK(m, hipFree(m->ly.rf_sets)); m->ly.rf_sets = nullptr; m->ly.rf_sets_words = 0; }
+            HIPCHK(m, hipMalloc(&m->ly.rf_sets, sizeof(u64) * set_words));
+            m->ly.rf_sets_words = set_words;
+        }
+        if (hist_words > m->ly.tl_hist_words) {
+            if (m->ly.tl_hist) { HIPCHK(m, hipFree(m->ly.tl_hist)); m->ly.tl_hist = nullptr; m->ly.tl_hist_words = 0; }
+            HIPCHK(m, hipMalloc(&m->ly.tl_hist, sizeof(u64) * hist_words));
+            m->ly.tl_hist_words = hist_words;
+        }
+        if (keep && !m->ly.tl_last) HIPCHK(m, hipMalloc(&m->ly.tl_last, sizeof(int) * DSPMAP_REACH_MAX_FIELDS));
+    }
+    ReachArgs a;
+    origin_fill(m, flags, &a);
+    a.with_current = (flags & DSPMAP_REACH_WITH_CURRENT) ? 1 : 0;
+    const bool timed = !(t_start < 0.f) && d.T > 0;
+    a.timed = timed ? 1 : 0;
+    a.t_start = t_start; a.step_seconds = step_seconds; a.max_steps = max_steps;
+    const int l_last = reach_layer_host(d, timed, t_start, step_seconds, max_steps);
+    int n_fix = max_steps;
+    while (n_fix > 0 && reach_layer_host(d, timed, t_start, step_seconds, n_fix - 1) == l_last) --n_fix;
+    a.n_fix = n_fix;
+    a.n_fields = n_fields; a.n_src = n_src;
+    a.bits = m->ly.cg_bits; a.field = m->ly.rf_field; a.sets = lds ? nullptr : m->ly.rf_sets;
+    HIPCHK(m, hipMemsetAsync(m->ly.rf_field, 0xff, sizeof(unsigned short) * cells, m->stream));   // every value DSPMAP_REACH_UNREACHED
+    launch_reach(dspmap_ctx_of(m), a, src_dev, keep ? m->ly.tl_hist : nullptr, keep ? m->ly.tl_last : nullptr);
+    HIPCHK(m, hipGetLastError());
+    m->ly.rf_n = n_fields;
+    m->ly.rf_invariant = reach_layer_host(d, timed, t_start, step_seconds, 0) == l_last;
+    m->ly.rf_storage[0] = lds ? n_fields : 0; m->ly.rf_storage[1] = lds ? 0 : n_fields;
+    m->ly.rf_valid = true;
+    if (keep) m->ly.tl_valid = true;
+    m->ly.tl_max_steps = max_steps;
+    return DSPMAP_OK;
+}
+// the synchronous entry points: the sources go through the query staging buffer
+static int reach_build_host(dspmap* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds, int max_steps,
+                            int flags, bool keep) {
+    int rc = reach_build_check(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, keep);
+    if (rc != DSPMAP_OK) return rc;
+    StageSec s[1] = {{src, nullptr, sizeof(dspmap_reach_point) * (size_t)n_src}};   // (no sources: no section, the kernel gets NULL)
+    if ((rc = stage_begin(m, s, 1)) != DSPMAP_OK) return rc;
+    if ((rc = reach_build(m, n_fields, n_src, (const dspmap_reach_point*)s[0].dev, t_start, step_seconds, max_steps, flags, keep)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 1);
+}
+extern "C" int dspmap_build_reach_fields(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds,
+                                         int max_steps, int flags) {
+    return reach_build_host(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, false);
+}
+extern "C" int dspmap_build_reach_timeline(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start, float step_seconds,
+                                           int max_steps, int flags) {
+    return reach_build_host(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, true);
+}
+extern "C" int dspmap_build_reach_timeline_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start,
+                                                  float step_seconds, int max_steps, int flags) {
+    const int rc = reach_build_check(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, true);
+    if (rc != DSPMAP_OK) return rc;
+    return reach_build(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags, true);
+}
+extern "C" int dspmap_build_reach_fields_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t_start,
+                                                float step_seconds, int max_steps, int flags) {
+    const int rc = reach_build_check(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags);
+    if (rc != DSPMAP_OK) return rc;
+    return reach_build(m, n_fields, n_src, src, t_start, step_seconds, max_steps, flags);
+}
+extern "C" const unsigned short* dspmap_reach_fields_device(dspmap_t* m) { return (m && m->ly.rf_valid) ? m->ly.rf_field : nullptr; }
+static int reach_ready(dspmap* m, const char* what) {
+    const int rc = whole_map_check(m, what, "a wavefront crosses slabs");
+    if (rc != DSPMAP_OK) return rc;
+    return snapshot_ready(m, m->ly.rf_valid, what,
+                          "no arrival fields, or the map or its cast grid has changed since they were built (dspmap_build_reach_fields)");
+}
+extern "C" int dspmap_get_reach_field(dspmap_t* m, int field, unsigned short* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "reach field: NULL output array");
+    if (field < 0 || field >= DSPMAP_REACH_MAX_FIELDS) return dspmap_fail(m, DSPMAP_E_ARG, "reach field: field %d outside [0, %d)", field, DSPMAP_REACH_MAX_FIELDS);
+    const int rc = reach_ready(m, "dspmap_get_reach_field");
+    if (rc != DSPMAP_OK) return rc;
+    if (field >= m->ly.rf_n) return dspmap_fail(m, DSPMAP_E_ARG, "reach field: field %d outside [0, %d), the fields of the last build", field, m->ly.rf_n);
+    return read_back(m, out, m->ly.rf_field + (size_t)field * m->d.v_glob, sizeof(unsigned short) * (size_t)m->d.v_glob);
+}
+// the fields' timeline: valid while the fields it was built with are
+static int reach_timeline_ready(dspmap* m, const char* what) {
+    const int rc = whole_map_check(m, what, "a wavefront crosses slabs");
+    if (rc != DSPMAP_OK) return rc;
+    return snapshot_ready(m, m->ly.tl_valid, what,
+                          "no timeline, or the map, its cast grid or the arrival fields have changed since it was built (dspmap_build_reach_timeline)");
+}
+extern "C" const unsigned long long* dspmap_reach_timeline_device(dspmap_t* m) {
+    return (m && m->ly.tl_valid) ? (const unsigned long long*)m->ly.tl_hist : nullptr;
+}
+extern "C" int dspmap_reach_last_steps(dspmap_t* m, int* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "reach last steps: NULL output array");
+    const int rc = reach_timeline_ready(m, "dspmap_reach_last_steps");
+    if (rc != DSPMAP_OK) return rc;
+    return read_back(m, out, m->ly.tl_last, sizeof(int) * (size_t)m->ly.rf_n);
+}
+extern "C" int dspmap_get_reach_sets(dspmap_t* m, int field, int first_step, int n_steps, unsigned long long* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (field < 0 || field >= DSPMAP_REACH_MAX_FIELDS) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: field %d outside [0, %d)", field, DSPMAP_REACH_MAX_FIELDS);
+    if (first_step < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: negative first_step %d", first_step);
+    if (n_steps < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: negative n_steps %d", n_steps);
+    if (first_step > DSPMAP_REACH_MAX_STEPS + 1 || n_steps > DSPMAP_REACH_MAX_STEPS + 1 - first_step)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: steps [%d, %d + %d) outside [0, %d]", first_step, first_step, n_steps, DSPMAP_REACH_MAX_STEPS);
+    if (n_steps > 0 && !out) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: NULL output array with n_steps %d", n_steps);
+    const int rc = reach_timeline_ready(m, "dspmap_get_reach_sets");
+    if (rc != DSPMAP_OK) return rc;
+    if (field >= m->ly.rf_n) return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: field %d outside [0, %d), the fields of the last build", field, m->ly.rf_n);
+    if (first_step + n_steps > m->ly.tl_max_steps + 1)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach sets: steps [%d, %d) outside [0, %d], the steps of the last build", first_step, first_step + n_steps,
+                           m->ly.tl_max_steps);
+    if (n_steps == 0) return DSPMAP_OK;
+    int last = 0;   // the field's last executed step: a later one repeats its row
+    HIPCHK(m, hipMemcpyAsync(&last, m->ly.tl_last + field, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    if (last < 0 || last > m->ly.tl_max_steps) return dspmap_fail(m, DSPMAP_E_DEVICE, "reach sets: field %d reports last step %d outside [0, %d]", field, last, m->ly.tl_max_steps);
+    const size_t lw = cast_layer_words(m->d);
+    const u64* rows = m->ly.tl_hist + (size_t)field * ((size_t)m->ly.tl_max_steps + 1) * lw;
+    const int n_own = first_step > last ? 0 : (first_step + n_steps - 1 > last ? last - first_step + 1 : n_steps);   // rows the build wrote
+    if (n_own > 0) HIPCHK(m, hipMemcpyAsync(out, rows + (size_t)first_step * lw, sizeof(u64) * lw * (size_t)n_own, hipMemcpyDeviceToHost, m->stream));
+    for (int k = n_own; k < n_steps; ++k)
+        HIPCHK(m, hipMemcpyAsync(out + (size_t)k * lw, rows + (size_t)last * lw, sizeof(u64) * lw, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+// the argument checks of dspmap_reach_paths* and dspmap_reach_timeline_paths*
+static int reach_paths_args_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: negative start count %d", n);
+    if (max_len < 0 || max_len > DSPMAP_REACH_MAX_STEPS + 1)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: max_len %d outside [0, %d]", max_len, DSPMAP_REACH_MAX_STEPS + 1);
+    if (n > 0 && (!start || !steps_out)) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: NULL start or steps_out array");
+    if (n > 0 && max_len > 0 && !cells_out) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: NULL cells_out array with max_len %d", max_len);
+    if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: unknown flags 0x%x", flags);
+    if ((unsigned long long)n * (unsigned long long)max_len > 0x80000000ull)
+        return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: %d paths of %d cells exceed 2^31 cells", n, max_len);
+    return DSPMAP_OK;
+}
+// ... then the state: the plain paths need time-invariant fields, the timeline's paths (`timeline`) the sets a timeline build kept
+static int reach_paths_check(dspmap* m, bool timeline, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
+    int rc = reach_paths_args_check(m, n, start, max_len, flags, steps_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    if (timeline) return reach_timeline_ready(m, "dspmap_reach_timeline_paths");
+    if ((rc = reach_ready(m, "dspmap_reach_paths")) != DSPMAP_OK) return rc;
+    if (!m->ly.rf_invariant)
+        return dspmap_fail(m, DSPMAP_E_STATE, "reach paths: the fields of the last build are not time-invariant (the tested layer changed "
+                                              "during the steps): first arrivals alone do not determine a path");
+    return DSPMAP_OK;
+}
+static int reach_paths_enqueue(dspmap* m, bool timeline, int n, const dspmap_reach_point* ds, int max_len, int flags, int* dt, int* dc) {
+    if (timeline) {
+        ReachTimelinePathArgs a;
+        origin_fill(m, flags, &a);
+        a.n_fields = m->ly.rf_n; a.max_len = max_len; a.max_steps = m->ly.tl_max_steps;
+        a.field = m->ly.rf_field; a.hist = m->ly.tl_hist; a.last = m->ly.tl_last;
+        launch_reach_timeline_paths(dspmap_ctx_of(m), a, n, ds, dt, dc);
+    } else {
+        ReachPathArgs a;
+        origin_fill(m, flags, &a);
+        a.n_fields = m->ly.rf_n; a.max_len = max_len;
+        a.field = m->ly.rf_field;
+        launch_reach_paths(dspmap_ctx_of(m), a, n, ds, dt, dc);
+    }
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+// the two host entry points (max_len == 0: no cells section, the kernel gets NULL) ...
+static int reach_paths_host(dspmap* m, bool timeline, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
+    int rc = reach_paths_check(m, timeline, n, start, max_len, flags, steps_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[3] = {{start, nullptr, sizeof(dspmap_reach_point) * (size_t)n}, {nullptr, steps_out, sizeof(int) * (size_t)n},
+                     {nullptr, cells_out, sizeof(int) * (size_t)n * max_len}};
+    if ((rc = stage_begin(m, s, 3)) != DSPMAP_OK) return rc;
+    if ((rc = reach_paths_enqueue(m, timeline, n, (const dspmap_reach_point*)s[0].dev, max_len, flags, (int*)s[1].dev, (int*)s[2].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 3);
+}
+// ... and the two stream-ordered ones
+static int reach_paths_device(dspmap* m, bool timeline, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
+    const int rc = reach_paths_check(m, timeline, n, start, max_len, flags, steps_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    return reach_paths_enqueue(m, timeline, n, start, max_len, flags, steps_out, cells_out);
+}
+extern "C" int dspmap_reach_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
+    return reach_paths_host(m, false, n, start, max_len, flags, steps_out, cells_out);
+}
+extern "C" int dspmap_reach_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
+    return reach_paths_device(m, false, n, start, max_len, flags, steps_out, cells_out);
+}
+extern "C" int dspmap_reach_timeline_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out,
+                                           int* cells_out) {
+    return reach_paths_host(m, true, n, start, max_len, flags, steps_out, cells_out);
+}
+extern "C" int dspmap_reach_timeline_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out,
+                                                  int* cells_out) {
+    return reach_paths_device(m, true, n, start, max_len, flags, steps_out, cells_out);
+}
+extern "C" int dspmap_debug_reach_storage(dspmap_t* m, long long out[2]) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "reach storage: NULL output array");
+    out[0] = m->ly.rf_storage[0]; out[1] = m->ly.rf_storage[1];
+    return DSPMAP_OK;
+}
+// test hook: all L layers of the VALID cast grid are replaced by the caller's words
+extern "C" int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long* words) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!words) return dspmap_fail(m, DSPMAP_E_ARG, "set cast grid: NULL word array");
+    const MapDims& d = m->d;
+    const size_t nw = (size_t)((d.nx + 63) >> 6), total = (size_t)(d.T + 1) * cast_layer_words(d);
+    if (d.nx & 63) {
+        const unsigned long long pad = ~0ull << (d.nx & 63);
+        for (size_t i = nw - 1; i < total; i += nw)
+            if (words[i] & pad) return dspmap_fail(m, DSPMAP_E_ARG, "set cast grid: word %zu has a bit set at x >= nx", i);
+    }
+    int rc = whole_map_check(m, "set cast grid", "");
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = cast_grid_ready(m, "dspmap_debug_set_cast_grid")) != DSPMAP_OK) return rc;
+    dspmap_layers_stale(m->ly, LAYERS_CAST_GRID_CHANGED);
+    HIPCHK(m, hipMemcpyAsync(m->ly.cg_bits, words, sizeof(u64) * total, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));   // (the caller's array is free again)
+    return DSPMAP_OK;
+}
+
+// --------------------------------------------------- occupancy forecast at caller-chosen times (dspmap_forecast.hip; semantics in include/dspmap.h)
+static_assert(FORECAST_MAX_TIMES == DSPMAP_FORECAST_MAX_TIMES, "ForecastArgs holds DSPMAP_FORECAST_MAX_TIMES times");
+extern "C" int dspmap_build_forecast(dspmap_t* m, int n_times, const float* times, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n_times < 1 || n_times > DSPMAP_FORECAST_MAX_TIMES)
+        return dspmap_fail(m, DSPMAP_E_ARG, "forecast: n_times %d outside [1, %d]", n_times, DSPMAP_FORECAST_MAX_TIMES);
+    if (!times) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: NULL times array");
+    for (int j = 0; j < n_times; ++j) {
+        if (!(times[j] >= 0.f && times[j] < INFINITY))
+            return dspmap_fail(m, DSPMAP_E_ARG, "forecast: times[%d] = %g is NaN, infinite or negative", j, (double)times[j]);
+        if (j > 0 && !(times[j] > times[j - 1]))
+            return dspmap_fail(m, DSPMAP_E_ARG, "forecast: times[%d] = %g is not greater than times[%d] = %g", j, (double)times[j], j - 1, (double)times[j - 1]);
+    }
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: unknown flags 0x%x", flags);
+    if ((unsigned long long)n_times * (unsigned long long)m->d.v_glob >= 0x80000000ull)
+        return dspmap_fail(m, DSPMAP_E_ARG, "forecast: %d layers of %d cells reach 2^31 cells", n_times, m->d.v_glob);
+    const int rc = whole_map_check(m, "forecast", "particles cross slabs");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    const MapDims& d = m->d;
+    dspmap_layers_stale(m->ly, LAYERS_FORECAST_REBUILD);
+    if (n_times > m->ly.fc_cap) {   // grown only after the stream has drained (an earlier call may still read them)
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        if (m->ly.fc_field) { HIPCHK(m, hipFree(m->ly.fc_field)); m->ly.fc_field = nullptr; }
+        if (m->ly.fc_acc) { HIPCHK(m, hipFree(m->ly.fc_acc)); m->ly.fc_acc = nullptr; }
+        m->ly.fc_cap = 0;
+        HIPCHK(m, hipMalloc(&m->ly.fc_field, sizeof(float) * (size_t)n_times * d.v_glob));
+        HIPCHK(m, hipMalloc(&m->ly.fc_acc, sizeof(u64) * (size_t)(n_times + 1) * d.v_loc));
+        m->ly.fc_cap = n_times;
+    }
+    ForecastArgs a;
+    a.n = n_times;
+    for (int j = 0; j < FORECAST_MAX_TIMES; ++j) a.t[j] = j < n_times ? times[j] : 0.f;
+    a.dyn = m->ly.fc_acc; a.stat = m->ly.fc_acc + (size_t)n_times * d.v_loc; a.out = m->ly.fc_field;
+    HIPCHK(m, hipMemsetAsync(m->ly.fc_acc, 0, sizeof(u64) * (size_t)(n_times + 1) * d.v_loc, m->stream));   // dyn and stat: one allocation
+    launch_forecast(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    m->ly.fc_n = n_times;
+    for (int j = 0; j < n_times; ++j) m->ly.fc_t[j] = times[j];
+    m->ly.fc_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" const float* dspmap_forecast_device(dspmap_t* m) { return (m && m->ly.fc_valid) ? m->ly.fc_field : nullptr; }
+static int forecast_ready(dspmap* m, const char* what) {
+    return snapshot_ready(m, m->ly.fc_valid, what, "no forecast, or the map has changed since it was built (dspmap_build_forecast)");
+}
+extern "C" int dspmap_forecast_times(dspmap_t* m, float* times_out, int cap) {
+    if (!m) return DSPMAP_E_ARG;
+    if (cap > 0 && !times_out) return dspmap_fail(m, DSPMAP_E_ARG, "forecast times: NULL output array");
+    const int rc = forecast_ready(m, "dspmap_forecast_times");
+    if (rc != DSPMAP_OK) return rc;
+    for (int j = 0; j < m->ly.fc_n && j < cap; ++j) times_out[j] = m->ly.fc_t[j];
+    return m->ly.fc_n;
+}
+extern "C" int dspmap_get_forecast(dspmap_t* m, int layer, float* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: NULL output array");
+    if (layer < 0 || layer >= DSPMAP_FORECAST_MAX_TIMES) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: layer %d outside [0, %d)", layer, DSPMAP_FORECAST_MAX_TIMES);
+    const int rc = forecast_ready(m, "dspmap_get_forecast");
+    if (rc != DSPMAP_OK) return rc;
+    if (layer >= m->ly.fc_n) return dspmap_fail(m, DSPMAP_E_ARG, "forecast: layer %d outside [0, %d), the layers of the last build", layer, m->ly.fc_n);
+    const size_t V = (size_t)m->d.v_glob;
+    return read_back(m, out, m->ly.fc_field + V * layer, sizeof(float) * V);
+}
+static int forecast_query_check(dspmap* m, int n, const void* in, const void* out, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, "forecast query", "sample", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = flags_check(m, "forecast query", flags, DSPMAP_QUERY_WORLD | DSPMAP_FORECAST_LERP)) != DSPMAP_OK) return rc;
+    if (outside != outside) return dspmap_fail(m, DSPMAP_E_ARG, "forecast query: outside_value is NaN");
+    return forecast_ready(m, "dspmap_query_forecast");
+}
+static ForecastQueryArgs forecast_query_args(const dspmap* m, int flags, float outside) {
+    ForecastQueryArgs a;
+    origin_fill(m, flags, &a);
+    a.lerp = (flags & DSPMAP_FORECAST_LERP) ? 1 : 0;
+    a.outside = outside;
+    a.n = m->ly.fc_n;
+    for (int j = 0; j < FORECAST_MAX_TIMES; ++j) a.t[j] = j < m->ly.fc_n ? m->ly.fc_t[j] : 0.f;
+    a.field = m->ly.fc_field;
+    return a;
+}
+static int forecast_query_enqueue(dspmap* m, int n, const float4* dq, int flags, float outside, float* dout) {
+    launch_forecast_query(dspmap_ctx_of(m), forecast_query_args(m, flags, outside), n, dq, dout);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_forecast(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, float* out) {
+    int rc = forecast_query_check(m, n, q, out, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[2] = {{q, nullptr, sizeof(dspmap_query) * (size_t)n}, {nullptr, out, sizeof(float) * (size_t)n}};
+    if ((rc = stage_begin(m, s, 2)) != DSPMAP_OK) return rc;
+    if ((rc = forecast_query_enqueue(m, n, (const float4*)s[0].dev, flags, outside, (float*)s[1].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 2);
+}
+extern "C" int dspmap_query_forecast_device(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, float* out) {
+    const int rc = forecast_query_check(m, n, q, out, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    return forecast_query_enqueue(m, n, (const float4*)q, flags, outside, out);
+}
+
+// --------------------------------------------------- known-space layer (dspmap_known.hip; semantics in include/dspmap.h)
+// the window of the current position: lattice index k0 of map voxel 0 and the offset o of that cell's centre from the sensor, per axis, in
+// double from the floats cur_pos and res (dspmap.h states the arithmetic; tests/known_ref.py restates it)
+static int known_window(dspmap* m, long long k0[3], float o[3]) {
+    const int n[3] = {m->d.nx, m->d.ny, m->d.nz};
+    const double res = (double)m->d.res;
+    for (int a = 0; a < 3; ++a) {
+        const double cur = (double)m->cur_pos[a];
+        const double g = cur / res - (double)n[a] / 2.0;
+        if (!(fabs(g) < 4.0e15))   // (also NaN: dspmap_set_current_position takes any float)
+            return dspmap_fail(m, DSPMAP_E_STATE, "known space: the current position %g on axis %d is not finite or beyond 4e15 cells", cur, a);
+        k0[a] = (long long)floor(g + 0.5);
+        o[a] = (float)(((double)k0[a] + 0.5) * res - cur);
+    }
+    return DSPMAP_OK;
+}
+static int known_slot(long long k, int n) { const long long r = k % n; return (int)(r < 0 ? r + n : r); }
+// everything forgotten (dspmap_known_reset, dspmap_clear_state, dspmap_load_checkpoint); a handle without a layer has nothing to forget
+int dspmap_known_forget(dspmap* m) {
+    m->ly.kn_integrated = false;
+    dspmap_layers_stale(m->ly, LAYERS_KNOWN_CHANGED);
+    if (m->ly.kn_stamp) HIPCHK(m, hipMemsetAsync(m->ly.kn_stamp, 0, sizeof(unsigned) * (size_t)m->d.v_glob, m->stream));
+    return DSPMAP_OK;
+}
+// FIRST thing in every entry point that reads or writes the layer: move the window to the current position.  The lattice cells that entered
+// it since the last synchronisation are reset to "never" on the stream (their slots held the cells that left on the other side); a shift of
+// n or more cells on an axis resets everything.  Fills the kernels' arguments.
+static int known_sync(dspmap* m, KnownArgs* a) {
+    long long k0[3];
+    float o[3];
+    const int rc = known_window(m, k0, o);
+    if (rc != DSPMAP_OK) return rc;
+    const MapDims& d = m->d;
+    const int n[3] = {d.nx, d.ny, d.nz};
+    if (m->ly.kn_stamp && (k0[0] != m->ly.kn_k0[0] || k0[1] != m->ly.kn_k0[1] || k0[2] != m->ly.kn_k0[2])) {
+        int s0[3] = {0, 0, 0}, cnt[3] = {0, 0, 0};
+        bool all = false;
+        for (int ax = 0; ax < 3; ++ax) {
+            const long long delta = k0[ax] - m->ly.kn_k0[ax];
+            if (delta >= n[ax] || -delta >= n[ax]) { all = true; break; }
+            // delta > 0: the cells [old + n, new + n) enter, delta < 0: the cells [new, old)
+            if (delta > 0) { s0[ax] = known_slot(m->ly.kn_k0[ax], n[ax]); cnt[ax] = (int)delta; }
+            else if (delta < 0) { s0[ax] = known_slot(k0[ax], n[ax]); cnt[ax] = (int)-delta; }
+        }
+        if (all) HIPCHK(m, hipMemsetAsync(m->ly.kn_stamp, 0, sizeof(unsigned) * (size_t)d.v_glob, m->stream));
+        else launch_known_clear(d, m->stream, m->ly.kn_stamp, s0, cnt);
+        HIPCHK(m, hipGetLastError());
+    }
+    for (int ax = 0; ax < 3; ++ax) m->ly.kn_k0[ax] = k0[ax];
+    a->stamp = m->ly.kn_stamp;
+    a->bx = known_slot(k0[0], d.nx); a->by = known_slot(k0[1], d.ny); a->bz = known_slot(k0[2], d.nz);
+    a->ox = o[0]; a->oy = o[1]; a->oz = o[2];
+    a->max_range = INFINITY;
+    a->occl_margin = m->fp.occl_margin;
+    a->now = (unsigned)m->update_counter;
+    return DSPMAP_OK;
+}
+static int known_whole_map(dspmap* m, const char* what) { return whole_map_check(m, what, "the sensor's view crosses slabs"); }
+extern "C" int dspmap_known_integrate(dspmap_t* m, float max_range, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!(max_range > 0.f)) return dspmap_fail(m, DSPMAP_E_ARG, "known space: max_range %g is NaN or not positive", (double)max_range);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "known space: unknown flags 0x%x", flags);
+    int rc = known_whole_map(m, "dspmap_known_integrate");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (m->update_counter < 1)
+        return dspmap_fail(m, DSPMAP_E_STATE, "known space: no frame has been accepted yet, there is no view to integrate (dspmap_update)");
+    dspmap_layers_stale(m->ly, LAYERS_KNOWN_CHANGED);
+    const bool fresh = !m->ly.kn_stamp;
+    if (fresh) {
+        HIPCHK(m, hipMalloc(&m->ly.kn_stamp, sizeof(unsigned) * (size_t)m->d.v_glob));
+        HIPCHK(m, hipMemsetAsync(m->ly.kn_stamp, 0, sizeof(unsigned) * (size_t)m->d.v_glob, m->stream));
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) {
+        if (fresh) { (void)hipStreamSynchronize(m->stream); (void)hipFree(m->ly.kn_stamp); m->ly.kn_stamp = nullptr; }
+        return rc;
+    }
+    a.max_range = max_range;
+    launch_known_integrate(m->d, m->s, m->stream, a, m->n_cu);
+    HIPCHK(m, hipGetLastError());
+    m->ly.kn_integrated = true;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_known_reset(dspmap_t* m) {
+    READY(m);
+    BENIGN(m);
+    return dspmap_known_forget(m);
+}
+extern "C" int dspmap_get_known(dspmap_t* m, int* age_out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!age_out) return dspmap_fail(m, DSPMAP_E_ARG, "known space: NULL output array");
+    int rc = known_whole_map(m, "dspmap_get_known");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    const size_t V = (size_t)m->d.v_glob;
+    if (!m->ly.kn_stamp) {   // never integrated: nothing allocated, nothing known
+        for (size_t i = 0; i < V; ++i) age_out[i] = -1;
+        return DSPMAP_OK;
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    StageSec s[1] = {{nullptr, age_out, sizeof(int) * V}};
+    if ((rc = stage_begin(m, s, 1)) != DSPMAP_OK) return rc;
+    launch_known_ages(m->d, m->stream, a, (int*)s[0].dev);
+    HIPCHK(m, hipGetLastError());
+    return stage_end(m, s, 1);
+}
+static int known_query_check(dspmap* m, int n, const void* in, const void* out, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, "known query", "sample", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = flags_check(m, "known query", flags, DSPMAP_QUERY_WORLD)) != DSPMAP_OK) return rc;
+    return known_whole_map(m, "dspmap_query_known");
+}
+// (the caller has synchronised the layer: known_sync queues work of its own, in front of the staging copies)
+static int known_query_enqueue(dspmap* m, const KnownArgs& a, int n, const float4* dq, int flags, int* dout) {
+    launch_known_query(m->d, m->stream, a, (flags & DSPMAP_QUERY_WORLD) ? 1 : 0, m->cur_pos, n, dq, dout);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_known(dspmap_t* m, int n, const dspmap_query* q, int flags, int* age_out) {
+    int rc = known_query_check(m, n, q, age_out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n == 0) return DSPMAP_OK;
+    if (!m->ly.kn_stamp) {
+        for (int i = 0; i < n; ++i) age_out[i] = -1;
+        return DSPMAP_OK;
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    StageSec s[2] = {{q, nullptr, sizeof(dspmap_query) * (size_t)n}, {nullptr, age_out, sizeof(int) * (size_t)n}};
+    if ((rc = stage_begin(m, s, 2)) != DSPMAP_OK) return rc;
+    if ((rc = known_query_enqueue(m, a, n, (const float4*)s[0].dev, flags, (int*)s[1].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 2);
+}
+extern "C" int dspmap_query_known_device(dspmap_t* m, int n, const dspmap_query* q, int flags, int* age_out) {
+    int rc = known_query_check(m, n, q, age_out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if (n == 0) return DSPMAP_OK;
+    if (!m->ly.kn_stamp) {   // never integrated: every byte 0xff is the int -1
+        HIPCHK(m, hipMemsetAsync(age_out, 0xff, sizeof(int) * (size_t)n, m->stream));
+        return DSPMAP_OK;
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    return known_query_enqueue(m, a, n, (const float4*)q, flags, age_out);
+}
+extern "C" int dspmap_mask_cast_grid(dspmap_t* m, int max_age, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "mask cast grid: negative max_age %d", max_age);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "mask cast grid: unknown flags 0x%x", flags);
+    int rc = cast_grid_ready(m, "dspmap_mask_cast_grid");
+    if (rc != DSPMAP_OK) return rc;
+    if (!m->ly.kn_stamp || !m->ly.kn_integrated)
+        return dspmap_fail(m, DSPMAP_E_STATE, "mask cast grid: no frame has been integrated into the known-space layer (dspmap_known_integrate)");
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    dspmap_layers_stale(m->ly, LAYERS_CAST_GRID_CHANGED);   // (arrival fields were grown in the grid as it was, frontiers found in it)
+    launch_known_mask(m->d, m->stream, a, max_age, m->d.T + 1, m->ly.cg_bits);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_known_stats(dspmap_t* m, int max_age, long long out[2]) {
+    if (!m) return DSPMAP_E_ARG;
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "known stats: negative max_age %d", max_age);
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "known stats: NULL output array");
+    int rc = known_whole_map(m, "dspmap_known_stats");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    out[0] = out[1] = 0;
+    if (!m->ly.kn_stamp) return DSPMAP_OK;
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    u64 sums[2] = {0, 0};
+    StageSec s[1] = {{nullptr, sums, sizeof(sums)}};
+    if ((rc = stage_begin(m, s, 1)) != DSPMAP_OK) return rc;
+    HIPCHK(m, hipMemsetAsync(s[0].dev, 0, sizeof(sums), m->stream));
+    launch_known_count(m->d, m->stream, a, max_age, (u64*)s[0].dev);
+    HIPCHK(m, hipGetLastError());
+    if ((rc = stage_end(m, s, 1)) != DSPMAP_OK) return rc;
+    out[0] = (long long)sums[0]; out[1] = (long long)sums[1];
+    return DSPMAP_OK;
+}
+
+// --------------------------------------------------- scores of candidate viewpoints (dspmap_view.hip; semantics in include/dspmap.h)
+// the table of unrotated central directions, once per handle: (1, tan alpha_h, tan beta_v) / |.| in double, rounded to fp32
+static int view_dirs(dspmap* m) {
+    if (m->ly.vw_dirs0) return DSPMAP_OK;
+    const MapDims& d = m->d;
+    std::vector<float> t((size_t)d.np * 3);
+    const double step = (double)m->cfg.angle_resolution * 3.14159265358979323846 / 180.0;
+    for (int h = 0; h < d.np_h; ++h)
+        for (int v = 0; v < d.np_v; ++v) {
+            const double y = tan(((double)h - (double)d.np_h / 2.0 + 0.5) * step), z = tan(-((double)v - (double)d.np_v / 2.0 + 0.5) * step);
+            const double len = sqrt(1.0 + y * y + z * z);
+            float* o = &t[3 * ((size_t)h * d.np_v + v)];
+            o[0] = (float)(1.0 / len); o[1] = (float)(y / len); o[2] = (float)(z / len);
+        }
+    float* dev = nullptr;
+    HIPCHK(m, hipMalloc(&dev, sizeof(float) * t.size()));
+    const hipError_t e = hipMemcpy(dev, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice);   // (synchronous: t is a local)
+    if (e != hipSuccess) { (void)hipFree(dev); HIPCHK(m, e); }
+    m->ly.vw_dirs0 = dev;
+    return DSPMAP_OK;
+}
+static void view_args_geometry(const dspmap* m, ViewArgs* a, int flags) {
+    const MapDims& d = m->d;
+    origin_fill(m, flags, a);
+    a->cx = -d.half_x + d.res * 0.5f; a->cy = -d.half_y + d.res * 0.5f; a->cz = -d.half_z + d.res * 0.5f;   // dspmap_voxel_center
+    a->dirs0 = m->ly.vw_dirs0;
+    a->reach = d.res * (float)(d.nx + d.ny + d.nz);
+}
+// the argument and state rules of every scoring entry point, in dspmap_grow_boxes' order; then the layer synchronised and the arguments filled
+static int view_check(dspmap* m, int n, const void* in, int max_age, int flags, const void* out, const char* what) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, what, "view", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative max_age %d", what, max_age);
+    if ((rc = flags_check(m, what, flags, DSPMAP_QUERY_WORLD)) != DSPMAP_OK) return rc;
+    if ((rc = whole_map_check(m, what, "a view crosses slabs")) != DSPMAP_OK) return rc;
+    if ((rc = cast_grid_ready(m, what)) != DSPMAP_OK) return rc;
+    if (!m->ly.kn_stamp || !m->ly.kn_integrated)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no frame has been integrated into the known-space layer (dspmap_known_integrate)", what);
+    return DSPMAP_OK;
+}
+static int view_args(dspmap* m, int max_age, int flags, ViewArgs* a) {
+    int rc = view_dirs(m);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = known_sync(m, &a->kn)) != DSPMAP_OK) return rc;
+    view_args_geometry(m, a, flags);
+    a->bits = m->ly.cg_bits;
+    a->max_age = max_age;
+    return DSPMAP_OK;
+}
+// (the caller has filled the arguments: view_args synchronises the known-space layer, in front of the staging copies.)  The kernel adds
+// into the scores, so they are zeroed first
+static int view_score_enqueue(dspmap* m, const ViewArgs& a, int n, const dspmap_view* dv, dspmap_view_score* ds) {
+    HIPCHK(m, hipMemsetAsync(ds, 0, sizeof(dspmap_view_score) * (size_t)n, m->stream));
+    launch_view_score(m->d, m->s, m->stream, a, n, view_chunks(m->d, n, m->n_cu, m->ly.vw_chunks), dv, ds, nullptr, nullptr);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_score_views(dspmap_t* m, int n, const dspmap_view* views, int max_age, int flags, dspmap_view_score* out) {
+    int rc = view_check(m, n, views, max_age, flags, out, "dspmap_score_views");
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    ViewArgs a;
+    if ((rc = view_args(m, max_age, flags, &a)) != DSPMAP_OK) return rc;
+    StageSec s[2] = {{views, nullptr, sizeof(dspmap_view) * (size_t)n}, {nullptr, out, sizeof(dspmap_view_score) * (size_t)n}};
+    if ((rc = stage_begin(m, s, 2)) != DSPMAP_OK) return rc;
+    if ((rc = view_score_enqueue(m, a, n, (const dspmap_view*)s[0].dev, (dspmap_view_score*)s[1].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 2);
+}
+extern "C" int dspmap_score_views_device(dspmap_t* m, int n, const dspmap_view* views, int max_age, int flags, dspmap_view_score* out) {
+    int rc = view_check(m, n, views, max_age, flags, out, "dspmap_score_views");
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    ViewArgs a;
+    if ((rc = view_args(m, max_age, flags, &a)) != DSPMAP_OK) return rc;
+    return view_score_enqueue(m, a, n, views, out);
+}
+extern "C" int dspmap_view_rays(dspmap_t* m, const float quat[4], float* planes_h, float* planes_v, float* dirs) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!quat) return dspmap_fail(m, DSPMAP_E_ARG, "dspmap_view_rays: NULL quaternion");
+    int rc = known_whole_map(m, "dspmap_view_rays");
+    if (rc != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    if ((rc = view_dirs(m)) != DSPMAP_OK) return rc;
+    const MapDims& d = m->d;
+    const size_t nh = 3 * (size_t)(d.np_h + 1), nv = 3 * (size_t)(d.np_v + 1), nd = 3 * (size_t)d.np;
+    if ((rc = query_buf(m, sizeof(float) * (nh + nv + nd))) != DSPMAP_OK) return rc;
+    ViewArgs a = {};
+    view_args_geometry(m, &a, 0);
+    float* o = (float*)m->ly.q_buf;
+    launch_view_rays(d, m->s, m->stream, a, quat, o);
+    HIPCHK(m, hipGetLastError());
+    if (planes_h) HIPCHK(m, hipMemcpyAsync(planes_h, o, sizeof(float) * nh, hipMemcpyDeviceToHost, m->stream));
+    if (planes_v) HIPCHK(m, hipMemcpyAsync(planes_v, o + nh, sizeof(float) * nv, hipMemcpyDeviceToHost, m->stream));
+    if (dirs) HIPCHK(m, hipMemcpyAsync(dirs, o + nh + nv, sizeof(float) * nd, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    return DSPMAP_OK;
+}
+// test hook: the seen set of ONE view as a bit grid in the cast grid's word layout, and the farthest returns its rays gave
+extern "C" int dspmap_debug_view_cells(dspmap_t* m, const dspmap_view* view, int flags, unsigned long long* words_out, float* ml_out) {
+    int rc = view_check(m, 1, view, 0, flags, words_out, "dspmap_debug_view_cells");
+    if (rc != DSPMAP_OK) return rc;
+    ViewArgs a;
+    if ((rc = view_args(m, 0, flags, &a)) != DSPMAP_OK) return rc;
+    const size_t lw = cast_layer_words(m->d);
+    StageSec s[4] = {{view, nullptr, sizeof(dspmap_view)}, {nullptr, nullptr, sizeof(dspmap_view_score)}, {nullptr, words_out, sizeof(u64) * lw},
+                     {nullptr, ml_out, sizeof(float) * (size_t)m->d.np}};
+    if ((rc = stage_begin(m, s, 4)) != DSPMAP_OK) return rc;
+    HIPCHK(m, hipMemsetAsync(s[1].dev, 0, (char*)s[3].dev - (char*)s[1].dev, m->stream));   // the score and the words: adjacent sections
+    launch_view_score(m->d, m->s, m->stream, a, 1, view_chunks(m->d, 1, m->n_cu, m->ly.vw_chunks), (const dspmap_view*)s[0].dev,
+                      (dspmap_view_score*)s[1].dev, (u64*)s[2].dev, (float*)s[3].dev);
+    HIPCHK(m, hipGetLastError());
+    return stage_end(m, s, 4);
+}
+
+// --------------------------------------------------- frontier cells and blocks (dspmap_frontier.hip; semantics in include/dspmap.h)
+// the layer t selects: the host twin of q_horizon (dspmap_device.h) + 1.  (t is not NaN here.)
+static int frontier_layer_host(const MapDims& d, float t) {
+    if (!(t >= 0.f) || d.T == 0) return 0;
+    int k = d.T - 1;
+    for (int j = d.T - 1; j >= 0; --j)
+        if (d.pred_t[j] >= t) k = j;
+    return k + 1;
+}
+// the buffers of a build with nb blocks: what does not depend on the block size once, the rest again when nb outgrows it
+static int frontier_alloc(dspmap* m, size_t nb) {
+    const MapDims& d = m->d;
+    const size_t lw = cast_layer_words(d);
+    if (!m->ly.fr_grid) HIPCHK(m, hipMalloc(&m->ly.fr_grid, sizeof(u64) * lw));
+    if (!m->ly.fr_cells) HIPCHK(m, hipMalloc(&m->ly.fr_cells, sizeof(int) * (size_t)d.v_glob));
+    if (!m->ly.fr_counts) HIPCHK(m, hipMalloc(&m->ly.fr_counts, 3 * sizeof(long long)));
+    if (!m->ly.fr_item_free) HIPCHK(m, hipMalloc(&m->ly.fr_item_free, sizeof(int) * lw));
+    if (nb > m->ly.fr_nb_cap) {
+        if (m->ly.fr_nb_cap) HIPCHK(m, hipStreamSynchronize(m->stream));   // (an earlier build may still write the smaller buffers)
+        for (void* q : {(void*)m->ly.fr_dense, (void*)m->ly.fr_blocks, (void*)m->ly.fr_tiles}) if (q) (void)hipFree(q);
+        m->ly.fr_dense = nullptr; m->ly.fr_blocks = nullptr; m->ly.fr_tiles = nullptr; m->ly.fr_nb_cap = 0;
+        HIPCHK(m, hipMalloc(&m->ly.fr_dense, sizeof(dspmap_frontier_block) * nb));
+        HIPCHK(m, hipMalloc(&m->ly.fr_blocks, sizeof(dspmap_frontier_block) * nb));
+        HIPCHK(m, hipMalloc(&m->ly.fr_tiles, sizeof(int) * (2 * (size_t)frontier_tiles((long long)lw) + (size_t)frontier_tiles((long long)nb))));
+        m->ly.fr_nb_cap = nb;
+    }
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_build_frontiers(dspmap_t* m, float t, int max_age, int min_unknown, int block, int flags) {
+    const char* what = "dspmap_build_frontiers";
+    if (!m) return DSPMAP_E_ARG;
+    if (t != t) return dspmap_fail(m, DSPMAP_E_ARG, "%s: t is NaN", what);
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative max_age %d", what, max_age);
+    if (min_unknown < 1 || min_unknown > 6) return dspmap_fail(m, DSPMAP_E_ARG, "%s: min_unknown %d outside [1, 6]", what, min_unknown);
+    if (block < 1 || block > DSPMAP_FRONTIER_MAX_BLOCK)
+        return dspmap_fail(m, DSPMAP_E_ARG, "%s: block %d outside [1, %d]", what, block, DSPMAP_FRONTIER_MAX_BLOCK);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: unknown flags 0x%x", what, flags);
+    int rc = whole_map_check(m, what, "a frontier crosses slabs");
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = cast_grid_ready(m, what)) != DSPMAP_OK) return rc;
+    if (!m->ly.kn_stamp || !m->ly.kn_integrated)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no frame has been integrated into the known-space layer (dspmap_known_integrate)", what);
+    const MapDims& d = m->d;
+    dspmap_layers_stale(m->ly, LAYERS_FRONTIERS_REBUILD);
+    FrontierArgs a;
+    if ((rc = known_sync(m, &a.kn)) != DSPMAP_OK) return rc;
+    a.nbx = (d.nx + block - 1) / block; a.nby = (d.ny + block - 1) / block;
+    const size_t nb = (size_t)a.nbx * a.nby * (size_t)((d.nz + block - 1) / block);   // (<= V < 2^31)
+    a.nb = (int)nb;
+    if ((rc = frontier_alloc(m, nb)) != DSPMAP_OK) return rc;
+    const size_t lw = cast_layer_words(d);
+    a.bits = m->ly.cg_bits + lw * (size_t)frontier_layer_host(d, t);
+    a.max_age = max_age; a.min_unknown = min_unknown; a.block = block;
+    a.grid = m->ly.fr_grid; a.cells = m->ly.fr_cells; a.dense = m->ly.fr_dense; a.blocks = m->ly.fr_blocks;
+    a.item_free = m->ly.fr_item_free;
+    a.tile_sum = m->ly.fr_tiles;
+    a.tile_free = m->ly.fr_tiles + frontier_tiles((long long)lw) + frontier_tiles((long long)nb);
+    a.counts = m->ly.fr_counts;
+    a.merge = m->ly.fr_merge ? 1 : 0;
+    HIPCHK(m, hipMemsetAsync(m->ly.fr_dense, 0, sizeof(dspmap_frontier_block) * nb, m->stream));
+    launch_frontiers(d, m->stream, a);
+    HIPCHK(m, hipGetLastError());
+    m->ly.fr_valid = true;
+    return DSPMAP_OK;
+}
+static int frontier_ready(dspmap* m, const char* what) {
+    return snapshot_ready(m, m->ly.fr_valid, what,
+                          "no frontiers, or the grid, the known-space layer or the position has changed since they were built (dspmap_build_frontiers)");
+}
+extern "C" int dspmap_frontier_counts(dspmap_t* m, long long out[3]) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "dspmap_frontier_counts: NULL output array");
+    const int rc = frontier_ready(m, "dspmap_frontier_counts");
+    if (rc != DSPMAP_OK) return rc;
+    return read_back(m, out, m->ly.fr_counts, 3 * sizeof(long long));
+}
+extern "C" int dspmap_get_frontier_grid(dspmap_t* m, unsigned long long* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "dspmap_get_frontier_grid: NULL output array");
+    const int rc = frontier_ready(m, "dspmap_get_frontier_grid");
+    if (rc != DSPMAP_OK) return rc;
+    return read_back(m, out, m->ly.fr_grid, sizeof(u64) * cast_layer_words(m->d));
+}
+// the first min(cap, n) entries of list `which` (0: cells, 1: blocks) of `bytes` each, and n
+static int frontier_list(dspmap* m, const char* what, int which, const void* dev, size_t bytes, int cap, void* out, int* n_out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (cap < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative capacity %d", what, cap);
+    if (!n_out || (cap > 0 && !out)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL output", what);
+    int rc = frontier_ready(m, what);
+    if (rc != DSPMAP_OK) return rc;
+    long long c[3];
+    if ((rc = read_back(m, c, m->ly.fr_counts, sizeof(c))) != DSPMAP_OK) return rc;
+    const long long n = c[which], take = n < cap ? n : cap;
+    if (take > 0 && (rc = read_back(m, out, dev, bytes * (size_t)take)) != DSPMAP_OK) return rc;
+    *n_out = (int)n;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_frontier_cells(dspmap_t* m, int cap, int* out, int* n_out) {
+    return frontier_list(m, "dspmap_get_frontier_cells", 0, m ? m->ly.fr_cells : nullptr, sizeof(int), cap, out, n_out);
+}
+extern "C" int dspmap_get_frontier_blocks(dspmap_t* m, int cap, dspmap_frontier_block* out, int* n_out) {
+    return frontier_list(m, "dspmap_get_frontier_blocks", 1, m ? m->ly.fr_blocks : nullptr, sizeof(dspmap_frontier_block), cap, out, n_out);
+}
+extern "C" const unsigned long long* dspmap_frontier_grid_device(dspmap_t* m) { return (m && m->ly.fr_valid) ? m->ly.fr_grid : nullptr; }
+extern "C" const int* dspmap_frontier_cells_device(dspmap_t* m) { return (m && m->ly.fr_valid) ? m->ly.fr_cells : nullptr; }
+extern "C" const dspmap_frontier_block* dspmap_frontier_blocks_device(dspmap_t* m) { return (m && m->ly.fr_valid) ? m->ly.fr_blocks : nullptr; }
+extern "C" const long long* dspmap_frontier_counts_device(dspmap_t* m) { return (m && m->ly.fr_valid) ? m->ly.fr_counts : nullptr; }
+// test hook: the ages of the known-space layer replaced cell by cell, written through the toroidal slot mapping
+extern "C" int dspmap_debug_set_known(dspmap_t* m, const int* age) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!age) return dspmap_fail(m, DSPMAP_E_ARG, "set known: NULL age array");
+    int rc = known_whole_map(m, "dspmap_debug_set_known");
+    if (rc != DSPMAP_OK) return rc;
+    if (m->update_counter < 1)
+        return dspmap_fail(m, DSPMAP_E_STATE, "set known: no frame has been accepted yet, there is no counter to age against (dspmap_update)");
+    const MapDims& d = m->d;
+    const size_t V = (size_t)d.v_glob;
+    for (size_t i = 0; i < V; ++i)
+        if (age[i] < -1 || age[i] > m->update_counter - 1)
+            return dspmap_fail(m, DSPMAP_E_ARG, "set known: age[%zu] = %d outside [-1, %d]", i, age[i], m->update_counter - 1);
+    READY(m);
+    BENIGN(m);
+    dspmap_layers_stale(m->ly, LAYERS_KNOWN_CHANGED);
+    if (!m->ly.kn_stamp) {
+        HIPCHK(m, hipMalloc(&m->ly.kn_stamp, sizeof(unsigned) * V));
+        HIPCHK(m, hipMemsetAsync(m->ly.kn_stamp, 0, sizeof(unsigned) * V, m->stream));
+    }
+    KnownArgs a;
+    if ((rc = known_sync(m, &a)) != DSPMAP_OK) return rc;
+    std::vector<unsigned> stamp(V);
+    auto slot = [](int i, int b, int n) { const int s = i + b; return s >= n ? s - n : s; };   // kn_slot
+    size_t g = 0;
+    for (int z = 0; z < d.nz; ++z)
+        for (int y = 0; y < d.ny; ++y) {
+            unsigned* row = &stamp[((size_t)slot(z, a.bz, d.nz) * d.ny + slot(y, a.by, d.ny)) * d.nx];
+            for (int x = 0; x < d.nx; ++x, ++g) row[slot(x, a.bx, d.nx)] = age[g] < 0 ? 0u : a.now - (unsigned)age[g];
+        }
+    HIPCHK(m, hipMemcpyAsync(m->ly.kn_stamp, stamp.data(), sizeof(unsigned) * V, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));   // (the local array is free again)
+    m->ly.kn_integrated = true;
+    return DSPMAP_OK;
+}
+
+// --------------------------------------------------- the end of the handle
+void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const char*)>& chk) {
+    const LayerState& l = m->ly;
+    for (void* q : {(void*)l.q_buf, (void*)l.df_field, (void*)l.df_g8, (void*)l.df_h16, (void*)l.cg_bits, (void*)l.cg_tmp, (void*)l.rf_field,
+                    (void*)l.rf_sets, (void*)l.tl_hist, (void*)l.tl_last, (void*)l.fc_field, (void*)l.fc_acc, (void*)l.kn_stamp, (void*)l.vw_dirs0,
+                    (void*)l.fr_grid, (void*)l.fr_cells, (void*)l.fr_counts, (void*)l.fr_item_free, (void*)l.fr_dense, (void*)l.fr_blocks,
+                    (void*)l.fr_tiles})
+        if (q) chk(hipFree(q), "hipFree");
+}
