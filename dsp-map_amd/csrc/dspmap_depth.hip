@@ -240,7 +240,10 @@ static int dp_check(dspmap* m, const dspmap_camera* cam, const void* image, floa
     if (!image) return dspmap_fail(m, DSPMAP_E_ARG, "depth: NULL image");
     if (cam->width < 1 || cam->height < 1 || cam->width > DP_MAX_SIDE || cam->height > DP_MAX_SIDE)
         return dspmap_fail(m, DSPMAP_E_ARG, "depth: image of %d x %d pixels", cam->width, cam->height);
-    if (cam->pixel_step < 1) return dspmap_fail(m, DSPMAP_E_ARG, "depth: pixel_step %d < 1", cam->pixel_step);
+    // (the upper bound keeps width + step - 1 on the host and su * step in k_dp_accumulate, lanes beyond ws included, inside an int:
+    //  su <= ws + 62 and ws * step < width + step, so su * step < 2^25 + 62 * 2^24 < 2^31)
+    if (cam->pixel_step < 1 || cam->pixel_step > DP_MAX_SIDE)
+        return dspmap_fail(m, DSPMAP_E_ARG, "depth: pixel_step %d outside 1 .. %d", cam->pixel_step, DP_MAX_SIDE);
     if (cam->format != DSPMAP_DEPTH_U16 && cam->format != DSPMAP_DEPTH_F32) return dspmap_fail(m, DSPMAP_E_ARG, "depth: unknown format %d", cam->format);
     const int eb = dp_elem_bytes(cam->format);
     if (cam->row_stride_bytes != 0 && ((long long)cam->row_stride_bytes < (long long)cam->width * eb || cam->row_stride_bytes % eb != 0))

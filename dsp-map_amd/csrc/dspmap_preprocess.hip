@@ -136,7 +136,12 @@ extern "C" int dspmap_preprocess_cloud(dspmap_t* m, int n, const float* points_d
     g.inv_leaf = 1.0f / leaf;   // inverse_leaf_size_ = Array4f::Ones() / leaf_size_
     long long cells = 1;
     for (int a = 0; a < 3; ++a) {
-        const int lo = (int)floorf(-hin[a] * g.inv_leaf), hi = (int)floorf(hin[a] * g.inv_leaf);
+        // the range test is made on the floats (as dp_ingest does): a leaf of 1e-9 m, or a denormal one whose inverse is +inf, would
+        // otherwise go through an out-of-range conversion to int and come back as a lattice of one leaf
+        const float flo = floorf(-hin[a] * g.inv_leaf), fhi = floorf(hin[a] * g.inv_leaf);
+        if (!(fhi - flo + 1.f <= (float)PP_MAX_CELLS))
+            return dspmap_fail(m, DSPMAP_E_ARG, "leaf size %.4g too small for the map box (more than %lld leaves)", leaf, (long long)PP_MAX_CELLS);
+        const int lo = (int)flo, hi = (int)fhi;
         g.min_b[a] = lo;
         g.div[a] = hi - lo + 1;
         cells *= (long long)g.div[a];

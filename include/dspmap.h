@@ -988,8 +988,8 @@ int dspmap_preprocess_cloud(dspmap_t* m, int n, const float* points_dev, int str
  * coordinate is accumulated per leaf as the 64-bit integer llrint((double)p * 2^20) (ties to even) and the centroid is
  * (float)(((double)S / (double)count) * 2^-20).  Integer sums do not depend on the order of the additions: the filtered cloud is the same
  * bits on every run, launch shape and pixel order.
- * Arguments are checked before the device is touched: a NULL handle / camera / image, width, height or pixel_step < 1 (or a side above
- * 2^24 pixels), a row stride smaller than a row or not a multiple of the element size, an unknown format, non-finite or non-positive fx,
+ * Arguments are checked before the device is touched: a NULL handle / camera / image, width, height or pixel_step < 1 (or a side or a
+ * pixel_step above 2^24: a larger step would overflow the pixel column of the tile's unused lanes), a row stride smaller than a row or not a multiple of the element size, an unknown format, non-finite or non-positive fx,
  * fy, depth_scale, non-finite cx, cy, min_depth > max_depth or a NaN among them, leaf <= 0, max_points < 0 (or NULL outputs / pose) are
  * DSPMAP_E_ARG with a text; without a usable device a valid call is DSPMAP_E_DEVICE. */
 #define DSPMAP_DEPTH_U16 0   /* raw units, value 0 = no return (RealSense / ROS 16UC1) */
@@ -1001,7 +1001,7 @@ typedef struct dspmap_camera {
     float fx, fy, cx, cy;       /* pinhole intrinsics, pixels */
     float depth_scale;          /* metres per raw unit (0.001 for millimetres, 1 for 32FC1) */
     float min_depth, max_depth; /* metres; a pixel is kept iff min_depth <= d <= max_depth */
-    int pixel_step;             /* use rows and columns 0, step, 2*step, ...; 1 = every pixel */
+    int pixel_step;             /* use rows and columns 0, step, 2*step, ...; 1 = every pixel, at most 2^24 */
 } dspmap_camera;
 /* depth image in device memory -> filtered cloud in device memory; same outputs and the same synchronous contract as
  * dspmap_preprocess_cloud(swap_axes = 1); *n_valid_out (optional) = pixels that passed the validity and range test */
