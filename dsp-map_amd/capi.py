@@ -109,6 +109,11 @@ VIEW_OK, VIEW_BLOCKED, VIEW_OUTSIDE, VIEW_INVALID = 0, 1, 3, 4
 # dspmap_frontier_block (dspmap_build_frontiers)
 FRONTIER_BLOCK_DTYPE = np.dtype([("block", "i4"), ("count", "i4"), ("sum_x", "i4"), ("sum_y", "i4"), ("sum_z", "i4"), ("unknown_faces", "i4")])
 FRONTIER_MAX_BLOCK = 32
+# dspmap_object (dspmap_build_objects): 88 bytes
+OBJECT_DTYPE = np.dtype([("label", "i4"), ("count", "i4"), ("min_x", "i4"), ("max_x", "i4"), ("min_y", "i4"), ("max_y", "i4"), ("min_z", "i4"), ("max_z", "i4"),
+                         ("sum_x", "i8"), ("sum_y", "i8"), ("sum_z", "i8"), ("mass_q", "i8"), ("mom_q", "i8", (3,))])
+OBJECTS_MAX = 1 << 20        # the largest max_objects
+OBJECT_Q = 1048576.0         # mass_q and mom_q count units of 2^-20
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -199,6 +204,15 @@ SIGNATURES = {
     "dspmap_frontier_blocks_device": (_P, [_P]),
     "dspmap_frontier_counts_device": (_P, [_P]),
     "dspmap_debug_set_known": (_i, [_P, _P]),
+    "dspmap_build_objects": (_i, [_P, _f, _i, _i, _i, _i]),
+    "dspmap_object_counts": (_i, [_P, _P]),
+    "dspmap_get_objects": (_i, [_P, _i, _P, _P]),
+    "dspmap_get_object_labels": (_i, [_P, _P]),
+    "dspmap_objects_device": (_P, [_P]),
+    "dspmap_object_labels_device": (_P, [_P]),
+    "dspmap_object_counts_device": (_P, [_P]),
+    "dspmap_query_objects": (_i, [_P, _i, _P, _i, _P]),
+    "dspmap_query_objects_device": (_i, [_P, _i, _P, _i, _P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -1157,6 +1171,97 @@ class DSPMap:
         half = np.array([cfg.nx, cfg.ny, cfg.nz], np.float64) * res / 2.0
         mean = np.stack([b["sum_x"], b["sum_y"], b["sum_z"]], 1) / np.maximum(b["count"], 1)[:, None]
         return ((mean + 0.5) * res - half).astype(np.float32)
+
+    # -- objects: components of a cast-grid layer (extension; semantics in include/dspmap.h next to dspmap_build_objects)
+    def build_objects(self, t=-1.0, connectivity=26, min_cells=1, max_objects=4096):
+        """enqueue the labelling of the layer t selects of the cast grid as it is, on the handle's stream: its connected components under
+        6- or 26-connectivity, those with at least min_cells cells as records (box, index sums, fixed-point mass and momentum from the
+        current result grid) in ascending label, the first max_objects kept, and a label grid.  Read-only towards the map and the grid;
+        the result is a snapshot of both."""
+        self._chk(self.L.dspmap_build_objects(self.h, float(t), int(connectivity), int(min_cells), int(max_objects), 0))
+
+    def object_counts(self):
+        """(n_objects, n_components, n_occupied) of the last build (synchronous): components with count >= min_cells -- also those past
+        max_objects --, all components, set bits of the layer"""
+        out = (C.c_longlong * 3)()
+        self._chk(self.L.dspmap_object_counts(self.h, C.cast(out, C.c_void_p)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def objects(self, device=None):
+        """the records the last build kept, in ascending label: structured numpy (OBJECT_DTYPE) [k], k = min(n_objects, max_objects)
+        (synchronous host copy); with device= (e.g. "cuda") an int32 tensor [k, 22] over the handle's own device buffer, without a copy
+        -- columns 0 .. 7 the ints, then the seven 64-bit fields as (low, high) pairs; `t[:, 8:].view(torch.int64)` gives them as [k, 7] --,
+        ordered with torch's current stream like frontier_cells and valid until the next build_objects or close()."""
+        n = C.c_int(0)
+        self._chk(self.L.dspmap_get_objects(self.h, 0, None, C.byref(n)))   # (synchronises the handle's stream; raises on a stale snapshot)
+        if device is not None:
+            import torch
+            dev = torch.device(device)
+            _, after = self._handle_stream_order(dev)
+            after()
+            if n.value == 0:
+                return torch.empty((0, 22), dtype=torch.int32, device=dev)
+            return torch.as_tensor(_DeviceSpan(self.L.dspmap_objects_device(self.h), (n.value, 22), "<i4"), device=dev)
+        out = np.zeros(n.value, OBJECT_DTYPE)
+        if n.value:
+            self._chk(self.L.dspmap_get_objects(self.h, n.value, _ptr(out), C.byref(n)))
+        return out
+
+    def object_labels(self, device=None):
+        """the label grid of the last build: numpy int32 [nz, ny, nx], per voxel the ordinal of its record in the list of objects (also an
+        ordinal >= max_objects), -1 for a clear bit or a component below min_cells (synchronous host copy); with device= an int32 tensor
+        of that shape over the handle's own device buffer, without a copy, as objects()"""
+        shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
+        if device is not None:
+            import torch
+            self.object_counts()   # (synchronises the handle's stream; raises on a stale snapshot)
+            dev = torch.device(device)
+            _, after = self._handle_stream_order(dev)
+            after()
+            return torch.as_tensor(_DeviceSpan(self.L.dspmap_object_labels_device(self.h), shape, "<i4"), device=dev)
+        out = np.zeros(shape, np.int32)
+        self._chk(self.L.dspmap_get_object_labels(self.h, _ptr(out)))
+        return out
+
+    def query_objects(self, q, world=False):
+        """the label-grid entry of the voxel that holds every sample {x, y, z, t} of q ([n, 4] float32; t is ignored), -1 outside the map
+        or for a NaN coordinate.  numpy in -> numpy int32 out (synchronous); a torch tensor on the GPU -> an int32 tensor on the same
+        device, enqueued on the handle's stream and ordered with torch's current stream like query_known."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(q):
+            import torch
+            q = self._device_samples(q, (4,), "query_objects")
+            n = q.numel() // 4
+            out = torch.empty(n, dtype=torch.int32, device=q.device)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_query_objects_device(self.h, n, q.data_ptr(), flags, out.data_ptr()))
+            after()
+            return out
+        q = np.ascontiguousarray(q, np.float32)
+        if q.shape[-1:] != (4,):
+            raise ValueError("query_objects: samples of shape [n, 4]")
+        n = q.size // 4
+        out = np.zeros(n, np.int32)
+        self._chk(self.L.dspmap_query_objects(self.h, n, _ptr(q), flags, _ptr(out)))
+        return out
+
+    def object_states(self, objs):
+        """what a planner takes from the records objs (OBJECT_DTYPE, what objects() returns), in the map frame: (centre [k, 3], box_lo
+        [k, 3], box_hi [k, 3], velocity [k, 3]), float32.  centre = the mean voxel index as a position, ((sum / count) + 0.5) * res -
+        half per axis (dspmap_voxel_center's expression on a mean index); box_lo / box_hi = the outer corners of the voxels min / max;
+        velocity = mom_q / mass_q in m/s, 0 where the object holds no mass."""
+        cfg = self.cfg
+        res = float(np.float32(cfg.voxel_resolution))
+        half = np.array([cfg.nx, cfg.ny, cfg.nz], np.float64) * res / 2.0
+        cnt = np.maximum(objs["count"], 1)[:, None].astype(np.float64)
+        mean = np.stack([objs["sum_x"], objs["sum_y"], objs["sum_z"]], 1) / cnt
+        lo = np.stack([objs["min_x"], objs["min_y"], objs["min_z"]], 1).astype(np.float64)
+        hi = np.stack([objs["max_x"], objs["max_y"], objs["max_z"]], 1).astype(np.float64)
+        mass = objs["mass_q"].astype(np.float64)[:, None]
+        vel = np.where(mass > 0, objs["mom_q"].astype(np.float64) / np.maximum(mass, 1.0), 0.0)
+        return (((mean + 0.5) * res - half).astype(np.float32), (lo * res - half).astype(np.float32),
+                ((hi + 1.0) * res - half).astype(np.float32), vel.astype(np.float32))
 
     def set_known(self, ages):
         """test hook: replace the ages of the known-space layer (int32 [nz, ny, nx], what known_age() returns; -1 = never, else 0 ..

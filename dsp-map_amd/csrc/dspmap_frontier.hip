@@ -19,6 +19,7 @@
 //                      Items, bits and blocks are visited in ascending order, so the lists are ascending whatever the launch.
 // No kernel waits for another workgroup: the three steps are three launches.  Nothing of the map, the grid or the layer is written.
 #include "dspmap_internal.h"
+#include "dspmap_block_scan.h"    // block_incl_scan_i
 #include "dspmap_known_slots.h"   // kn_cell, kn_age
 
 #define FR_TPB 256
@@ -92,23 +93,6 @@ __global__ void __launch_bounds__(FR_TPB) k_frontier_mark(MapDims d, FrontierArg
     atomicAdd(&b->unknown_faces, faces);
 }
 
-// inclusive scan of one int per thread over the workgroup; s_w: FR_WAVES ints
-__device__ __forceinline__ int fr_block_incl_scan(int v, int* s_w, int& total) {
-    const int inc = wave_incl_scan_i(v);
-    const int wv = (int)threadIdx.x >> 6;
-    __syncthreads();   // (s_w may still be read from an earlier scan)
-    if (lane_id() == 63) s_w[wv] = inc;
-    __syncthreads();
-    int off = 0;
-    total = 0;
-#pragma unroll
-    for (int j = 0; j < FR_WAVES; ++j) {
-        if (j < wv) off += s_w[j];
-        total += s_w[j];
-    }
-    return inc + off;
-}
-
 // what thread `tid` of tile `tile` counts: the cells of its frontier word (tiles [0, ntc)) or its block being non-empty (tiles behind)
 __device__ __forceinline__ int fr_item_count(const FrontierArgs& a, int n_items, int ntc, int tile, int tid) {
     if (tile < ntc) {
@@ -123,11 +107,11 @@ __global__ void __launch_bounds__(FR_TPB) k_frontier_sums(FrontierArgs a, int n_
     __shared__ int s_w[FR_WAVES];
     const int tile = (int)blockIdx.x;
     int total;
-    (void)fr_block_incl_scan(fr_item_count(a, n_items, ntc, tile, (int)threadIdx.x), s_w, total);
+    (void)block_incl_scan_i<FR_WAVES>(fr_item_count(a, n_items, ntc, tile, (int)threadIdx.x), s_w, total);
     if (threadIdx.x == 0) a.tile_sum[tile] = total;
     if (tile < ntc) {
         const long long i = (long long)tile * FR_TILE + threadIdx.x;
-        (void)fr_block_incl_scan(i < n_items ? a.item_free[i] : 0, s_w, total);
+        (void)block_incl_scan_i<FR_WAVES>(i < n_items ? a.item_free[i] : 0, s_w, total);
         if (threadIdx.x == 0) a.tile_free[tile] = total;
     }
 }
@@ -144,7 +128,7 @@ __global__ void __launch_bounds__(FR_TPB) k_frontier_scan(FrontierArgs a, int nt
         const int i = base + (int)threadIdx.x;
         const int v = i < n ? t[i] : 0;
         int total;
-        const int inc = fr_block_incl_scan(v, s_w, total);
+        const int inc = block_incl_scan_i<FR_WAVES>(v, s_w, total);
         if (i < n) {
             t[i] = (int)carry + inc - v;   // (n_cells <= V < 2^31)
             if (cells) fre += a.tile_free[i];
@@ -170,7 +154,7 @@ __global__ void __launch_bounds__(FR_TPB) k_frontier_emit(MapDims d, FrontierArg
     const int tile = (int)blockIdx.x, tid = (int)threadIdx.x;
     const int c = fr_item_count(a, n_items, ntc, tile, tid);
     int total;
-    const int at = a.tile_sum[tile] + fr_block_incl_scan(c, s_w, total) - c;   // where this thread's item starts in its list
+    const int at = a.tile_sum[tile] + block_incl_scan_i<FR_WAVES>(c, s_w, total) - c;   // where this thread's item starts in its list
     if (tile >= ntc) {   // (workgroup-uniform) a block record
         if (c) {
             const int i = (tile - ntc) * FR_TILE + tid;

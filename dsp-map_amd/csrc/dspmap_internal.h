@@ -72,9 +72,18 @@ struct LayerState {
     size_t fr_nb_cap = 0;
     bool fr_valid = false;
     bool fr_merge = true;            // DSPMAP_P_FRONTIER_MERGE
+    // objects (dspmap_build_objects): three arrays of V ints -- the union-find labels, per root its count and then its ordinal, the label
+    // grid --, the counts {n_objects, n_components, n_occupied, fault word} and the compaction's tile scratch, allocated by the first
+    // build; the records [ob_cap], allocated by the first build and again when a larger max_objects needs more (never more than V); all
+    // freed with the device state.  ob_valid: a snapshot of the map (mass, momentum) AND of the cast grid -- cleared with cg_valid
+    // (dspmap_snapshots_stale) and by every call that changes the grid, by nothing else
+    int* ob_parent = nullptr; int* ob_root = nullptr; int* ob_labels = nullptr; int* ob_tiles = nullptr; long long* ob_counts = nullptr;
+    dspmap_object* ob_objects = nullptr; size_t ob_cap = 0;
+    int ob_max = 0;                  // max_objects of the last build
+    bool ob_valid = false;
 };
 // What a change makes stale.  The snapshots depend on each other like this:
-//     map -> distance field, forecast, cast grid;   cast grid -> arrival fields, frontiers;   arrival fields -> timeline;
+//     map -> distance field, forecast, cast grid, objects;   cast grid -> arrival fields, frontiers, objects;   arrival fields -> timeline;
 //     known-space layer -> frontiers;               position -> frontiers
 // LAYERS_x_CHANGED: x has changed under the snapshots taken of it.  LAYERS_x_REBUILD: a build of x starts -- x itself is stale too, until the
 // build sets its flag behind its launch.  dspmap_layers_stale is the ONLY place that clears a *_valid flag, so a reader tests its own flag alone.
@@ -87,19 +96,21 @@ enum LayerChange {
     LAYERS_POSITION_CHANGED,
     LAYERS_FRONTIERS_REBUILD,
     LAYERS_DISTANCE_REBUILD,
-    LAYERS_FORECAST_REBUILD
+    LAYERS_FORECAST_REBUILD,
+    LAYERS_OBJECTS_REBUILD
 };
 inline void dspmap_layers_stale(LayerState& l, LayerChange c) {
     switch (c) {   // (the first four cases are one chain: each falls through to what depends on it)
     case LAYERS_MAP_CHANGED: l.df_valid = false; l.fc_valid = false; [[fallthrough]];
     case LAYERS_CAST_GRID_REBUILD: l.cg_valid = false; [[fallthrough]];
-    case LAYERS_CAST_GRID_CHANGED: l.fr_valid = false; [[fallthrough]];
+    case LAYERS_CAST_GRID_CHANGED: l.fr_valid = false; l.ob_valid = false; [[fallthrough]];
     case LAYERS_REACH_REBUILD: l.rf_valid = false; l.tl_valid = false; break;
     case LAYERS_KNOWN_CHANGED:
     case LAYERS_POSITION_CHANGED:
     case LAYERS_FRONTIERS_REBUILD: l.fr_valid = false; break;
     case LAYERS_DISTANCE_REBUILD: l.df_valid = false; break;
     case LAYERS_FORECAST_REBUILD: l.fc_valid = false; break;
+    case LAYERS_OBJECTS_REBUILD: l.ob_valid = false; break;
     }
 }
 
@@ -293,7 +304,7 @@ struct dspmap {
 };
 
 // everything that computes a frame or replaces state calls this: the distance field, the cast grid, the arrival fields grown in it, the
-// frontiers found in it and the forecast are snapshots of the map before it
+// frontiers and the objects found in it and the forecast are snapshots of the map before it
 inline void dspmap_snapshots_stale(dspmap* m) { dspmap_layers_stale(m->ly, LAYERS_MAP_CHANGED); }
 // dspmap_layers.hip: everything the known-space layer holds forgotten (a new state: dspmap_clear_state, dspmap_load_checkpoint), and the
 // layers' device buffers released (free_dev; chk reports a failed call)

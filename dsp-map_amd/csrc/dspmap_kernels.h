@@ -312,6 +312,22 @@ struct FrontierArgs {
     int merge;           // DSPMAP_P_FRONTIER_MERGE: block sums per (wave, block) instead of per cell
 };
 void launch_frontiers(const MapDims& d, hipStream_t stream, const FrontierArgs& a);
+// objects: the connected components of one layer of the cast grid (dspmap_objects.hip; semantics in include/dspmap.h, dspmap_build_objects)
+struct dspmap_object;
+#define OBJ_COUNTS 4   // long longs of the counts buffer: {n_objects, n_components, n_occupied} and the fault word
+struct ObjectArgs {
+    const u64* bits;     // [nz][ny][W] the SELECTED layer of the cast grid
+    int conn;            // 6 or 26
+    int min_cells, max_objects;
+    int* parent;         // [V] union-find labels, -1 for a clear bit; after the flattening the root (= smallest voxel index) of the cell's component
+    int* root_val;       // [V] zeroed by the caller: per root its cell count, then its ordinal (-1 below min_cells)
+    int* labels;         // out [V] the label grid
+    struct dspmap_object* objects;   // out [min(max_objects, V)]
+    int* tile_sum;       // scratch [tiles of V]
+    long long* counts;   // out [OBJ_COUNTS], zeroed by the caller
+};
+void launch_objects(const LaunchCtx& c, const ObjectArgs& a);
+void launch_objects_query(const LaunchCtx& c, const int* labels, int world, const float cur[3], int n, const float4* q, int* out);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

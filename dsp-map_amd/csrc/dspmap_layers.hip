@@ -1211,12 +1211,134 @@ extern "C" int dspmap_debug_set_known(dspmap_t* m, const int* age) {
     return DSPMAP_OK;
 }
 
+// --------------------------------------------------- objects: components of a cast-grid layer (dspmap_objects.hip; semantics in include/dspmap.h)
+#define DSPMAP_OBJECTS_MAX (1 << 20)
+// the buffers of a build that keeps `cap` records: what depends on V alone once, the records again when cap outgrows them
+static int objects_alloc(dspmap* m, size_t cap) {
+    const size_t V = (size_t)m->d.v_glob;
+    if (!m->ly.ob_parent) HIPCHK(m, hipMalloc(&m->ly.ob_parent, sizeof(int) * V));
+    if (!m->ly.ob_root) HIPCHK(m, hipMalloc(&m->ly.ob_root, sizeof(int) * V));
+    if (!m->ly.ob_labels) HIPCHK(m, hipMalloc(&m->ly.ob_labels, sizeof(int) * V));
+    if (!m->ly.ob_tiles) HIPCHK(m, hipMalloc(&m->ly.ob_tiles, sizeof(int) * (size_t)frontier_tiles((long long)V)));
+    if (!m->ly.ob_counts) HIPCHK(m, hipMalloc(&m->ly.ob_counts, OBJ_COUNTS * sizeof(long long)));
+    if (cap > m->ly.ob_cap) {
+        if (m->ly.ob_cap) HIPCHK(m, hipStreamSynchronize(m->stream));   // (an earlier build may still write the smaller buffer)
+        if (m->ly.ob_objects) { (void)hipFree(m->ly.ob_objects); m->ly.ob_objects = nullptr; m->ly.ob_cap = 0; }
+        HIPCHK(m, hipMalloc(&m->ly.ob_objects, sizeof(dspmap_object) * cap));
+        m->ly.ob_cap = cap;
+    }
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_build_objects(dspmap_t* m, float t, int connectivity, int min_cells, int max_objects, int flags) {
+    const char* what = "dspmap_build_objects";
+    if (!m) return DSPMAP_E_ARG;
+    if (t != t) return dspmap_fail(m, DSPMAP_E_ARG, "%s: t is NaN", what);
+    if (connectivity != 6 && connectivity != 26) return dspmap_fail(m, DSPMAP_E_ARG, "%s: connectivity %d is neither 6 nor 26", what, connectivity);
+    if (min_cells < 1) return dspmap_fail(m, DSPMAP_E_ARG, "%s: min_cells %d below 1", what, min_cells);
+    if (max_objects < 1 || max_objects > DSPMAP_OBJECTS_MAX)
+        return dspmap_fail(m, DSPMAP_E_ARG, "%s: max_objects %d outside [1, %d]", what, max_objects, DSPMAP_OBJECTS_MAX);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: unknown flags 0x%x", what, flags);
+    int rc = whole_map_check(m, what, "components cross slabs");
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = cast_grid_ready(m, what)) != DSPMAP_OK) return rc;
+    const MapDims& d = m->d;
+    const size_t V = (size_t)d.v_glob;
+    dspmap_layers_stale(m->ly, LAYERS_OBJECTS_REBUILD);
+    if ((rc = objects_alloc(m, (size_t)max_objects < V ? (size_t)max_objects : V)) != DSPMAP_OK) return rc;
+    ObjectArgs a;
+    a.bits = m->ly.cg_bits + cast_layer_words(d) * (size_t)frontier_layer_host(d, t);
+    a.conn = connectivity; a.min_cells = min_cells; a.max_objects = max_objects;
+    a.parent = m->ly.ob_parent; a.root_val = m->ly.ob_root; a.labels = m->ly.ob_labels; a.objects = m->ly.ob_objects;
+    a.tile_sum = m->ly.ob_tiles; a.counts = m->ly.ob_counts;
+    HIPCHK(m, hipMemsetAsync(m->ly.ob_root, 0, sizeof(int) * V, m->stream));
+    HIPCHK(m, hipMemsetAsync(m->ly.ob_counts, 0, OBJ_COUNTS * sizeof(long long), m->stream));
+    launch_objects(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    m->ly.ob_max = max_objects;
+    m->ly.ob_valid = true;
+    return DSPMAP_OK;
+}
+static int objects_ready(dspmap* m, const char* what) {
+    return snapshot_ready(m, m->ly.ob_valid, what, "no objects, or the map or its cast grid has changed since they were built (dspmap_build_objects)");
+}
+// the counts of the valid build, read back; a non-zero fault word (the labelling met a broken invariant or ran out of a trip bound) is an error
+static int objects_counts(dspmap* m, const char* what, long long c[OBJ_COUNTS]) {
+    const int rc = read_back(m, c, m->ly.ob_counts, OBJ_COUNTS * sizeof(long long));
+    if (rc != DSPMAP_OK) return rc;
+    if (c[3] != 0) return dspmap_fail(m, DSPMAP_E_DEVICE, "%s: the labelling of the last dspmap_build_objects gave up (fault word 0x%llx)", what, (unsigned long long)c[3]);
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_object_counts(dspmap_t* m, long long out[3]) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "dspmap_object_counts: NULL output array");
+    int rc = objects_ready(m, "dspmap_object_counts");
+    if (rc != DSPMAP_OK) return rc;
+    long long c[OBJ_COUNTS];
+    if ((rc = objects_counts(m, "dspmap_object_counts", c)) != DSPMAP_OK) return rc;
+    out[0] = c[0]; out[1] = c[1]; out[2] = c[2];
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_objects(dspmap_t* m, int cap, dspmap_object* out, int* n_out) {
+    const char* what = "dspmap_get_objects";
+    if (!m) return DSPMAP_E_ARG;
+    if (cap < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative capacity %d", what, cap);
+    if (!n_out || (cap > 0 && !out)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL output", what);
+    int rc = objects_ready(m, what);
+    if (rc != DSPMAP_OK) return rc;
+    long long c[OBJ_COUNTS];
+    if ((rc = objects_counts(m, what, c)) != DSPMAP_OK) return rc;
+    const long long n = c[0] < m->ly.ob_max ? c[0] : m->ly.ob_max, take = n < cap ? n : cap;   // the records the build kept
+    if (take > 0 && (rc = read_back(m, out, m->ly.ob_objects, sizeof(dspmap_object) * (size_t)take)) != DSPMAP_OK) return rc;
+    *n_out = (int)n;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_object_labels(dspmap_t* m, int* out) {
+    const char* what = "dspmap_get_object_labels";
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL output array", what);
+    int rc = objects_ready(m, what);
+    if (rc != DSPMAP_OK) return rc;
+    long long c[OBJ_COUNTS];
+    if ((rc = objects_counts(m, what, c)) != DSPMAP_OK) return rc;
+    return read_back(m, out, m->ly.ob_labels, sizeof(int) * (size_t)m->d.v_glob);
+}
+extern "C" const dspmap_object* dspmap_objects_device(dspmap_t* m) { return (m && m->ly.ob_valid) ? m->ly.ob_objects : nullptr; }
+extern "C" const int* dspmap_object_labels_device(dspmap_t* m) { return (m && m->ly.ob_valid) ? m->ly.ob_labels : nullptr; }
+extern "C" const long long* dspmap_object_counts_device(dspmap_t* m) { return (m && m->ly.ob_valid) ? m->ly.ob_counts : nullptr; }
+static int objects_query_check(dspmap* m, int n, const void* in, const void* out, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, "objects query", "sample", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = flags_check(m, "objects query", flags, DSPMAP_QUERY_WORLD)) != DSPMAP_OK) return rc;
+    return objects_ready(m, "dspmap_query_objects");
+}
+static int objects_query_enqueue(dspmap* m, int n, const float4* dq, int flags, int* dout) {
+    launch_objects_query(dspmap_ctx_of(m), m->ly.ob_labels, (flags & DSPMAP_QUERY_WORLD) ? 1 : 0, m->cur_pos, n, dq, dout);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_objects(dspmap_t* m, int n, const dspmap_query* q, int flags, int* ordinal_out) {
+    int rc = objects_query_check(m, n, q, ordinal_out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[2] = {{q, nullptr, sizeof(dspmap_query) * (size_t)n}, {nullptr, ordinal_out, sizeof(int) * (size_t)n}};
+    if ((rc = stage_begin(m, s, 2)) != DSPMAP_OK) return rc;
+    if ((rc = objects_query_enqueue(m, n, (const float4*)s[0].dev, flags, (int*)s[1].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 2);
+}
+extern "C" int dspmap_query_objects_device(dspmap_t* m, int n, const dspmap_query* q, int flags, int* ordinal_out) {
+    const int rc = objects_query_check(m, n, q, ordinal_out, flags);
+    if (rc != DSPMAP_OK) return rc;
+    return objects_query_enqueue(m, n, (const float4*)q, flags, ordinal_out);
+}
+
 // --------------------------------------------------- the end of the handle
 void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const char*)>& chk) {
     const LayerState& l = m->ly;
     for (void* q : {(void*)l.q_buf, (void*)l.df_field, (void*)l.df_g8, (void*)l.df_h16, (void*)l.cg_bits, (void*)l.cg_tmp, (void*)l.rf_field,
                     (void*)l.rf_sets, (void*)l.tl_hist, (void*)l.tl_last, (void*)l.fc_field, (void*)l.fc_acc, (void*)l.kn_stamp, (void*)l.vw_dirs0,
                     (void*)l.fr_grid, (void*)l.fr_cells, (void*)l.fr_counts, (void*)l.fr_item_free, (void*)l.fr_dense, (void*)l.fr_blocks,
-                    (void*)l.fr_tiles})
+                    (void*)l.fr_tiles, (void*)l.ob_parent, (void*)l.ob_root, (void*)l.ob_labels, (void*)l.ob_tiles, (void*)l.ob_counts,
+                    (void*)l.ob_objects})
         if (q) chk(hipFree(q), "hipFree");
 }

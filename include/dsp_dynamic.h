@@ -353,6 +353,18 @@ public:
     }
     int getFrontierCells(int cap, int* cells, int& n) { return dspmap_get_frontier_cells(h_, cap, cells, &n); }
     int getFrontierBlocks(int cap, dspmap_frontier_block* blocks, int& n) { return dspmap_get_frontier_blocks(h_, cap, blocks, &n); }
+    /* extension: objects (dspmap_build_objects in dspmap.h): the connected components (connectivity 6 or 26) of the layer t selects of
+     * the cast grid, those with at least min_cells cells as records -- box, index sums (centroid = sum / count), fixed-point mass and
+     * momentum of the current result grid (velocity = mom_q / mass_q) -- in ascending label, at most max_objects of them.  buildObjects
+     * enqueues; getObjects copies the first min(cap, n) records and reports n; queryObjects gives, per sample {x, y, z, t} (t ignored),
+     * the ordinal of the object that holds it or -1.  Return DSPMAP_OK or a negative error code. */
+    int buildObjects(int connectivity = 26, int min_cells = 1, int max_objects = 4096, float t = -1.f) {
+        return dspmap_build_objects(h_, t, connectivity, min_cells, max_objects, 0);
+    }
+    int getObjects(int cap, dspmap_object* objects, int& n) { return dspmap_get_objects(h_, cap, objects, &n); }
+    int queryObjects(int n, const dspmap_query* samples, int* ordinals, bool world = false) {
+        return dspmap_query_objects(h_, n, samples, world ? DSPMAP_QUERY_WORLD : 0, ordinals);
+    }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

@@ -866,6 +866,80 @@ const dspmap_frontier_block* dspmap_frontier_blocks_device(dspmap_t* m);
 const long long* dspmap_frontier_counts_device(dspmap_t* m);
 int dspmap_debug_set_known(dspmap_t* m, const int* age_host);
 
+/* ---- objects: the connected components of one layer of the cast grid, each with its box, the sums behind its centroid, and the mass
+ * and momentum the filter holds in its cells (no counterpart in the reference).  "There are five obstacles, this one is 0.6 x 0.4 x 1.7 m,
+ * centred here, moving at (0.8, -0.1) m/s" is the input of every MPC or velocity-obstacle planner, and the one product of this map that
+ * a static occupancy grid cannot give: the filter estimates a mean velocity per voxel (voxels_objects_number[v][1..3],
+ * dspmap_get_results), this groups the voxels.  One layer, integers only, no tracking across frames.  An extension beside the frame,
+ * like the sections above: the frame path, its launch chain, the captured graph and the parameter ring do not know about it.
+ *
+ *  Input: the grid of the last dspmap_build_cast_grid EXACTLY AS IT IS (inflated, masked or replaced through
+ *  dspmap_debug_set_cast_grid).  t selects ONE layer as for dspmap_build_frontiers: layer 0 for t < 0 or a map without horizons, else
+ *  layer 1 + k(t) with the k(t) of dspmap_query_occupancy.
+ *  Components: two cells with set bits are adjacent under connectivity 6 when they share a face, under 26 when they share a face, an edge
+ *  or a corner.  Cells outside the map do not exist.  The objects are the connected components of the set cells; the label of a
+ *  component is the smallest voxel index (the reference's voxel order, :1081) among its cells.
+ *  Record: dspmap_object, 88 bytes, all integers -- the label, count = its cells, the box min / max per axis in voxel indices
+ *  (inclusive), sum_x, sum_y, sum_z = the sums of its cells' voxel indices per axis, and mass_q, mom_q[3]: mass and momentum in units
+ *  of 2^-20, summed over the object's cells from the CURRENT result grid, bit for bit what dspmap_get_results returns, in fixed point so
+ *  that the order of arrival cannot matter.  Every named operation is rounded to fp32 on its own.  With w = res[v][0], u_a = res[v][1 + a]:
+ *   - a cell contributes to mass_q iff w is finite and 0 < w < 4096: (long long)fl(w * 1048576.0f), the C cast, truncating (the product
+ *     is exact);
+ *   - the same cell contributes to mom_q[a] iff u_a is finite and |fl(w * u_a)| < 4096: (long long)fl(fl(w * u_a) * 1048576.0f);
+ *   - every other cell contributes 0.
+ *  A contribution is below 2^32 in magnitude and a map has fewer than 2^31 cells (dspmap_create's limit), so every sum stays below 2^63;
+ *  the index sums stay below 2^31 * 2^10.  For a predicted layer (t >= 0) the two sums still say what the filter holds in that region NOW:
+ *  the cells are those of the predicted layer, mass and velocity those of the current result grid.  The host derives centroid = sum /
+ *  count (a mean voxel index is the centre of that voxel) and velocity = mom_q / mass_q.
+ *  One build gives, all integers, defined bit for bit and independent of the launch:
+ *   1. the records of the components with count >= min_cells in ASCENDING label; the first max_objects of them are kept, the counts
+ *      still report all of them;
+ *   2. a label grid of V ints in the reference's voxel order: the ordinal of the voxel's record in that list -- an ordinal >= max_objects
+ *      included --, -1 for a clear bit or a component below min_cells;
+ *   3. the counts {n_objects, n_components, n_occupied}: the components with count >= min_cells, all components, the set bits of the layer.
+ *
+ *  - dspmap_build_objects: enqueued on the handle's stream behind the grid's build and the frame, no synchronisation.
+ *  - dspmap_object_counts, dspmap_get_object_labels: host copies, synchronous.  dspmap_get_objects copies the first min(cap, n) records
+ *    and sets *n_out = n, the records the build kept (min(n_objects, max_objects)); out_host may be NULL for cap == 0 (the convention of
+ *    dspmap_get_frontier_cells).
+ *  - dspmap_objects_device, dspmap_object_labels_device, dspmap_object_counts_device: the device buffers of the last build, NULL when
+ *    there is none or it is stale; valid once the handle's stream has reached the build, until the next build or the handle's
+ *    destruction.  The counts buffer holds a fourth word behind the three counts: 0, or why the labelling gave up (below).
+ *  - dspmap_query_objects*: the label-grid entry of the voxel that holds the sample (dspmap_point_voxel_index's expression); samples,
+ *    frame convention and DSPMAP_QUERY_WORLD as in dspmap_query_known; t is ignored.  -1 outside the map or for a NaN coordinate.  The
+ *    _device variant only enqueues.
+ *  - arguments, checked before the device is touched and in this order, DSPMAP_E_ARG with a text: a NULL handle, a NaN t, connectivity
+ *    not 6 or 26, min_cells < 1, max_objects outside [1, 2^20], flags != 0; a NULL output, cap < 0, n < 0, flags other than
+ *    DSPMAP_QUERY_WORLD.  Then a sharded handle (slab) is DSPMAP_E_STATE (components cross slabs); then a stale or never-built grid is
+ *    DSPMAP_E_STATE with a text naming dspmap_build_cast_grid.  Accessors and queries without a valid build are DSPMAP_E_STATE with a
+ *    text naming dspmap_build_objects.
+ *  - the labelling is a union-find on labels that only ever decrease, in launches of its own; no kernel waits for another workgroup and
+ *    every loop has a trip bound, so it cannot hang.  Should a bound ever run out, the build records it and the synchronous accessors
+ *    return DSPMAP_E_DEVICE.
+ *  - life cycle.  The result is a snapshot of the map and of the grid.  It goes stale with everything that makes the cast grid stale and
+ *    with every dspmap_build_cast_grid, dspmap_mask_cast_grid and dspmap_debug_set_cast_grid -- not with builds of arrival fields,
+ *    distance fields, forecasts or frontiers, not with the known-space calls, not with dspmap_set_current_position.
+ *  - read-only towards the map and the grid; the captured frame and its parameter ring are untouched.  The first build allocates three
+ *    arrays of V ints, min(max_objects, V) records (more when a later build asks for more) and a few bytes of scan scratch per 256
+ *    voxels; all of it is freed with the device state.  A handle that never builds objects allocates nothing. */
+typedef struct dspmap_object {
+    int label;                        /* smallest voxel index of the component */
+    int count;                        /* its cells, >= min_cells */
+    int min_x, max_x, min_y, max_y, min_z, max_z;   /* box in voxel indices, inclusive */
+    long long sum_x, sum_y, sum_z;    /* sums of voxel indices per axis */
+    long long mass_q;                 /* units of 2^-20 */
+    long long mom_q[3];               /* units of 2^-20 m/s */
+} dspmap_object;
+int dspmap_build_objects(dspmap_t* m, float t, int connectivity, int min_cells, int max_objects, int flags /* must be 0 */);
+int dspmap_object_counts(dspmap_t* m, long long out[3]);                  /* {n_objects, n_components, n_occupied}; synchronous */
+int dspmap_get_objects(dspmap_t* m, int cap, dspmap_object* out_host, int* n_out);
+int dspmap_get_object_labels(dspmap_t* m, int* out_host);                 /* V ints; synchronous */
+const dspmap_object* dspmap_objects_device(dspmap_t* m);
+const int* dspmap_object_labels_device(dspmap_t* m);
+const long long* dspmap_object_counts_device(dspmap_t* m);
+int dspmap_query_objects(dspmap_t* m, int n, const dspmap_query* q_host, int flags, int* ordinal_out_host);
+int dspmap_query_objects_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, int* ordinal_out_dev);
+
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
 int dspmap_point_voxel_index(const dspmap_t* m, float px, float py, float pz, int* index);
