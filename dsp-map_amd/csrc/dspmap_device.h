@@ -530,6 +530,18 @@ __device__ __forceinline__ int claim_slot(u64* mask, int lv, const MapDims& d) {
 // the first look and the kernel boundary in front of the waiter has already made the data visible; after a real wait an acquire fence
 // drops what the caches may hold.  A wait is bounded (200 ms of the 100 MHz wall clock): the pairing of the two queues is the host's job
 // and a missing partner must not hang the device -- the give-up is noted in host-mapped memory and the next call fails on it.
+// a parameter block that arrived as a KERNEL ARGUMENT, stored for the kernels that follow (one lane).  Member by member: a whole-struct
+// assignment can make the compiler keep a per-lane copy of the argument, and behind a barrier that copy landed in LDS (60 bytes x 256 lanes,
+// seen with tools/kernel_resources.sh)
+__device__ __forceinline__ void store_frame_params(FrameParams* __restrict__ dst, const FrameParams& v) {
+    static_assert(sizeof(FrameParams) == 96, "a new member of FrameParams: copy it below");
+    dst->quat[0] = v.quat[0]; dst->quat[1] = v.quat[1]; dst->quat[2] = v.quat[2]; dst->quat[3] = v.quat[3];
+    dst->cur_pos[0] = v.cur_pos[0]; dst->cur_pos[1] = v.cur_pos[1]; dst->cur_pos[2] = v.cur_pos[2];
+    dst->od[0] = v.od[0]; dst->od[1] = v.od[1]; dst->od[2] = v.od[2];
+    dst->dt = v.dt; dst->n_pts = v.n_pts; dst->n_birth = v.n_birth; dst->static_birth = v.static_birth;
+    dst->res_filter = v.res_filter; dst->epoch = v.epoch; dst->clear_fut = v.clear_fut; dst->from_ring = v.from_ring;
+    dst->ring_pos = v.ring_pos; dst->birth_reach = v.birth_reach; dst->pts = v.pts; dst->birth = v.birth;
+}
 __device__ __forceinline__ void xq_publish(int* word, int seq) {
     __hip_atomic_store(word, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

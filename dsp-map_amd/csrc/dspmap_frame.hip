@@ -640,6 +640,8 @@ int dspmap_device_frame(dspmap* m, int n_points, const float* points_dev, int n_
     } else {
         if (m->frame_ring) { rc = queue_estimator(); if (rc != DSPMAP_OK) return rc; }
         m->branch_pending = false;
+        // plain launches can carry this frame's values as kernel arguments: the block as it stands in the ring slot (dspmap_ring_push)
+        if (m->frame_ring) c.hpv = &m->hp;
         enqueue_frame(m, c, n_points, nb_grid, mode == 1, mode == 2);
         if (m->branch_pending) ++m->branch_frames;
         if (m->frame_ring) ++m->plain_frames;

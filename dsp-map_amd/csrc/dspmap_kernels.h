@@ -66,6 +66,9 @@ struct LaunchCtx {
     int side_wg = 3;          // workgroups per CU of the side-stream placement (sel = 0; DSPMAP_P_SIDE_PLACEMENT)
     bool branches = false;   // this frame runs as two branches (DSPMAP_P_FRAME_BRANCHES; see KernelScratch::tile_cls)
     bool sparse = false; // most tiles hold nothing (dspmap::sparse_mode): k_predict's variant that leaves such tiles first
+    const FrameParams* hpv = nullptr;   // (host memory) a frame queued as PLAIN launches through the parameter ring: the block that was just pushed into its ring
+                                        // slot -- the frame's first kernel takes it as a kernel argument instead of reading it back over the bus.
+                                        // nullptr: a captured frame (frozen arguments), or no ring
 };
 
 // frame setup: rotate boundary planes (:226-232), reset per-frame counters/bins (:235-238)

@@ -67,8 +67,12 @@ __global__ void k_reset(MapDims d, DevState s, int flags) {
 // k_obs_points: one thread per input point: rotate into the world-aligned
 // sensor-centred frame (:247), FOV test (:250), pyramid cell (:260-263), range (:266).
 // --------------------------------------------------------------------------
-template <bool FUSED>
-__global__ void __launch_bounds__(256) k_obs_points(MapDims d, DevState s, const FrameParams* __restrict__ ring, int ring_mask, int bits_blk0) {
+// BYVAL (a whole frame queued as plain launches): the host knows every word of the frame's parameter block when it launches -- `pv` IS the
+// block (the ring slot's contents, from_ring and ring_pos included), a kernel argument: no look at the ring's read position and no read over
+// the bus in front of the kernel's first useful load.  The ring slot is still filled and k_predict still advances the read position, so a
+// replayed frame finds the ring where a run of plain frames left it.
+template <bool FUSED, bool BYVAL = false>
+__global__ void __launch_bounds__(256) k_obs_points(MapDims d, DevState s, const FrameParams* __restrict__ ring, int ring_mask, int bits_blk0, FrameParams pv) {
     // bits_blk0 >= 0 (sparse whole frames): the workgroups from that index on rebuild the tile bitmaps from the per-tile flags, 256 tiles
     // each (DevState::vis_bits): whatever wrote the flags since the last frame -- a frame, an import, a restored checkpoint -- is in them
     if (FUSED && bits_blk0 >= 0 && (int)blockIdx.x >= bits_blk0) {
@@ -89,17 +93,18 @@ __global__ void __launch_bounds__(256) k_obs_points(MapDims d, DevState s, const
     // also stores it in HBM for the kernels that follow.  The ring's read position is advanced by k_predict, after every
     // workgroup here has used it.
     const FrameParams* __restrict__ fpp = s.fpar;
-    if (FUSED && ring) {
+    if (FUSED && !BYVAL && ring) {
         fpp = ring + (*s.ring_seq & ring_mask);
         if (blockIdx.x == 0 && threadIdx.x < sizeof(FrameParams) / 4)
             reinterpret_cast<int*>(s.fpar)[threadIdx.x] = reinterpret_cast<const int*>(fpp)[threadIdx.x];
     }
-    const int n_pts = fpp->n_pts;
-    const float* __restrict__ pts = fpp->pts;
-    const float qw = fpp->quat[0], qx = fpp->quat[1], qy = fpp->quat[2], qz = fpp->quat[3];
-    const float cpx = fpp->cur_pos[0], cpy = fpp->cur_pos[1], cpz = fpp->cur_pos[2];
+    if (BYVAL && blockIdx.x == 0 && threadIdx.x == 0) store_frame_params(s.fpar, pv);   // (one lane: the kernels that follow read the copy)
+    const int n_pts = BYVAL ? pv.n_pts : fpp->n_pts;
+    const float* __restrict__ pts = BYVAL ? pv.pts : fpp->pts;
+    const float qw = BYVAL ? pv.quat[0] : fpp->quat[0], qx = BYVAL ? pv.quat[1] : fpp->quat[1], qy = BYVAL ? pv.quat[2] : fpp->quat[2], qz = BYVAL ? pv.quat[3] : fpp->quat[3];
+    const float cpx = BYVAL ? pv.cur_pos[0] : fpp->cur_pos[0], cpy = BYVAL ? pv.cur_pos[1] : fpp->cur_pos[1], cpz = BYVAL ? pv.cur_pos[2] : fpp->cur_pos[2];
     (void)cpx; (void)cpy; (void)cpz;
-    const int make_static_birth = fpp->static_birth;
+    const int make_static_birth = BYVAL ? pv.static_birth : fpp->static_birth;
     const float q[4] = {qw, qx, qy, qz};
     __shared__ float s_ph[DSP_MAX_PLANES_H * 3];
     __shared__ float s_pv[DSP_MAX_PLANES_V * 3];
@@ -143,7 +148,7 @@ __global__ void __launch_bounds__(256) k_obs_points(MapDims d, DevState s, const
         s.pt_rot[i] = make_float4(r[0], r[1], r[2], len);
         s.pt_pyr[i] = pyr;
         // the view is not empty: this frame's synthesised birth cloud is the live one (dspmap_birth.h, BirthView)
-        if (make_static_birth == 1 && pyr >= 0) s.fs->view_epoch = fpp->epoch;
+        if (make_static_birth == 1 && pyr >= 0) s.fs->view_epoch = BYVAL ? pv.epoch : fpp->epoch;
     }
 }
 
@@ -1610,11 +1615,13 @@ void launch_frame_setup(const LaunchCtx& c, bool reset_obs) {
 void launch_setup_and_bin(const LaunchCtx& c, int n_pts_grid, bool gather, const FrameParams* ring, int ring_mask) {   // whole frame: launch_frame_setup(c, true) + launch_obs_bin
     const int grid = n_pts_grid > 0 ? (n_pts_grid + 255) / 256 : 1;
     const int nbits = c.tile_bits ? (c.k.ntiles + 255) / 256 : 0;   // the bitmap rebuild rides along (sparse whole frames)
-    hipLaunchKernelGGL(k_obs_points<true>, dim3(grid + nbits), dim3(256), 0, c.stream, c.d, c.s, ring, ring_mask, c.tile_bits ? grid : -1);
+    // (c.hpv: a frame queued as plain launches -- the block the host has just put into the ring slot goes along as a kernel argument)
+    if (ring && c.hpv) hipLaunchKernelGGL((k_obs_points<true, true>), dim3(grid + nbits), dim3(256), 0, c.stream, c.d, c.s, ring, ring_mask, c.tile_bits ? grid : -1, *c.hpv);
+    else hipLaunchKernelGGL(k_obs_points<true>, dim3(grid + nbits), dim3(256), 0, c.stream, c.d, c.s, ring, ring_mask, c.tile_bits ? grid : -1, FrameParams{});
     if (gather) hipLaunchKernelGGL(k_obs_gather, dim3(c.d.np), dim3(WAVE), 0, c.stream, c.d, c.s);
 }
 void launch_obs_bin(const LaunchCtx& c, int n_pts_grid) {
-    if (n_pts_grid > 0) hipLaunchKernelGGL(k_obs_points<false>, dim3((n_pts_grid + 255) / 256), dim3(256), 0, c.stream, c.d, c.s, (const FrameParams*)nullptr, 0, -1);
+    if (n_pts_grid > 0) hipLaunchKernelGGL(k_obs_points<false>, dim3((n_pts_grid + 255) / 256), dim3(256), 0, c.stream, c.d, c.s, (const FrameParams*)nullptr, 0, -1, FrameParams{});
     hipLaunchKernelGGL(k_obs_gather, dim3(c.d.np), dim3(WAVE), 0, c.stream, c.d, c.s);
 }
 
