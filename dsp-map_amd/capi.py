@@ -114,6 +114,11 @@ OBJECT_DTYPE = np.dtype([("label", "i4"), ("count", "i4"), ("min_x", "i4"), ("ma
                          ("sum_x", "i8"), ("sum_y", "i8"), ("sum_z", "i8"), ("mass_q", "i8"), ("mom_q", "i8", (3,))])
 OBJECTS_MAX = 1 << 20        # the largest max_objects
 OBJECT_Q = 1048576.0         # mass_q and mom_q count units of 2^-20
+# dspmap_track (dspmap_track_update): 72 bytes
+TRACK_DTYPE = np.dtype([("id", "i8"), ("parent", "i8"), ("prev_sum_x", "i8"), ("prev_sum_y", "i8"), ("prev_sum_z", "i8"), ("prev_count", "i4"),
+                        ("prev_ordinal", "i4"), ("age", "i4"), ("born_seq", "i4"), ("overlap", "i4"), ("shift_x", "i4"), ("shift_y", "i4"), ("shift_z", "i4")])
+TRACK_PER_CELL = 1           # DSPMAP_TRACK_PER_CELL
+TRACK_MAX_SHIFT = 64         # the largest max_shift
 
 # every symbol include/dspmap.h declares: name -> (restype, argtypes)
 _P, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
@@ -213,6 +218,12 @@ SIGNATURES = {
     "dspmap_object_counts_device": (_P, [_P]),
     "dspmap_query_objects": (_i, [_P, _i, _P, _i, _P]),
     "dspmap_query_objects_device": (_i, [_P, _i, _P, _i, _P]),
+    "dspmap_track_update": (_i, [_P, _f, _i, _i, _i, _i]),
+    "dspmap_track_reset": (_i, [_P]),
+    "dspmap_track_counts": (_i, [_P, _P]),
+    "dspmap_get_tracks": (_i, [_P, _i, _P, _P]),
+    "dspmap_tracks_device": (_P, [_P]),
+    "dspmap_track_counts_device": (_P, [_P]),
     "dspmap_voxel_center": (None, [_P, _i, _fp, _fp, _fp]),
     "dspmap_point_voxel_index": (_i, [_P, _f, _f, _f, _ip]),
     "dspmap_voxel_num": (_i, [_P]),
@@ -1262,6 +1273,58 @@ class DSPMap:
         vel = np.where(mass > 0, objs["mom_q"].astype(np.float64) / np.maximum(mass, 1.0), 0.0)
         return (((mean + 0.5) * res - half).astype(np.float32), (lo * res - half).astype(np.float32),
                 ((hi + 1.0) * res - half).astype(np.float32), vel.astype(np.float32))
+
+    # -- tracks: objects across builds (extension; semantics in include/dspmap.h next to dspmap_track_update)
+    def update_tracks(self, dt, min_overlap=1, max_shift=8, max_pairs=0, per_cell=False):
+        """enqueue the association of the objects of the valid build_objects with those the previous update_tracks saw, on the handle's
+        stream: voxel overlap after each previous object's predicted shift (velocity * dt, at most max_shift voxels, and the window's
+        move), mutual best matches with at least min_overlap cells.  A matched object inherits its id, an unmatched one gets a fresh
+        id; tracks()[i] belongs to objects()[i].  max_pairs: slots of the pair table (0: 8 x the record capacity); per_cell: one table
+        insert per cell instead of one per run, the same result."""
+        self._chk(self.L.dspmap_track_update(self.h, float(dt), int(min_overlap), int(max_shift), int(max_pairs), TRACK_PER_CELL if per_cell else 0))
+
+    def reset_tracks(self):
+        """forget every track and the stored previous objects; ids start at 0 again"""
+        self._chk(self.L.dspmap_track_reset(self.h))
+
+    def track_counts(self):
+        """(n_tracks, n_matched, n_born, n_ended, n_pairs, next_id) of the last update (synchronous)"""
+        out = (C.c_longlong * 6)()
+        self._chk(self.L.dspmap_track_counts(self.h, C.cast(out, C.c_void_p)))
+        return tuple(int(v) for v in out)
+
+    def tracks(self, device=None):
+        """the tracks of the last update, one per record of objects(): structured numpy (TRACK_DTYPE) [k] (synchronous host copy); with
+        device= (e.g. "cuda") an int32 tensor [k, 18] over the handle's own device buffer, without a copy -- columns 0 .. 9 the five
+        64-bit fields as (low, high) pairs, `t[:, :10].view(torch.int64)` gives them as [k, 5], then the eight ints --, ordered with
+        torch's current stream like objects() and valid until the next update_tracks, reset_tracks or close()."""
+        n = C.c_int(0)
+        self._chk(self.L.dspmap_get_tracks(self.h, 0, None, C.byref(n)))   # (synchronises the handle's stream; raises without an update)
+        if device is not None:
+            import torch
+            dev = torch.device(device)
+            _, after = self._handle_stream_order(dev)
+            after()
+            if n.value == 0:
+                return torch.empty((0, 18), dtype=torch.int32, device=dev)
+            return torch.as_tensor(_DeviceSpan(self.L.dspmap_tracks_device(self.h), (n.value, 18), "<i4"), device=dev)
+        out = np.zeros(n.value, TRACK_DTYPE)
+        if n.value:
+            self._chk(self.L.dspmap_get_tracks(self.h, n.value, _ptr(out), C.byref(n)))
+        return out
+
+    def track_states(self, tracks, objs, dt):
+        """what a planner takes from the tracks (TRACK_DTYPE) and their records objs (OBJECT_DTYPE) of the same update: (displacement
+        [k, 3], velocity [k, 3]), float32 -- the centroid's displacement since the previous update in metres, (sum / count - prev_sum /
+        prev_count) * res per axis, and the velocity measured from it, displacement / dt (0 for dt <= 0); both 0 for a born track."""
+        res = float(np.float32(self.cfg.voxel_resolution))
+        cnt = np.maximum(objs["count"], 1)[:, None].astype(np.float64)
+        pcnt = np.maximum(tracks["prev_count"], 1)[:, None].astype(np.float64)
+        mean = np.stack([objs["sum_x"], objs["sum_y"], objs["sum_z"]], 1) / cnt
+        prev = np.stack([tracks["prev_sum_x"], tracks["prev_sum_y"], tracks["prev_sum_z"]], 1) / pcnt
+        disp = np.where((tracks["prev_ordinal"] >= 0)[:, None], (mean - prev) * res, 0.0)
+        vel = disp / float(dt) if float(dt) > 0.0 else np.zeros_like(disp)
+        return disp.astype(np.float32), vel.astype(np.float32)
 
     def set_known(self, ages):
         """test hook: replace the ages of the known-space layer (int32 [nz, ny, nx], what known_age() returns; -1 = never, else 0 ..

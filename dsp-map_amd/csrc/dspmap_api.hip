@@ -907,6 +907,7 @@ extern "C" int dspmap_clear_state(dspmap_t* m) {
     HIPCHK(m, hipMemsetAsync(m->s.pyr_cnt, 0, sizeof(int) * d.np, m->stream));
     HIPCHK(m, hipMemsetAsync(&m->s.fs->vmax_bits, 0, sizeof(int), m->stream));   // (no particle, no speed)
     { const int rc = dspmap_known_forget(m); if (rc != DSPMAP_OK) return rc; }   // a new state: nothing has been seen
+    { const int rc = dspmap_track_forget(m); if (rc != DSPMAP_OK) return rc; }   // ... and nothing tracked
     HIPCHK(m, hipStreamSynchronize(m->stream));
     if (m->stream3) HIPCHK(m, hipStreamSynchronize(m->stream3));
     if (m->hint_host) m->hint_host[3] = 0;   // a new state: an earlier frame's give-up on the estimator's queue is history (also: dspmap_load_checkpoint)
@@ -1304,6 +1305,7 @@ extern "C" int dspmap_load_checkpoint(dspmap_t* m, const char* path) {
     READY(m);
     dspmap_snapshots_stale(m);
     { const int rc = dspmap_known_forget(m); if (rc != DSPMAP_OK) return rc; }   // (the layer is not part of a checkpoint: its stamps belong to the counter of the state that is replaced)
+    { const int rc = dspmap_track_forget(m); if (rc != DSPMAP_OK) return rc; }   // (nor are the tracks: their objects were those of the state that is replaced)
     if (!path) return DSPMAP_E_ARG;
     FILE* f = fopen(path, "rb");
     if (!f) return dspmap_fail(m, DSPMAP_E_ARG, "cannot open %s", path);

@@ -81,6 +81,20 @@ struct LayerState {
     dspmap_object* ob_objects = nullptr; size_t ob_cap = 0;
     int ob_max = 0;                  // max_objects of the last build
     bool ob_valid = false;
+    // tracks (dspmap_track_update): the tracker's copies of the label grid [V] and the records [tk_cap] of the build the last update saw,
+    // two track arrays [tk_cap] -- tk_tracks[tk_cur] holds the last update's, the next one writes the other --, the per-track shifts, the
+    // compaction's tile scratch, what every update clears in ONE allocation (tk_zero: the two best arrays [tk_cap], then the pair
+    // table's keys and counts) and the counts [TRK_WORDS]; allocated by the first update (the per-record arrays again, contents kept,
+    // when the objects' records outgrow them; tk_zero when a call asks for more), freed with the device state.  NOT a snapshot: like
+    // the known-space layer it lives through frames, and it is no part of dspmap_layers_stale.  tk_have: the device holds a previous
+    // state that belongs to window tk_k0; tk_valid: an update has been enqueued since the last reset (the accessors' flag); tk_seq:
+    // updates enqueued since the last reset
+    int* tk_labels = nullptr; dspmap_object* tk_objects = nullptr; dspmap_track* tk_tracks[2] = {nullptr, nullptr};
+    int4* tk_shift = nullptr; int* tk_tiles = nullptr; char* tk_zero = nullptr; long long* tk_counts = nullptr;
+    size_t tk_cap = 0, tk_zero_bytes = 0;
+    int tk_cur = 0, tk_seq = 0, tk_slots = 0;   // tk_slots: the table size of the last update
+    long long tk_k0[3] = {0, 0, 0};
+    bool tk_have = false, tk_valid = false;
 };
 // What a change makes stale.  The snapshots depend on each other like this:
 //     map -> distance field, forecast, cast grid, objects;   cast grid -> arrival fields, frontiers, objects;   arrival fields -> timeline;
@@ -309,6 +323,7 @@ inline void dspmap_snapshots_stale(dspmap* m) { dspmap_layers_stale(m->ly, LAYER
 // dspmap_layers.hip: everything the known-space layer holds forgotten (a new state: dspmap_clear_state, dspmap_load_checkpoint), and the
 // layers' device buffers released (free_dev; chk reports a failed call)
 int dspmap_known_forget(dspmap* m);
+int dspmap_track_forget(dspmap* m);   // ... and the tracker's: no previous state, no tracks, ids from 0 again (dspmap_track_reset)
 void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const char*)>& chk);
 int dspmap_fail(dspmap* m, int code, const char* fmt, ...);
 void dspmap_prof_mark(dspmap* m, int i);

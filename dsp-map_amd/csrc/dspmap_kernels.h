@@ -331,6 +331,36 @@ struct ObjectArgs {
 };
 void launch_objects(const LaunchCtx& c, const ObjectArgs& a);
 void launch_objects_query(const LaunchCtx& c, const int* labels, int world, const float cur[3], int n, const float4* q, int* out);
+// tracks: the objects of consecutive builds associated by voxel overlap (dspmap_track.hip; semantics in include/dspmap.h, dspmap_track_update)
+struct dspmap_track;
+#define TRK_COUNTS 6     // long longs of the counts: {n_tracks, n_matched, n_born, n_ended, n_pairs, next_id}
+#define TRK_FAULT 6      // ... behind them: 0, or 1 when the pair table was full
+#define TRK_KEPT 7       // ... and two words that live through the updates: the records the stored previous state holds (K_prev)
+#define TRK_NEXT 8       //     and the next fresh id
+#define TRK_WORDS 9
+#define TRK_ORD_BITS 20  // a pair's key is ((j << 20 | o) + 1): ordinals stay below DSPMAP_OBJECTS_MAX = 2^20
+struct TrackArgs {
+    const int* labels;                     // [V] the label grid, the records and the counts of the valid build of objects
+    const struct dspmap_object* objects;
+    const long long* obj_counts;
+    int max_objects;                       // ... and its max_objects: K_now = min(obj_counts[0], max_objects)
+    const int* p_labels;                   // [V] the tracker's copies from the previous update; K_prev = counts[TRK_KEPT]
+    const struct dspmap_object* p_objects; // [cap]
+    const struct dspmap_track* p_tracks;   // [cap] the previous tracks
+    struct dspmap_track* tracks;           // out [cap]
+    int4* shift;                           // scratch [cap]: shift_j, per previous track
+    u64* best_prev; u64* best_now;         // scratch [cap] each, zeroed by the caller unless fresh
+    u64* keys; int* vals;                  // the pair table [slots], zeroed by the caller unless fresh
+    int slots;                             // a power of two
+    int* tile_sum;                         // scratch [tiles of cap]
+    long long* counts;                     // [TRK_WORDS], the first TRK_FAULT + 1 zeroed by the caller
+    int cap;                               // records every per-record array holds
+    int fresh;                             // nothing is associated: no previous state, or the window moved by a whole map
+    int dk0[3];                            // k0_now - k0_prev
+    int min_overlap, max_shift, per_cell, seq;
+    float dt;
+};
+void launch_track(const LaunchCtx& c, const TrackArgs& a);
 // state helpers
 void launch_seed_uniform(const LaunchCtx& c, int per_voxel, float weight, unsigned seed, float vmax);
 void launch_import(const LaunchCtx& c, int n, const int* voxel_dev, const int* slot_dev, const float* rec8_dev, int* n_failed_dev);

@@ -1332,6 +1332,154 @@ extern "C" int dspmap_query_objects_device(dspmap_t* m, int n, const dspmap_quer
     return objects_query_enqueue(m, n, (const float4*)q, flags, ordinal_out);
 }
 
+// --------------------------------------------------- tracks: objects across builds (dspmap_track.hip; semantics in include/dspmap.h)
+static_assert(DSPMAP_OBJECTS_MAX <= (1 << TRK_ORD_BITS), "a pair's key holds two ordinals of TRK_ORD_BITS bits");
+#define DSPMAP_TRACK_MAX_SHIFT 64
+#define DSPMAP_TRACK_MAX_SLOTS (1 << 24)
+// a per-record array of the tracker grown from `old_n` to `n` records of `bytes` each (the stream has drained); keep: with its contents
+template <class T> static int track_grow(dspmap* m, T** p, size_t old_n, size_t n, bool keep) {
+    T* q = nullptr;
+    HIPCHK(m, hipMalloc(&q, sizeof(T) * n));
+    if (keep && *p && old_n) HIPCHK(m, hipMemcpy(q, *p, sizeof(T) * old_n, hipMemcpyDeviceToDevice));
+    if (*p) (void)hipFree(*p);
+    *p = q;
+    return DSPMAP_OK;
+}
+// the tracker's buffers for `cap` records and a table of `slots`: what depends on V alone once, the rest again when it is outgrown.  What
+// an update clears -- the two best arrays [cap] and the table's keys and counts [slots] -- is ONE allocation, cleared by one memset
+static size_t track_zero_bytes(size_t cap, size_t slots) { return 2 * sizeof(u64) * cap + (sizeof(u64) + sizeof(int)) * slots; }
+static int track_alloc(dspmap* m, size_t cap, size_t slots) {
+    LayerState& l = m->ly;
+    int rc;
+    if (!l.tk_labels) HIPCHK(m, hipMalloc(&l.tk_labels, sizeof(int) * (size_t)m->d.v_glob));
+    if (!l.tk_counts) {
+        HIPCHK(m, hipMalloc(&l.tk_counts, TRK_WORDS * sizeof(long long)));
+        HIPCHK(m, hipMemsetAsync(l.tk_counts, 0, TRK_WORDS * sizeof(long long), m->stream));
+    }
+    if (cap > l.tk_cap) {
+        if (l.tk_cap) HIPCHK(m, hipStreamSynchronize(m->stream));   // (an earlier update may still use the smaller arrays)
+        const size_t old = l.tk_cap;
+        const size_t tiles = (size_t)frontier_tiles((long long)cap), old_tiles = (size_t)frontier_tiles((long long)old);
+        if ((rc = track_grow(m, &l.tk_objects, old, cap, true)) != DSPMAP_OK) return rc;
+        if ((rc = track_grow(m, &l.tk_tracks[l.tk_cur], old, cap, true)) != DSPMAP_OK) return rc;
+        if ((rc = track_grow(m, &l.tk_tracks[l.tk_cur ^ 1], old, cap, false)) != DSPMAP_OK) return rc;
+        if ((rc = track_grow(m, &l.tk_shift, old, cap, false)) != DSPMAP_OK) return rc;
+        if ((rc = track_grow(m, &l.tk_tiles, old_tiles, tiles, false)) != DSPMAP_OK) return rc;
+        l.tk_cap = cap;
+    }
+    const size_t zero = track_zero_bytes(l.tk_cap, slots);
+    if (zero > l.tk_zero_bytes) {
+        if (l.tk_zero_bytes) HIPCHK(m, hipStreamSynchronize(m->stream));
+        if ((rc = track_grow(m, &l.tk_zero, l.tk_zero_bytes, zero, false)) != DSPMAP_OK) return rc;
+        l.tk_zero_bytes = zero;
+    }
+    return DSPMAP_OK;
+}
+// everything forgotten (dspmap_track_reset, dspmap_clear_state, dspmap_load_checkpoint); a handle that never tracked has nothing to forget
+int dspmap_track_forget(dspmap* m) {
+    LayerState& l = m->ly;
+    l.tk_have = false; l.tk_valid = false; l.tk_seq = 0;
+    if (l.tk_counts) {
+        if (m->device >= 0) (void)hipSetDevice(m->device);
+        HIPCHK(m, hipMemsetAsync(l.tk_counts, 0, TRK_WORDS * sizeof(long long), m->stream));
+    }
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_track_reset(dspmap_t* m) {
+    if (!m) return DSPMAP_E_ARG;
+    return dspmap_track_forget(m);
+}
+extern "C" int dspmap_track_update(dspmap_t* m, float dt, int min_overlap, int max_shift, int max_pairs, int flags) {
+    const char* what = "dspmap_track_update";
+    if (!m) return DSPMAP_E_ARG;
+    if (!(dt >= 0.f && dt < INFINITY)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: dt %g is NaN, negative or infinite", what, (double)dt);
+    if (min_overlap < 1) return dspmap_fail(m, DSPMAP_E_ARG, "%s: min_overlap %d below 1", what, min_overlap);
+    if (max_shift < 0 || max_shift > DSPMAP_TRACK_MAX_SHIFT)
+        return dspmap_fail(m, DSPMAP_E_ARG, "%s: max_shift %d outside [0, %d]", what, max_shift, DSPMAP_TRACK_MAX_SHIFT);
+    if (max_pairs < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative max_pairs %d", what, max_pairs);
+    int rc = flags_check(m, what, flags, DSPMAP_TRACK_PER_CELL);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = whole_map_check(m, what, "components cross slabs")) != DSPMAP_OK) return rc;
+    if ((rc = objects_ready(m, what)) != DSPMAP_OK) return rc;
+    long long k0[3];
+    float o[3];
+    if ((rc = known_window(m, k0, o)) != DSPMAP_OK) return rc;
+    LayerState& l = m->ly;
+    const MapDims& d = m->d;
+    const size_t V = (size_t)d.v_glob;
+    // the table: max_pairs (0: 8 x the record capacity, at least 1024) rounded up to a power of two, at most 2^24 slots
+    size_t want = max_pairs > 0 ? (size_t)max_pairs : (8 * l.ob_cap > 1024 ? 8 * l.ob_cap : 1024), slots = 1;
+    while (slots < want && slots < DSPMAP_TRACK_MAX_SLOTS) slots <<= 1;
+    if ((rc = track_alloc(m, l.ob_cap, slots)) != DSPMAP_OK) return rc;
+    TrackArgs a;
+    a.fresh = l.tk_have ? 0 : 1;
+    const int n[3] = {d.nx, d.ny, d.nz};
+    for (int ax = 0; ax < 3; ++ax) {
+        const long long delta = l.tk_have ? k0[ax] - l.tk_k0[ax] : 0;
+        if (delta >= n[ax] || -delta >= n[ax]) a.fresh = 1;   // the window moved by a whole map: nothing of the previous grid is in it
+        a.dk0[ax] = a.fresh ? 0 : (int)delta;
+    }
+    if (a.fresh) a.dk0[0] = a.dk0[1] = a.dk0[2] = 0;          // (a later axis may have decided)
+    a.labels = l.ob_labels; a.objects = l.ob_objects; a.obj_counts = l.ob_counts; a.max_objects = l.ob_max;
+    a.p_labels = l.tk_labels; a.p_objects = l.tk_objects; a.p_tracks = l.tk_tracks[l.tk_cur]; a.tracks = l.tk_tracks[l.tk_cur ^ 1];
+    a.shift = l.tk_shift;
+    a.best_prev = (u64*)l.tk_zero; a.best_now = a.best_prev + l.tk_cap; a.keys = a.best_now + l.tk_cap; a.vals = (int*)(a.keys + slots);
+    a.slots = (int)slots; a.tile_sum = l.tk_tiles; a.counts = l.tk_counts; a.cap = (int)l.tk_cap;
+    a.min_overlap = min_overlap; a.max_shift = max_shift; a.per_cell = (flags & DSPMAP_TRACK_PER_CELL) ? 1 : 0; a.seq = l.tk_seq; a.dt = dt;
+    HIPCHK(m, hipMemsetAsync(l.tk_counts, 0, (TRK_FAULT + 1) * sizeof(long long), m->stream));
+    if (!a.fresh) HIPCHK(m, hipMemsetAsync(l.tk_zero, 0, track_zero_bytes(l.tk_cap, slots), m->stream));
+    launch_track(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    // what the next update associates with: this build's label grid and records (k_track_keep has set their number)
+    const size_t kept = (size_t)l.ob_max < V ? (size_t)l.ob_max : V;   // (<= ob_cap <= tk_cap)
+    HIPCHK(m, hipMemcpyAsync(l.tk_labels, l.ob_labels, sizeof(int) * V, hipMemcpyDeviceToDevice, m->stream));
+    HIPCHK(m, hipMemcpyAsync(l.tk_objects, l.ob_objects, sizeof(dspmap_object) * kept, hipMemcpyDeviceToDevice, m->stream));
+    l.tk_cur ^= 1;
+    for (int ax = 0; ax < 3; ++ax) l.tk_k0[ax] = k0[ax];
+    l.tk_have = true; l.tk_valid = true; l.tk_slots = (int)slots;
+    ++l.tk_seq;
+    return DSPMAP_OK;
+}
+static int tracks_ready(dspmap* m, const char* what) {
+    return snapshot_ready(m, m->ly.tk_valid, what, "no tracks: no update since the handle was created, reset or given a new state (dspmap_track_update)");
+}
+// the counts of the last update, read back; a set fault word (the pair table was full, the update is void) is an error
+static int tracks_counts(dspmap* m, const char* what, long long c[TRK_FAULT + 1]) {
+    const int rc = read_back(m, c, m->ly.tk_counts, (TRK_FAULT + 1) * sizeof(long long));
+    if (rc != DSPMAP_OK) return rc;
+    if (c[TRK_FAULT] != 0)
+        return dspmap_fail(m, DSPMAP_E_DEVICE, "%s: the pair table of the last dspmap_track_update was full (max_pairs: %d slots), the update is void", what,
+                           m->ly.tk_slots);
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_track_counts(dspmap_t* m, long long out[6]) {
+    const char* what = "dspmap_track_counts";
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL output array", what);
+    int rc = tracks_ready(m, what);
+    if (rc != DSPMAP_OK) return rc;
+    long long c[TRK_FAULT + 1];
+    if ((rc = tracks_counts(m, what, c)) != DSPMAP_OK) return rc;
+    for (int i = 0; i < TRK_COUNTS; ++i) out[i] = c[i];
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_get_tracks(dspmap_t* m, int cap, dspmap_track* out, int* n_out) {
+    const char* what = "dspmap_get_tracks";
+    if (!m) return DSPMAP_E_ARG;
+    if (cap < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative capacity %d", what, cap);
+    if (!n_out || (cap > 0 && !out)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL output", what);
+    int rc = tracks_ready(m, what);
+    if (rc != DSPMAP_OK) return rc;
+    long long c[TRK_FAULT + 1];
+    if ((rc = tracks_counts(m, what, c)) != DSPMAP_OK) return rc;
+    const long long n = c[0], take = n < cap ? n : cap;
+    if (take > 0 && (rc = read_back(m, out, m->ly.tk_tracks[m->ly.tk_cur], sizeof(dspmap_track) * (size_t)take)) != DSPMAP_OK) return rc;
+    *n_out = (int)n;
+    return DSPMAP_OK;
+}
+extern "C" const dspmap_track* dspmap_tracks_device(dspmap_t* m) { return (m && m->ly.tk_valid) ? m->ly.tk_tracks[m->ly.tk_cur] : nullptr; }
+extern "C" const long long* dspmap_track_counts_device(dspmap_t* m) { return (m && m->ly.tk_valid) ? m->ly.tk_counts : nullptr; }
+
 // --------------------------------------------------- the end of the handle
 void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const char*)>& chk) {
     const LayerState& l = m->ly;
@@ -1339,6 +1487,7 @@ void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const ch
                     (void*)l.rf_sets, (void*)l.tl_hist, (void*)l.tl_last, (void*)l.fc_field, (void*)l.fc_acc, (void*)l.kn_stamp, (void*)l.vw_dirs0,
                     (void*)l.fr_grid, (void*)l.fr_cells, (void*)l.fr_counts, (void*)l.fr_item_free, (void*)l.fr_dense, (void*)l.fr_blocks,
                     (void*)l.fr_tiles, (void*)l.ob_parent, (void*)l.ob_root, (void*)l.ob_labels, (void*)l.ob_tiles, (void*)l.ob_counts,
-                    (void*)l.ob_objects})
+                    (void*)l.ob_objects, (void*)l.tk_labels, (void*)l.tk_objects, (void*)l.tk_tracks[0], (void*)l.tk_tracks[1], (void*)l.tk_shift,
+                    (void*)l.tk_tiles, (void*)l.tk_zero, (void*)l.tk_counts})
         if (q) chk(hipFree(q), "hipFree");
 }

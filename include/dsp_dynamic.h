@@ -365,6 +365,16 @@ public:
     int queryObjects(int n, const dspmap_query* samples, int* ordinals, bool world = false) {
         return dspmap_query_objects(h_, n, samples, world ? DSPMAP_QUERY_WORLD : 0, ordinals);
     }
+    /* extension: tracks (dspmap_track_update in dspmap.h): after buildObjects, trackObjects associates the objects with those of the
+     * previous call by voxel overlap -- predicted by each object's velocity over dt seconds, at most max_shift voxels -- and gives every
+     * record a dspmap_track with the same index: an id that persists while the object is matched, its age, the id it split off from.
+     * trackObjects enqueues; getTracks copies the first min(cap, n) tracks and reports n; resetTracks forgets everything and starts the
+     * ids at 0 again.  Return DSPMAP_OK or a negative error code. */
+    int trackObjects(float dt, int min_overlap = 1, int max_shift = 8, int max_pairs = 0) {
+        return dspmap_track_update(h_, dt, min_overlap, max_shift, max_pairs, 0);
+    }
+    int getTracks(int cap, dspmap_track* tracks, int& n) { return dspmap_get_tracks(h_, cap, tracks, &n); }
+    int resetTracks() { return dspmap_track_reset(h_); }
     void clearOccupancyMapPrediction() { dspmap_clear_future(h_); }  // :431-438
 
     void getKMClusterResult(pcl::PointCloud<pcl::PointXYZINormal>& cluster_cloud) {  // :441-445

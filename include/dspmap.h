@@ -940,6 +940,77 @@ const long long* dspmap_object_counts_device(dspmap_t* m);
 int dspmap_query_objects(dspmap_t* m, int n, const dspmap_query* q_host, int flags, int* ordinal_out_host);
 int dspmap_query_objects_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, int* ordinal_out_dev);
 
+/* ---- tracks: the objects of consecutive builds associated by voxel overlap -- ids that persist, an age, a parent for what split off (no
+ * counterpart in the reference).  Every dspmap_build_objects numbers the obstacles anew; a planner filters a per-obstacle state over time
+ * and needs "obstacle 17 is the one I avoided a moment ago, it has existed for 40 frames, and it just split off obstacle 9".  Like the
+ * known-space layer this is persistent state beside the frame, not a snapshot: it lives through frames, and the frame path does not know
+ * about it.  After update -> dspmap_build_cast_grid -> dspmap_build_objects the caller calls dspmap_track_update(dt, ...): it
+ * associates the objects of the valid build with those the previous update saw and yields one dspmap_track per record, tracks[i]
+ * belonging to objects[i].  Integers throughout but the predicted shift, whose double operations are each rounded on their own: the
+ * update is defined bit for bit and independent of the launch.  Only enqueued on the handle's stream, no synchronisation, no host read.
+ *
+ *  Input: records, label grid and counts of the valid dspmap_build_objects, K_now = min(n_objects, max_objects) read on the device; the
+ *  tracker's own copy of the same three from the previous update, K_prev, with the previous tracks; and the window: k0[a], the world
+ *  lattice index of map voxel 0 on axis a, from the current position by the known-space layer's expression (above), dk0 = k0_now - k0_prev.
+ *  Fresh start: without a previous state (first update, after a reset, a new state or a void update), or with |dk0[a]| >= n[a] on some
+ *  axis, nothing is associated: every object is born, the previous tracks all end.
+ *  Predicted shift per previous track j, from its record: with mass_q > 0, per axis v = (double)mom_q[a] / (double)mass_q,
+ *  d = v * (double)dt, e = d / (double)res, p = floor(e + 0.5), then p clamped to [-max_shift, max_shift] while still a double; with
+ *  mass_q <= 0, p = 0.  shift_j[a] = (int)p - dk0[a].  dt = 0 is pure overlap.
+ *  Overlap: every cell c of the previous label grid whose ordinal is j < K_prev looks at c' = c + shift_j; if c' lies inside the map and
+ *  the current label grid holds o with 0 <= o < K_now there, n(j, o) += 1.  Ordinals >= K on either side and -1 contribute nothing.
+ *  Association: bj(o) = the j with the largest n(j, o) > 0, ties to the smaller j; bo(j) = the o with the largest n(j, o) > 0, ties to
+ *  the smaller o; o is matched to j iff bj(o) = j, bo(j) = o and n(j, o) >= min_overlap.
+ *  A matched track: id, parent and born_seq of track j; age = age_j + 1; prev_ordinal = j; overlap = n(j, o); shift_* = shift_j;
+ *  prev_count = count_j; prev_sum_a = sum_a,j - count_j * dk0[a], the previous index sums in the CURRENT window's voxel indices, so that
+ *  sum / count - prev_sum / prev_count is the centroid's displacement in voxels.
+ *  A born track: id = next_id + r, r its rank among the unmatched objects in ascending ordinal; parent = the id of track bj(o) if bj(o)
+ *  exists (what a split leaves behind names its parent this way), else -1; age = 0; born_seq = the number of updates enqueued since the
+ *  last reset before this one (the first is 0; a void update counts); prev_ordinal = -1; overlap = n(bj(o), o) or 0; shifts, prev_count
+ *  and prev_sum_* 0.  Then next_id += the number born.  Ids start at 0 after a reset.
+ *  Counts, long long[6]: {n_tracks, n_matched, n_born, n_ended, n_pairs, next_id}; n_ended = the previous tracks without a match, n_pairs
+ *  = the distinct (j, o) with n > 0.  The device buffer holds a seventh word: 0, or 1 when the pair table was full.
+ *  Pair table: n(j, o) lives in an open-addressing table of max_pairs slots -- 0 selects 8 x the record capacity of the objects, at least
+ *  1024; any value is rounded up to a power of two, at most 2^24.  Probing is bounded by the table size.  If an insert finds no slot --
+ *  exactly when the distinct pairs exceed the slots -- the update is VOID: the fault word is 1, the counts are 0 but next_id, which is
+ *  unchanged, the stored previous state is emptied on the device (the following update starts fresh), and the synchronous accessors
+ *  return DSPMAP_E_DEVICE with a text naming max_pairs.  An ordinary, reported outcome of a capacity argument, like the exhausted bound
+ *  of dspmap_build_objects.
+ *  flags: DSPMAP_TRACK_PER_CELL makes one table insert per contributing cell instead of one per run of equal pairs along x; the same
+ *  bytes, for measurements and tests.
+ *
+ *  - dspmap_track_reset: everything forgotten, ids from 0 again; dspmap_clear_state and dspmap_load_checkpoint do the same.
+ *  - dspmap_track_counts: synchronous.  dspmap_get_tracks: the conventions of dspmap_get_objects, *n_out = n_tracks.
+ *  - dspmap_tracks_device, dspmap_track_counts_device: the device buffers of the last update (the track array changes with every
+ *    update), NULL without one; valid once the handle's stream has reached the update, until the next update or reset.
+ *  - checks, in this order.  DSPMAP_E_ARG with a text, before the device is touched: a NULL handle, dt NaN, negative or infinite,
+ *    min_overlap < 1, max_shift outside [0, 64], max_pairs < 0, unknown flags; a NULL output, cap < 0.  Then a sharded handle (slab) is
+ *    DSPMAP_E_STATE; then no valid build of objects is DSPMAP_E_STATE with a text naming dspmap_build_objects; then a position the
+ *    known-space window refuses.  Accessors without an update are DSPMAP_E_STATE with a text naming dspmap_track_update.
+ *  - life cycle.  The tracks of the last update stay readable through frames, until the next update or reset; only their pairing with
+ *    objects[i] depends on that build.  Nothing that makes a snapshot stale touches them, and an update makes no snapshot stale.
+ *  - a handle that never tracks allocates nothing.  The first update allocates a copy of the label grid (V ints), copies of the records
+ *    and counts, two track arrays (swapped, not copied), the per-track shifts, the two best arrays, the pair table and a little scan
+ *    scratch; all of it is freed with the device state. */
+#define DSPMAP_TRACK_PER_CELL 1
+typedef struct dspmap_track {
+    long long id;                     /* persists while the track is matched */
+    long long parent;                 /* id of the track it was born from (a split), or -1 */
+    long long prev_sum_x, prev_sum_y, prev_sum_z;   /* the previous index sums in the current window's voxel indices */
+    int prev_count;                   /* the previous record's cells, 0 for a born track */
+    int prev_ordinal;                 /* its ordinal in the previous build, -1 for a born track */
+    int age;                          /* updates since it was born */
+    int born_seq;                     /* sequence number of the update it was born in */
+    int overlap;                      /* n(j, o) of the match, or of the best previous track of a born one */
+    int shift_x, shift_y, shift_z;    /* shift_j of the match */
+} dspmap_track;
+int dspmap_track_update(dspmap_t* m, float dt, int min_overlap, int max_shift, int max_pairs, int flags);
+int dspmap_track_reset(dspmap_t* m);
+int dspmap_track_counts(dspmap_t* m, long long out[6]);                   /* synchronous */
+int dspmap_get_tracks(dspmap_t* m, int cap, dspmap_track* out_host, int* n_out);
+const dspmap_track* dspmap_tracks_device(dspmap_t* m);
+const long long* dspmap_track_counts_device(dspmap_t* m);
+
 /* getVoxelPositionFromIndexPublic :1556-1572 / getPointVoxelsIndexPublic :1574-1584 (host math) */
 void dspmap_voxel_center(const dspmap_t* m, int index, float* px, float* py, float* pz);
 int dspmap_point_voxel_index(const dspmap_t* m, float px, float py, float pz, int* index);
