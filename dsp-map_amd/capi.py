@@ -20,7 +20,7 @@ OK, REJECTED = 1, 0
 P_POSITION_STDDEV, P_VELOCITY_STDDEV, P_OBSERVATION_STDDEV, P_NEWBORN_WEIGHT, P_NEWBORN_NUMBER, \
     P_VOXEL_FILTER_RES, P_KAPPA, P_DETECTION, P_VELOCITY_ESTIMATOR, P_REGENERATE_TABLES, P_USE_GRAPH, P_OCCLUSION_MARGIN, \
     P_PAIR_CULL_SIGMAS, P_UPDATE_TIME, P_UPDATE_COUNTER, P_PLACE_SPLIT_TILES, P_FAST_DIVISION, P_SPARSE_SWEEP, P_ROLLOUT_INLINE, \
-    P_RESAMPLE_WG_TILES, P_SWEEP_ALTERNATE, P_STATIC_TILE_SKIP, P_HOST_CLOUD_DIRECT, _P_REMOVED_24, P_ESTIMATOR_QUEUE, P_FRAME_BRANCHES, P_TILING, P_SIDE_PLACEMENT, P_RESAMPLE_SPLIT, P_TILE_BITMAPS, P_VIEW_CHUNKS, P_FRONTIER_MERGE = range(1, 33)
+    P_RESAMPLE_WG_TILES, P_SWEEP_ALTERNATE, P_STATIC_TILE_SKIP, P_HOST_CLOUD_DIRECT, _P_REMOVED_24, P_ESTIMATOR_QUEUE, P_FRAME_BRANCHES, P_TILING, P_SIDE_PLACEMENT, P_RESAMPLE_SPLIT, P_TILE_BITMAPS, P_VIEW_CHUNKS, P_FRONTIER_MERGE, P_PAIR_PREPARE = range(1, 34)
 
 
 class Config(C.Structure):
@@ -243,6 +243,7 @@ SIGNATURES = {
     "dspmap_debug_rollout_plan": (_i, [_P, _ip, _ip]),
     "dspmap_debug_pair_items": (_i, [_P, _ip]),
     "dspmap_debug_weight_variant": (_i, [_P]),
+    "dspmap_debug_pair_path": (_i, [_P]),
     "dspmap_debug_estimator_queue": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_frame_branches": (_i, [_P, C.POINTER(C.c_longlong)]),
     "dspmap_debug_resample_split_frames": (C.c_longlong, [_P]),
@@ -437,6 +438,11 @@ class DSPMap:
     def weight_variant(self):
         """which k_weight the last weight update launched: 'mask' (every pair evaluated), 'skip' (far pairs branched over), or None"""
         return {0: None, 1: "mask", 2: "skip"}.get(self.L.dspmap_debug_weight_variant(self.h))
+
+    def pair_path(self):
+        """how the last frame gave its pair kernels their work: 'prepared' (k_pyr_prepare), 'self' (self-mapped, no k_pyr_prepare), or None
+        -- DSPMAP_P_PAIR_PREPARE"""
+        return {0: None, 1: "prepared", 2: "self"}.get(self.L.dspmap_debug_pair_path(self.h))
 
     def estimator_queue(self):
         """(frames whose estimator ran on a queue of its own, hand-over word 0, hand-over word 1, give-ups, frames whose first birth kernel

@@ -387,11 +387,12 @@ extern "C" int dspmap_init_device(dspmap_t* m) {
     HIPCHK(m, hipHostMalloc((void**)&m->ring_host, sizeof(FrameParams) * DSPMAP_RING, hipHostMallocMapped));
     memset(m->ring_host, 0, sizeof(FrameParams) * DSPMAP_RING);
     { void* dp = nullptr; HIPCHK(m, hipHostGetDevicePointer(&dp, m->ring_host, 0)); m->ring_dev = (const FrameParams*)dp; }
-    HIPCHK(m, hipHostMalloc((void**)&m->hint_host, 4 * sizeof(int), hipHostMallocMapped));
+    HIPCHK(m, hipHostMalloc((void**)&m->hint_host, 5 * sizeof(int), hipHostMallocMapped));
     m->hint_host[0] = 1 << 24;   // (nothing known yet: not sparse)
     m->hint_host[1] = 0;
     m->hint_host[2] = 0;         // ring position behind the last frame whose first kernel is done with its parameter / cloud slot
     m->hint_host[3] = 0;
+    m->hint_host[4] = 0;         // a self-mapped Ck launch found a pyramid list past its capacity (dspmap_pair_sticky)
     { void* dp = nullptr; HIPCHK(m, hipHostGetDevicePointer(&dp, (void*)m->hint_host, 0)); m->s.hint_out = (int*)dp; }
     HIPCHK(m, hipMalloc((void**)&m->s.ring_seq, sizeof(int)));
     HIPCHK(m, hipMemset(m->s.ring_seq, 0, sizeof(int)));
@@ -463,8 +464,10 @@ extern "C" int dspmap_init_device(dspmap_t* m) {
     HIPCHK(m, dalloc(&k.omask, W));
     HIPCHK(m, hipMemset(k.omask, 0, sizeof(u64) * W));
     HIPCHK(m, dalloc(&k.ck_items, (size_t)d.np * ((d.capp + 31) / 32 + 1)));   // (items of 32 particles up to CK_SMALL_FOV in view: a small map with every list past 128 has more than capp / 64 + 1 per pyramid)
-    HIPCHK(m, dalloc(&k.wu_items, (size_t)d.np * ((d.capp + 31) / 32 + 1)));
+    HIPCHK(m, dalloc(&k.wu_items, std::max((size_t)d.np * ((d.capp + 31) / 32 + 1), (size_t)1024)));   // (self-mapped pair kernels: the prefix of k_weight's items, PH_MAXNP + 1 ints)
+    HIPCHK(m, hipMemset(k.wu_items, 0, sizeof(int) * 1024));
     HIPCHK(m, dalloc(&k.n_items, (size_t)4));
+    HIPCHK(m, hipMemset(k.n_items, 0, sizeof(int) * 4));
     HIPCHK(m, dalloc(&k.nb_tab, (size_t)d.np * NB_TAB_STRIDE));
     HIPCHK(m, hipMemset(k.in_cnt, 0, sizeof(int) * ntiles));
     const bool slab = !(d.z_lo == 0 && d.z_hi == d.nz);
@@ -616,6 +619,9 @@ extern "C" int dspmap_set_param(dspmap_t* m, int key, double v) {
             break;
         case DSPMAP_P_FRAME_BRANCHES: m->frame_branches = v < 0 ? -1 : (v != 0 ? 1 : 0); m->graph_epoch++; break;
         case DSPMAP_P_RESAMPLE_SPLIT: m->resample_split = v != 0 ? 1 : 0; m->graph_epoch++; break;
+        case DSPMAP_P_PAIR_PREPARE:   // (part of the captured frame's key)
+            if (v != 0 && v != 1 && v != 2) return dspmap_fail(m, DSPMAP_E_ARG, "pair prepare: 0 auto, 1 always prepare the lists, 2 self-mapped pair kernels wherever legal");
+            m->pair_prepare = (int)v; break;
         case DSPMAP_P_TILE_BITMAPS: m->tile_bitmaps = v != 0; m->graph_epoch++; break;
         case DSPMAP_P_VIEW_CHUNKS: m->ly.vw_chunks = v >= 1.f ? (int)fminf(v, 64.f) : 0; break;   // (launch shape of dspmap_score_views only)
         case DSPMAP_P_FRONTIER_MERGE: m->ly.fr_merge = v != 0; break;   // (how dspmap_build_frontiers adds up its block sums only)
@@ -682,6 +688,7 @@ extern "C" double dspmap_get_param(const dspmap_t* m, int key) {
         case DSPMAP_P_FRAME_BRANCHES: return m->frame_branches;
         case DSPMAP_P_SIDE_PLACEMENT: return m->side_fork * 16 + m->side_wg;
         case DSPMAP_P_RESAMPLE_SPLIT: return m->resample_split;
+        case DSPMAP_P_PAIR_PREPARE: return m->pair_prepare;
         case DSPMAP_P_TILE_BITMAPS: return m->tile_bitmaps ? 1 : 0;
         case DSPMAP_P_VIEW_CHUNKS: return (float)m->ly.vw_chunks;
         case DSPMAP_P_FRONTIER_MERGE: return m->ly.fr_merge ? 1.f : 0.f;
@@ -911,6 +918,8 @@ extern "C" int dspmap_clear_state(dspmap_t* m) {
     HIPCHK(m, hipStreamSynchronize(m->stream));
     if (m->stream3) HIPCHK(m, hipStreamSynchronize(m->stream3));
     if (m->hint_host) m->hint_host[3] = 0;   // a new state: an earlier frame's give-up on the estimator's queue is history (also: dspmap_load_checkpoint)
+    if (m->hint_host) m->hint_host[4] = 0;   // ... and so are its overfull pyramid lists (DSPMAP_P_PAIR_PREPARE)
+    m->pair_sticky = false;
     m->xq_failed = false;
     m->have_last = false;
     if (m->nb_dirty) { m->nb_dirty = false; m->graph_epoch++; }
@@ -1139,6 +1148,10 @@ extern "C" int dspmap_debug_pair_items(dspmap_t* m, int out[3]) {
 extern "C" int dspmap_debug_weight_variant(dspmap_t* m) {
     if (!m) return DSPMAP_E_ARG;
     return m->last_weight_variant;
+}
+extern "C" int dspmap_debug_pair_path(dspmap_t* m) {
+    if (!m) return DSPMAP_E_ARG;
+    return m->last_pair_path;
 }
 extern "C" int dspmap_debug_rollout_plan(dspmap_t* m, int halo_out[DSPMAP_MAX_PRED_TIMES], int* lds_cells_out) {
     if (!m || !halo_out) return DSPMAP_E_ARG;   // (host state only: no device needed)

@@ -285,10 +285,11 @@ static void enqueue_frame(dspmap* m, LaunchCtx& c, int pts_grid, int birth_grid,
     side_place(1);
     dspmap_prof_mark(m, 3);
     side_leaves(0);
-    launch_ck_partial(c, split);
+    if (c.pair_self) launch_ck_partial_self(c);   // (never a split placement: k_place's end is this launch's start)
+    else launch_ck_partial(c, split);
     side_place(0);
     dspmap_prof_mark(m, 4);
-    m->last_weight_variant = launch_weight_update(c);
+    m->last_weight_variant = launch_weight_update(c, c.pair_self);
     dspmap_prof_mark(m, 5);
     if (with_est ? est_branch : split) (void)hipStreamWaitEvent(m->stream, m->ev_join, 0);   // the side stream's last kernel before the births
     if (!with_est && birth_grid <= 0) launch_ck_finalize(c);   // otherwise k_birth_rank reduces the 1/Ck sums (one launch less)
@@ -390,6 +391,7 @@ static int frame_with_host_stages(dspmap* m, int np, const float* pts_dev, const
     launch_predict(c, true);
     launch_ck_partial(c);
     m->last_weight_variant = launch_weight_update(c);
+    m->last_pair_path = 1;
     int nb = nb_static_grid;
     if (m->use_vel_est != 0 && !m->cfg.static_model) {
         if (pts_ready) HIPCHK(m, hipEventSynchronize(pts_ready));
@@ -559,6 +561,14 @@ int dspmap_device_frame(dspmap* m, int n_points, const float* points_dev, int n_
     }
     if (xq) c.s.xq = m->xq_dev;
     if (mode == 2) m->est_path = xq ? 1 : ((m->est_queue && m->xq_shared) ? 2 : 3);
+    // (DSPMAP_P_PAIR_PREPARE) a map whose k_weight evaluates every pair needs nothing from k_pyr_prepare while no pyramid list is overfull: its
+    // single-chain frames launch the self-mapped pair kernels.  Whether a list IS overfull only the device knows: such a frame sorts and cuts
+    // inside the Ck launch (slow, exact) and says so in hint_host[4]; from the first frame that finds the word set the handle prepares its
+    // lists again, until its state is cleared or restored.  The choice follows the configuration and that word, never the frame's data.
+    if (m->hint_host && m->hint_host[4]) m->pair_sticky = true;
+    c.pair_self = m->pair_prepare != 1 && (m->pair_prepare == 2 || !m->pair_sticky) && !m->prof && !m->mgpu_bound &&
+                  !frame_splits_placement(m, c) && !frame_runs_two_branches(m, c) && pair_self_legal(c);
+    m->last_pair_path = c.pair_self ? 2 : 1;
     if (m->frame_ring && m->host_cloud && n_points > 0) { rc = host_cloud_to_ring(m, n_points, m->ring_head); if (rc != DSPMAP_OK) return rc; }
     rc = m->frame_ring ? dspmap_ring_push(m) : dspmap_push_frame_params(m);
     if (rc != DSPMAP_OK) return rc;
@@ -613,7 +623,7 @@ int dspmap_device_frame(dspmap* m, int n_points, const float* points_dev, int n_
     const bool plain_small = m->graph_mode == 1 && chain && c.k.ntiles < DSPMAP_PLAIN_TILES && !m->host_cloud;
     if (m->use_graph && !m->prof && !two && !plain_small) {
         // the kernel arguments of a frame are constant (per-frame values live in s.fpar): capture once, replay
-        const unsigned long long key = ((unsigned long long)m->graph_epoch << 8) | (has_vz ? 1u : 0u) | ((unsigned)mode << 1) | (c.sparse ? 8u : 0u) | (c.ro_inline ? 16u : 0u) | (xq ? 32u : 0u);
+        const unsigned long long key = ((unsigned long long)m->graph_epoch << 8) | (has_vz ? 1u : 0u) | ((unsigned)mode << 1) | (c.sparse ? 8u : 0u) | (c.ro_inline ? 16u : 0u) | (xq ? 32u : 0u) | (c.pair_self ? 64u : 0u);
         const int gi = c.sweep_rev ? 1 : 0;   // (one executable graph per sweep direction: the direction is a kernel argument)
         if (!m->graph_exec[gi] || m->graph_key[gi] != key) {
             if (m->graph_exec[gi]) {   // (replays of the old executable graph may still be queued: let them finish before it goes)
@@ -842,6 +852,7 @@ extern "C" int dspmap_stage_update(dspmap_t* m) {
     LaunchCtx c = dspmap_ctx_of(m);
     launch_ck_partial(c);
     m->last_weight_variant = launch_weight_update(c);
+    m->last_pair_path = 1;
     launch_ck_finalize(c);
     HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;

@@ -263,6 +263,9 @@ struct dspmap {
     int resample_wg_tiles = 8192;    // one-word maps with fewer tiles (and sparse ones of any size) run the four-waves-per-tile resampler (DSPMAP_P_RESAMPLE_WG_TILES)
     int last_resample_variant = 0;   // resample_variant() of the last frame / stage (dspmap_debug_rollout_paths)
     int last_weight_variant = 0;     // what launch_weight_update returned for the last frame / stage (dspmap_debug_weight_variant)
+    int pair_prepare = 0;            // DSPMAP_P_PAIR_PREPARE: 0 self-mapped pair kernels where legal until a frame reports an overfull list, 1 always k_pyr_prepare, 2 self-mapped wherever legal
+    bool pair_sticky = false;        // a self-mapped frame has reported an overfull pyramid list (hint_host[4]): frames prepare their lists until the state is cleared / restored
+    int last_pair_path = 0;          // the last frame / weight-update stage: 1 lists prepared by k_pyr_prepare, 2 self-mapped pair kernels; 0 none yet (dspmap_debug_pair_path)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec[2] = {nullptr, nullptr};   // the captured frame, one per sweep direction (LaunchCtx::sweep_rev is a kernel argument)
     unsigned long long graph_key[2] = {~0ull, ~0ull};

@@ -28,7 +28,7 @@ struct KernelScratch {
     int* vb_idx;        // [v_loc*128] their birth indices
     int* ck_items;      // [np * (ceil(capp/32)+1)] work items of k_ck_partial (pyramid<<12 | chunk)
     int* wu_items;      // [np * (ceil(capp/256)+1)] work items of k_weight
-    int* n_items;       // [3] Ck items, weight items, particles per Ck item (dspmap_debug_pair_items)
+    int* n_items;       // [4] Ck items, weight items, particles per Ck item (dspmap_debug_pair_items); [3] workgroups of an overfull self-mapped Ck launch that are done
     int* nb_tab;        // [NB_TAB_STRIDE][np] neighbourhood of every pyramid: bins (h-major, -1 padded) + exclusive offsets of
                         // their observation counts, written by k_pyr_items once per frame
     int* part_birth;    // [ceil(birth_cap*32/256)*2] per-block {born, dropped} of k_birth_insert
@@ -64,6 +64,7 @@ struct LaunchCtx {
                               // kernels (sel = 0): k_predict leaves the list of the tiles with a view (KernelScratch::view_list)
     bool tile_bits = false;   // this frame's sweeps go by the tile bitmaps (sparse whole frames of an unsharded map; DSPMAP_P_TILE_BITMAPS)
     int side_wg = 3;          // workgroups per CU of the side-stream placement (sel = 0; DSPMAP_P_SIDE_PLACEMENT)
+    bool pair_self = false;  // this frame's pair kernels map their items themselves and read the lists as registered: no k_pyr_prepare (DSPMAP_P_PAIR_PREPARE)
     bool branches = false;   // this frame runs as two branches (DSPMAP_P_FRAME_BRANCHES; see KernelScratch::tile_cls)
     bool sparse = false; // most tiles hold nothing (dspmap::sparse_mode): k_predict's variant that leaves such tiles first
     const FrameParams* hpv = nullptr;   // (host memory) a frame queued as PLAIN launches through the parameter ring: the block that was just pushed into its ring
@@ -113,7 +114,9 @@ void launch_pyr_kept(const LaunchCtx& c, const int* kstar, int* kept);   // afte
 void launch_pyr_prepare(const LaunchCtx& c);   // range sort + full-list selection of the pyramid lists, work items (idempotent)
 void launch_ck_partial(const LaunchCtx& c, bool prepared = false, bool with_fix = true);   // with_fix: the first workgroups run k_place_fix's pass     // launch_pyr_prepare (unless already queued) + the Ck pass
 void launch_ck_finalize(const LaunchCtx& c);
-int launch_weight_update(const LaunchCtx& c);   // returns which k_weight it launched: 1 = <false> (every pair evaluated, far ones masked), 2 = <true> (far pairs branched over)
+bool pair_self_legal(const LaunchCtx& c);        // this configuration can run the self-mapped pair kernels: every pair evaluated, unsharded, np and capp within their LDS tables
+void launch_ck_partial_self(const LaunchCtx& c);   // the Ck pass on the lists as registered: no launch_pyr_prepare; overfull lists are sorted, cut and re-slotted by its extra workgroups
+int launch_weight_update(const LaunchCtx& c, bool self = false);   // self: after launch_ck_partial_self (only where pair_self_legal);   // returns which k_weight it launched: 1 = <false> (every pair evaluated, far ones masked), 2 = <true> (far pairs branched over)
 // mapAddNewBornParticlesByObservation (:796-921)
 void launch_birth(const LaunchCtx& c, int n_birth, bool in_frame, bool all_static);  // in_frame: between k_weight and k_resample of a whole frame
 void launch_birth_split(const LaunchCtx& c, int n_birth);

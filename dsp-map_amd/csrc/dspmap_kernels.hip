@@ -180,9 +180,13 @@ extern "C" int dspmap_debug_pyr_prof(long long* out, int n) { return (int)hipMem
 #else
 #define PSTAMP(k) do { } while (0)
 #endif
-__device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState& s, int b) {
-    __shared__ int s_hist[PS_NBK], s_base[PS_NBK];
-    __shared__ int s_sel[8192];
+// NT threads per workgroup; the selection takes DIG bits per pass in s_sel[1 << DIG] (k_pyr_prepare: 1024 threads and 13 bits; the overfull
+// path of the self-mapped k_ck_partial: 256 threads and 12 bits, in that kernel's dynamic LDS).  The threshold the selection finds -- the
+// capp-th smallest key -- and everything that follows from it depend on neither.
+template <int NT, int DIG>
+__device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState& s, int b, int* s_sel, int* s_hist, int* s_base) {
+    constexpr int NSEL = 1 << DIG, BPT = NSEL / NT;   // bins of a selection pass, bins per thread
+    constexpr int PSU_ = NT == 1024 ? PSU : 1;        // list entries per thread and step (the rare path inside k_ck_partial_self: few registers)
     __shared__ int s_pick[2];
     __shared__ int s_scan[17];
     const int tid = threadIdx.x;
@@ -212,30 +216,30 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
         // entries away although its own share is short of the capacity, and keeps fewer than CAPP of them
         kstar = s.pyr_kstar[b];
     } else if (P_all > d.capp) {
-        // keys are below v_glob * slots: 13 bits per pass (8192 bins), highest digits first
+        // keys are below v_glob * slots: DIG bits per pass, highest digits first
         const unsigned kmax = (unsigned)d.v_glob * (unsigned)d.slots;
         const int nbits = 32 - __clz((int)max(kmax, 2u) - 1);
-        const int npass = (nbits + 12) / 13;
+        const int npass = (nbits + DIG - 1) / DIG;
         unsigned prefix = 0;
         int want = d.capp;
         for (int ps = npass - 1; ps >= 0; --ps) {
-            const int shift = ps * 13;
-            for (int q = tid; q < 8192; q += 1024) s_sel[q] = 0;
+            const int shift = ps * DIG;
+            for (int q = tid; q < NSEL; q += NT) s_sel[q] = 0;
             __syncthreads();
-            for (int i00 = 0; i00 < P_all; i00 += 1024 * PSU) {
-                unsigned k_u[PSU];
+            for (int i00 = 0; i00 < P_all; i00 += NT * PSU_) {
+                unsigned k_u[PSU_];
 #pragma unroll
-                for (int u = 0; u < PSU; ++u) k_u[u] = (unsigned)src_key[min(i00 + u * 1024 + tid, P_all - 1)];   // (the step's loads together)
+                for (int u = 0; u < PSU_; ++u) k_u[u] = (unsigned)src_key[min(i00 + u * NT + tid, P_all - 1)];   // (the step's loads together)
 #pragma unroll
-                for (int u = 0; u < PSU; ++u) {
-                const int i = i00 + u * 1024 + tid;
+                for (int u = 0; u < PSU_; ++u) {
+                const int i = i00 + u * NT + tid;
                 int bin = -1;
                 if (i < P_all) {
                     const unsigned k = k_u[u];
-                    if (ps == npass - 1 || (k >> (shift + 13)) == (prefix >> (shift + 13))) bin = (int)((k >> shift) & 8191u);
+                    if (ps == npass - 1 || (k >> (shift + DIG)) == (prefix >> (shift + DIG))) bin = (int)((k >> shift) & (unsigned)(NSEL - 1));
                 }
                 // the keys of a pyramid share their HIGH bits: in the first pass one LDS atomic per distinct bin of a wavefront, not one
-                // per lane; the lower digits scatter over the 8192 bins -- there the grouping loop would run once per lane (round 6)
+                // per lane; the lower digits scatter over the bins -- there the grouping loop would run once per lane (round 6)
                 if (ps == npass - 1) {
                     u64 todo = __ballot(bin >= 0);
                     while (todo) {
@@ -248,23 +252,25 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
                 } else if (bin >= 0) atomicAdd(&s_sel[bin], 1);
                 }
             }
-            for (int q = tid; q < n_sp; q += 1024) {
+            for (int q = tid; q < n_sp; q += NT) {
                 if (s.pool_pyr[q] != b) continue;
                 const unsigned k = (unsigned)src_key[sp0 - (size_t)b * d.capa + q];
-                if (ps == npass - 1 || (k >> (shift + 13)) == (prefix >> (shift + 13))) atomicAdd(&s_sel[(k >> shift) & 8191u], 1);
+                if (ps == npass - 1 || (k >> (shift + DIG)) == (prefix >> (shift + DIG))) atomicAdd(&s_sel[(k >> shift) & (unsigned)(NSEL - 1)], 1);
             }
             __syncthreads();
-            {   // the bin that holds the want-th key: thread t owns bins [8t, 8t + 8); exclusive prefix over the threads
-                int c8[8], mine = 0;
+            {   // the bin that holds the want-th key: thread t owns bins [BPT t, BPT t + BPT); exclusive prefix over the threads
+                constexpr bool HOLD = BPT <= 8;   // (more bins per thread: read twice instead of held in registers)
+                int c8[HOLD ? BPT : 1], mine = 0;
 #pragma unroll
-                for (int q = 0; q < 8; ++q) { c8[q] = s_sel[tid * 8 + q]; mine += c8[q]; }
+                for (int q = 0; q < BPT; ++q) { const int cq = s_sel[tid * BPT + q]; if (HOLD) c8[q] = cq; mine += cq; }
                 int tot;
                 int ex = block_excl_scan_1024(mine, s_scan, &tot);
                 if (ex < want && want <= ex + mine) {
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        if (ex < want && want <= ex + c8[q]) { s_pick[0] = tid * 8 + q; s_pick[1] = want - ex; }
-                        ex += c8[q];
+                    for (int q = 0; q < BPT; ++q) {
+                        const int cq = HOLD ? c8[HOLD ? q : 0] : s_sel[tid * BPT + q];
+                        if (ex < want && want <= ex + cq) { s_pick[0] = tid * BPT + q; s_pick[1] = want - ex; }
+                        ex += cq;
                     }
                 }
             }
@@ -296,18 +302,18 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
     };
     // (PSU entries per thread and step, their loads issued together: a step is one memory round trip, ~1.5 us, and a list of config E
     // has 55 k entries -- 54 steps per pass at one entry per thread: 75 + 80 us for the two passes of the longest lists, round 5)
-    for (int i0 = tid; i0 < P_all; i0 += 1024 * PSU) {
-        int key_u[PSU];
-        float4 r_u[PSU];
+    for (int i0 = tid; i0 < P_all; i0 += NT * PSU_) {
+        int key_u[PSU_];
+        float4 r_u[PSU_];
 #pragma unroll
-        for (int u = 0; u < PSU; ++u) {   // unconditional loads (clamped index): a predicated load would be waited for before the next is issued
-            const int ic = min(i0 + u * 1024, P_all - 1);
+        for (int u = 0; u < PSU_; ++u) {   // unconditional loads (clamped index): a predicated load would be waited for before the next is issued
+            const int ic = min(i0 + u * NT, P_all - 1);
             key_u[u] = src_key[ic];
             r_u[u] = src[ic];
         }
 #pragma unroll
-        for (int u = 0; u < PSU; ++u) {
-        const int i = i0 + u * 1024;
+        for (int u = 0; u < PSU_; ++u) {
+        const int i = i0 + u * NT;
         if (i >= P_all) continue;
         const int key_i = key_u[u];
         const float4 r_i = r_u[u];
@@ -315,7 +321,7 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
         else if (key_i != 0x7fffffff) { turn_away(i); ++removed; }
         }
     }
-    for (int q = tid; q < n_sp; q += 1024) {   // (the spill pool: its entries of this pyramid, relative to the list's base)
+    for (int q = tid; q < n_sp; q += NT) {   // (the spill pool: its entries of this pyramid, relative to the list's base)
         if (s.pool_pyr[q] != b) continue;
         const size_t i = sp0 - (size_t)b * d.capa + q;
         const int key_i = src_key[i];
@@ -342,22 +348,22 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
     {
         // software-pipelined: the NEXT step's loads are issued before this step's (scattered) stores -- loads and stores share one
         // in-order counter on this part, so a step that waits for its loads also waits for every store issued before them
-        int key_u[PSU], sl_u[PSU], key_n[PSU], sl_n[PSU];
-        float4 r_u[PSU], r_n[PSU];
-        auto fetch = [&](int i0, int (&kk)[PSU], int (&ss)[PSU], float4 (&rr)[PSU]) {
+        int key_u[PSU_], sl_u[PSU_], key_n[PSU_], sl_n[PSU_];
+        float4 r_u[PSU_], r_n[PSU_];
+        auto fetch = [&](int i0, int (&kk)[PSU_], int (&ss)[PSU_], float4 (&rr)[PSU_]) {
 #pragma unroll
-            for (int u = 0; u < PSU; ++u) {
-                const int ic = min(i0 + u * 1024, P_all - 1);
+            for (int u = 0; u < PSU_; ++u) {
+                const int ic = min(i0 + u * NT, P_all - 1);
                 kk[u] = src_key[ic]; rr[u] = src[ic]; ss[u] = src_slot[ic];
             }
         };
         fetch(tid, key_u, sl_u, r_u);
-        for (int i0 = tid; i0 < P_all; i0 += 1024 * PSU) {
-            const bool more = i0 + 1024 * PSU < P_all;
-            if (more) fetch(i0 + 1024 * PSU, key_n, sl_n, r_n);
+        for (int i0 = tid; i0 < P_all; i0 += NT * PSU_) {
+            const bool more = i0 + NT * PSU_ < P_all;
+            if (more) fetch(i0 + NT * PSU_, key_n, sl_n, r_n);
 #pragma unroll
-            for (int u = 0; u < PSU; ++u) {
-                const int i = i0 + u * 1024;
+            for (int u = 0; u < PSU_; ++u) {
+                const int i = i0 + u * NT;
                 if (i >= P_all || key_u[u] > kstar) continue;
                 const float4 r = r_u[u];
                 const int k = range_bucket(d, r);
@@ -372,10 +378,10 @@ __device__ __forceinline__ void pyr_sort_block(const MapDims& d, const DevState&
             }
             if (more) {
 #pragma unroll
-                for (int u = 0; u < PSU; ++u) { key_u[u] = key_n[u]; sl_u[u] = sl_n[u]; r_u[u] = r_n[u]; }
+                for (int u = 0; u < PSU_; ++u) { key_u[u] = key_n[u]; sl_u[u] = sl_n[u]; r_u[u] = r_n[u]; }
             }
         }
-        for (int q = tid; q < n_sp; q += 1024) {   // the kept entries of the spill pool
+        for (int q = tid; q < n_sp; q += NT) {   // the kept entries of the spill pool
             if (s.pool_pyr[q] != b) continue;
             const size_t i = sp0 + q;
             const int key = s.fov_key[i];
@@ -403,8 +409,10 @@ __device__ __forceinline__ void pyr_items_block(const MapDims& d, const DevState
 // per CU and spills, 37.8 against 13 us on lists that need no selection, LOG.md)
 __global__ void __launch_bounds__(1024, 8) k_pyr_prepare(MapDims d, DevState s, int* __restrict__ ck_items, int* __restrict__ wu_items,
                                                       int* __restrict__ n_items, int* __restrict__ nb_tab) {
+    __shared__ int s_sel[8192];
+    __shared__ int s_hist[PS_NBK], s_base[PS_NBK];
     if ((int)blockIdx.x == d.np) pyr_items_block(d, s, ck_items, wu_items, n_items, nb_tab);
-    else pyr_sort_block(d, s, (int)blockIdx.x);
+    else pyr_sort_block<1024, 13>(d, s, (int)blockIdx.x, s_sel, s_hist, s_base);
 }
 
 // --------------------------------------------------------------------------
@@ -790,6 +798,101 @@ __device__ __forceinline__ void neighbor_load(const MapDims& d, const int* __res
     else if (tid >= 32 && tid - 32 <= d.nbins) s_off[tid - 32] = tab[(size_t)(DSP_MAX_NBINS + tid - 32) * d.np];
 }
 
+struct PairHead;
+__device__ __forceinline__ void neighbor_self(const MapDims& d, const PairHead& H, int b, int* s_bin, int* s_off);
+// One item of k_ck_partial: the chunk's `npart` particles of pyramid b (`r`: this thread's, the first wave's count) against the observations
+// of its neighbourhood -- from k_pyr_prepare's table, or (SELF) from the counts in the workgroup's PairHead.  All threads of the workgroup
+// call, behind a barrier that ends the previous item's use of LDS.
+template <bool SELF>
+__device__ __forceinline__ void ck_item_pairs(const MapDims& d, const DevState& s, const float p_det, const float cull_r, const float sigma_ob, const float inv_sigma_ob, const float pdf_c3,
+                                              const int* __restrict__ nb_tab, const PairHead* H,
+                                              int b, int npart, float4 r, float4* s_z) {
+    int* s_oi = reinterpret_cast<int*>(s_z + (size_t)d.nbins * DSP_OBS_CAP);   // ... and their global indices
+    __shared__ float4 s_p[CK_PCH];
+    __shared__ int s_bin[DSP_MAX_NBINS];
+    __shared__ int s_off[DSP_MAX_NBINS + 1];
+    __shared__ float s_rng[2];
+    __shared__ int s_n;
+    const int tid = threadIdx.x;
+    if (!SELF) neighbor_load(d, nb_tab, b, s_bin, s_off);
+    else if (tid >> 6 == 1) neighbor_self(d, *H, b, s_bin, s_off);
+    if (tid < CK_PCH) {   // the first wave holds the chunk: its range interval decides which observations matter
+        const float len = sqrtf(r.x * r.x + r.y * r.y + r.z * r.z);
+        float lo = tid < npart ? len : 3.0e38f, hi = tid < npart ? len : -3.0e38f;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o, WAVE)); hi = fmaxf(hi, __shfl_xor(hi, o, WAVE)); }
+        r.w = p_det * r.w;  // P_detection * weight (pre-update weights), :732
+        // The radius beyond which this chunk's terms are EXACTLY zero: a term is snapped to the 2^-34 grid before it is added
+        // (ck_snap), so c3 * w * exp2(-K s) < 2^-35 adds nothing; ranges R apart mean a distance >= R, i.e.
+        // s >= (1000 R / sigma - sqrt(3))^2 for the truncated table indices (u in (1000 z - 1, 1000 z]).  With the chunk's
+        // largest weight: s > (log2(c3 w) + 35) / K  <=>  R > sigma * (sqrt(.) / 1000 + 0.0018); 0.01 sigma of margin covers
+        // the roundings of the two ranges.  Never wider than the handle's cull radius (which also bounds the +-9.9 clamp).
+        float wm = tid < npart ? r.w : 0.f;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) wm = fmaxf(wm, __shfl_xor(wm, o, WAVE));
+        const float need = (__log2f(pdf_c3 * wm) + 35.f) * (1.f / 7.213475204444817e-07f);
+        const float rad = fminf(cull_r, sigma_ob * (sqrtf(fmaxf(need, 0.f)) * 0.001f + 0.01f));
+        if (tid == 0) { s_rng[0] = lo - rad; s_rng[1] = hi + rad; s_n = 0; }
+        s_p[tid] = r;
+    }
+    __syncthreads();
+    const int O_all = s_off[d.nbins];
+    if (O_all == 0) return;
+    {   // keep the observations whose range lies within 9 sigma of the chunk's (compacted, any order: Ck is order-free)
+        const float lo = s_rng[0], hi = s_rng[1];
+        for (int base = 0; base < O_all; base += CK_TPB) {
+            const int o = base + tid;
+            bool keep = false;
+            float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            int oi = 0;
+            if (o < O_all) {
+                int k = 0;
+                for (int q = 1; q < d.nbins; ++q) k += (o >= s_off[q]) ? 1 : 0;
+                oi = s_bin[k] * DSP_OBS_CAP + (o - s_off[k]);
+                z = s.obs[oi];
+                keep = z.w >= lo && z.w <= hi;
+            }
+            const u64 bal = __ballot(keep);
+            int wbase = 0;
+            if (lane_id() == 0 && bal) wbase = atomicAdd(&s_n, (int)__popcll(bal));
+            wbase = __builtin_amdgcn_readfirstlane(wbase);
+            if (keep) {
+                const int pos = wbase + (int)__popcll(bal & lanemask_lt());
+                s_z[pos] = z;
+                s_oi[pos] = oi;
+            }
+        }
+    }
+    __syncthreads();
+    const int O = s_n;
+    if (O == 0) return;
+    // lanes = (observation, particle group): with few observations the 256 lanes split the particle
+    // chunk G ways so that every lane is busy and the loop is short; partial sums meet in the (fixed-point, order-independent) atomic
+    const int opad = O <= 64 ? 64 : (O <= 128 ? 128 : 256);
+    const int G = CK_TPB / opad;
+    const int g = tid / opad;
+    for (int o = tid % opad; o < O; o += opad) {
+        const int oi = s_oi[o];
+        const float4 z = s_z[o];
+        // every term is snapped to the 2^-34 grid before it is added, so the (double) partial sum is exact and the
+        // total does not depend on the order of the particles in the pyramid's list either (built with atomics)
+        double acc = 0.0;
+        int i = g;
+        for (; i + G < npart; i += 2 * G) {   // two particles per iteration: packed fp32
+            const float4 p = s_p[i], p2 = s_p[i + G];
+            const f2v gk = pair_gk2(f2v{p.x, p2.x}, f2v{p.y, p2.y}, f2v{p.z, p2.z}, f2v{z.x, z.x}, f2v{z.y, z.y}, f2v{z.z, z.z},
+                                    sigma_ob, inv_sigma_ob, pdf_c3);
+            acc = __dadd_rn(acc, ck_snap(p.w * gk.x));
+            acc = __dadd_rn(acc, ck_snap(p2.w * gk.y));
+        }
+        if (i < npart) {
+            const float4 p = s_p[i];
+            acc = __dadd_rn(acc, ck_snap(p.w * pair_gk(p.x, p.y, p.z, z.x, z.y, z.z, sigma_ob, inv_sigma_ob, pdf_c3)));
+        }
+        atomicAdd(reinterpret_cast<unsigned long long*>(&s.obs_ck[oi]), (unsigned long long)__double2ll_rn(acc * CK_FIX_SCALE));
+    }
+}
+
 __global__ void __launch_bounds__(CK_TPB) k_ck_partial(MapDims d, DevState s, FilterParams fp, const int* __restrict__ items,
                                                        const int* __restrict__ n_items, const int* __restrict__ nb_tab,
                                                        const float4* __restrict__ in_rec, const u64* __restrict__ omask, const int* __restrict__ refs, int with_fix) {
@@ -798,12 +901,6 @@ __global__ void __launch_bounds__(CK_TPB) k_ck_partial(MapDims d, DevState s, Fi
     extern __shared__ float4 s_z[];
     if ((int)blockIdx.x < PF_WG) { if (with_fix) place_fix_block(d, s, in_rec, omask, refs, reinterpret_cast<int*>(s_z), (int)blockIdx.x, PF_WG); return; }
     const int BX = (int)blockIdx.x - PF_WG, GX = (int)gridDim.x - PF_WG;   // [nbins * DSP_OBS_CAP] the neighbourhood's observations within range of the chunk ...
-    int* s_oi = reinterpret_cast<int*>(s_z + (size_t)d.nbins * DSP_OBS_CAP);   // ... and their global indices
-    __shared__ float4 s_p[CK_PCH];
-    __shared__ int s_bin[DSP_MAX_NBINS];
-    __shared__ int s_off[DSP_MAX_NBINS + 1];
-    __shared__ float s_rng[2];
-    __shared__ int s_n;
     const int tid = threadIdx.x;
     const int total = n_items[0], pch = n_items[2];
     int item_next = BX < total ? items[BX] : 0;
@@ -820,82 +917,193 @@ __global__ void __launch_bounds__(CK_TPB) k_ck_partial(MapDims d, DevState s, Fi
         if (it + GX < total) item_next = items[it + GX];
         const int npart = min(pch, P - start);
         __syncthreads();  // LDS reuse across items
-        neighbor_load(d, nb_tab, b, s_bin, s_off);
-        if (tid < CK_PCH) {   // the first wave holds the chunk: its range interval decides which observations matter
-            const float len = sqrtf(r.x * r.x + r.y * r.y + r.z * r.z);
-            float lo = tid < npart ? len : 3.0e38f, hi = tid < npart ? len : -3.0e38f;
+        ck_item_pairs<false>(d, s, fp.p_det, fp.cull_r, fp.sigma_ob, fp.inv_sigma_ob, fp.pdf_c3, nb_tab, nullptr, b, npart, r, s_z);
+    }
+}
+
+// --------------------------------------------------------------------------
+// SELF-MAPPED pair kernels (maps that take k_weight<false>, unsharded; launch_ck_partial_self / launch_weight_update).
+// What k_pyr_prepare hands the pair kernels on such a map is a function of 2 x np ints -- pyr_cnt[] and obs_cnt[], final when k_place
+// ends -- unless a list is overfull: the range order of a list changes nothing (k_weight<false> evaluates every pair, k_ck_partial only
+// narrows its window with it: dropped terms are zero on the Ck grid), and the cut to capp entries keeps every entry of a list that has no
+// more.  So every workgroup loads the 2 x np counts in one round trip (the one it would spend on items[BX]) and derives in LDS what
+// pyr_items_block derives: P, pch, the items per pyramid and their exclusive prefix (ck_head; k_weight's prefix, which needs every
+// neighbourhood's O, is derived by ONE workgroup of the Ck launch and loaded by k_weight's: wu_head); item -> (pyramid, chunk) is a search
+// in the prefix (pyramid-major, then chunk: pyr_items_block's order), the neighbourhood table of its pyramid a dozen LDS reads.  Particles are read from
+// the lists as k_predict / k_place left them (fov_rec, fov_slot: capa entries per pyramid).
+// Z = some pyr_cnt[b] > capp (every workgroup of both launches sees the same words and agrees on it): the np extra workgroups of the Ck
+// launch, which otherwise return at once, do what k_pyr_prepare does -- pair_overfull_block -- and k_weight reads the sorted lists.
+// --------------------------------------------------------------------------
+#define PH_MAXNP 512   // pyramids the LDS tables hold (two per thread); maps with more keep k_pyr_prepare
+struct PairHead {
+    int pre[PH_MAXNP + 1];           // exclusive prefix of the items per pyramid; [b >= np] = the total
+    unsigned short P[PH_MAXNP];      // list entries the pair kernels read: min(pyr_cnt, capp) (capp < 65536 on this path)
+    unsigned char oc[PH_MAXNP];      // obs_cnt (<= DSP_OBS_CAP - 1)
+    int red[16];                     // per-wave partial sums of the two steps
+    int cur;                         // the pyramid of the item at hand
+};
+// observations in pyramid b's neighbourhood (pyr_items_block's O)
+__device__ __forceinline__ int head_obs(const MapDims& d, const PairHead& H, int b) {
+    const int h0 = b / d.np_v, v0 = b - h0 * d.np_v;
+    int O = 0;
+    for (int i = -d.nn; i <= d.nn; ++i)
+        for (int j = -d.nn; j <= d.nn; ++j) {
+            const int h = h0 + i, v = v0 + j;
+            if (h >= 0 && h < d.np_h && v >= 0 && v < d.np_v) O += H.oc[h * d.np_v + v];
+        }
+    return O;
+}
+// The head of k_ck_partial_self; all 256 threads call.  Every workgroup: the counts, Z, pch and the prefix of ceil(P / pch) per pyramid -- the
+// pyramids nobody observes included: their items return when they find O == 0, which keeps the neighbourhood sums out of every workgroup's
+// head (the head's instructions are paid by every workgroup of the launch at once).  Workgroup 0 (`totals`) also derives what only
+// depends on those sums: the item counts as pyr_items_block reports them (n_items[0..2]) and the prefix of k_weight's items, which it
+// leaves in wu_pre[0 .. PH_MAXNP] for that launch.  Returns the number of items.
+__device__ __forceinline__ int ck_head(const MapDims& d, const DevState& s, PairHead& H, int& pch, bool& Z, int* totals, int* __restrict__ wu_pre) {
+    const int tid = threadIdx.x, w = tid >> 6;
+    const int b0 = 2 * tid, b1 = b0 + 1;
+    const int c0 = b0 < d.np ? s.pyr_cnt[b0] : 0, c1 = b1 < d.np ? s.pyr_cnt[b1] : 0;
+    const int o0 = b0 < d.np ? s.obs_cnt[b0] : 0, o1 = b1 < d.np ? s.obs_cnt[b1] : 0;
+    const int P0 = min(c0, d.capp), P1 = min(c1, d.capp);
+    H.P[b0] = (unsigned short)P0; H.P[b1] = (unsigned short)P1;
+    H.oc[b0] = (unsigned char)o0; H.oc[b1] = (unsigned char)o1;
+    const int inc_p = wave_incl_scan_i(P0 + P1);
+    const u64 over = __ballot(c0 > d.capp || c1 > d.capp);
+    if ((tid & 63) == 63) { H.red[w] = inc_p; H.red[4 + w] = over != 0ull ? 1 : 0; }
+    __syncthreads();
+    const int tot_fov = (H.red[0] + H.red[1]) + (H.red[2] + H.red[3]);
+    Z = (H.red[4] | H.red[5] | H.red[6] | H.red[7]) != 0;
+    pch = tot_fov <= CK_SMALL_FOV ? CK_PCH / 2 : CK_PCH;
+    const int sh = pch == CK_PCH ? 6 : 5;
+    const int n0 = (P0 + pch - 1) >> sh, n1 = (P1 + pch - 1) >> sh;
+    const int inc = wave_incl_scan_i(n0 + n1);
+    if ((tid & 63) == 63) H.red[8 + w] = inc;
+    __syncthreads();
+    int before = 0, total = 0;
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o, WAVE)); hi = fmaxf(hi, __shfl_xor(hi, o, WAVE)); }
-            r.w = fp.p_det * r.w;  // P_detection * weight (pre-update weights), :732
-            // The radius beyond which this chunk's terms are EXACTLY zero: a term is snapped to the 2^-34 grid before it is added
-            // (ck_snap), so c3 * w * exp2(-K s) < 2^-35 adds nothing; ranges R apart mean a distance >= R, i.e.
-            // s >= (1000 R / sigma - sqrt(3))^2 for the truncated table indices (u in (1000 z - 1, 1000 z]).  With the chunk's
-            // largest weight: s > (log2(c3 w) + 35) / K  <=>  R > sigma * (sqrt(.) / 1000 + 0.0018); 0.01 sigma of margin covers
-            // the roundings of the two ranges.  Never wider than the handle's cull radius (which also bounds the +-9.9 clamp).
-            float wm = tid < npart ? r.w : 0.f;
+    for (int q = 0; q < 4; ++q) { const int t = H.red[8 + q]; total += t; before += q < w ? t : 0; }
+    const int ex = before + inc - (n0 + n1);
+    H.pre[b0] = ex; H.pre[b1] = ex + n0;
+    if (tid == 0) H.pre[PH_MAXNP] = total;
+    if (totals) {   // (workgroup 0)
+        const int O0 = b0 < d.np ? head_obs(d, H, b0) : 0, O1 = b1 < d.np ? head_obs(d, H, b1) : 0;
+        const int pw0 = WU_TPB / wu_split(O0), pw1 = WU_TPB / wu_split(O1);
+        const int wu0 = b0 < d.np ? max(1, (P0 + pw0 - 1) / pw0) : 0, wu1 = b1 < d.np ? max(1, (P1 + pw1 - 1) / pw1) : 0;   // chunk 0 always exists: it owns the bin's 1/Ck sum
+        const int inc_w = wave_incl_scan_i(wu0 + wu1);
+        const int ck = wave_sum_i((O0 > 0 ? n0 : 0) + (O1 > 0 ? n1 : 0));
+        if ((tid & 63) == 63) { H.red[12 + w] = inc_w; H.red[w] = ck; }   // (red[0..4) were read before the barrier above)
+        __syncthreads();
+        int bw = 0, tw = 0;
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) wm = fmaxf(wm, __shfl_xor(wm, o, WAVE));
-            const float need = (__log2f(fp.pdf_c3 * wm) + 35.f) * (1.f / 7.213475204444817e-07f);
-            const float rad = fminf(fp.cull_r, fp.sigma_ob * (sqrtf(fmaxf(need, 0.f)) * 0.001f + 0.01f));
-            if (tid == 0) { s_rng[0] = lo - rad; s_rng[1] = hi + rad; s_n = 0; }
-            s_p[tid] = r;
+        for (int q = 0; q < 4; ++q) { const int t = H.red[12 + q]; tw += t; bw += q < w ? t : 0; }
+        const int exw = bw + inc_w - (wu0 + wu1);
+        wu_pre[b0] = exw; wu_pre[b1] = exw + wu0;
+        if (tid == 0) { wu_pre[PH_MAXNP] = tw; totals[0] = (H.red[0] + H.red[1]) + (H.red[2] + H.red[3]); totals[1] = tw; totals[2] = pch; }
+    }
+    __syncthreads();
+    return total;
+}
+// The head of k_weight<false, true>: the counts and workgroup 0's prefix (ck_head) into LDS -- loads and one barrier.  Returns the number of items.
+__device__ __forceinline__ int wu_head(const MapDims& d, const DevState& s, PairHead& H, bool& Z, const int* __restrict__ wu_pre) {
+    const int tid = threadIdx.x, w = tid >> 6;
+    const int b0 = 2 * tid, b1 = b0 + 1;
+    const int c0 = b0 < d.np ? s.pyr_cnt[b0] : 0, c1 = b1 < d.np ? s.pyr_cnt[b1] : 0;
+    const int o0 = b0 < d.np ? s.obs_cnt[b0] : 0, o1 = b1 < d.np ? s.obs_cnt[b1] : 0;
+    const int p0 = wu_pre[b0], p1 = wu_pre[b1], total = wu_pre[PH_MAXNP];
+    H.P[b0] = (unsigned short)min(c0, d.capp); H.P[b1] = (unsigned short)min(c1, d.capp);
+    H.oc[b0] = (unsigned char)o0; H.oc[b1] = (unsigned char)o1;
+    H.pre[b0] = p0; H.pre[b1] = p1;
+    if (tid == 0) H.pre[PH_MAXNP] = total;
+    const u64 over = __ballot(c0 > d.capp || c1 > d.capp);
+    if ((tid & 63) == 0) H.red[4 + w] = over != 0ull ? 1 : 0;
+    __syncthreads();
+    Z = (H.red[4] | H.red[5] | H.red[6] | H.red[7]) != 0;
+    return total;
+}
+// the pyramid of item `it`: the b with pre[b] <= it < pre[b + 1] (one thread finds it; empty pyramids have pre[b] == pre[b + 1])
+__device__ __forceinline__ void head_find(PairHead& H, int it) {
+    const int b0 = 2 * (int)threadIdx.x;
+    const int p0 = H.pre[b0], p1 = H.pre[b0 + 1], p2 = H.pre[b0 + 2];
+    if (p0 <= it && it < p1) H.cur = b0;
+    if (p1 <= it && it < p2) H.cur = b0 + 1;
+}
+// neighbor_load's tables from the counts in LDS: one whole wave calls (lanes = the (2 nn + 1)^2 bins, h-major; valid ones compacted,
+// then -1 bins whose offset is O)
+__device__ __forceinline__ void neighbor_self(const MapDims& d, const PairHead& H, int b, int* s_bin, int* s_off) {
+    const int l = lane_id(), side = 2 * d.nn + 1;
+    const int h0 = b / d.np_v, v0 = b - h0 * d.np_v;
+    const int h = h0 + l / side - d.nn, v = v0 + l % side - d.nn;
+    const bool in = l < d.nbins, valid = in && h >= 0 && h < d.np_h && v >= 0 && v < d.np_v;
+    const int bin = valid ? h * d.np_v + v : -1;
+    const int c = valid ? (int)H.oc[valid ? bin : 0] : 0;
+    const int inc = wave_incl_scan_i(c);
+    const int O = __shfl(inc, 63, WAVE);
+    const u64 bv = __ballot(valid), bp = __ballot(in && !valid);
+    if (in) {
+        const int pos = valid ? (int)__popcll(bv & lanemask_lt()) : (int)__popcll(bv) + (int)__popcll(bp & lanemask_lt());
+        s_bin[pos] = bin;
+        s_off[pos] = valid ? inc - c : O;
+    }
+    if (l == 0) s_off[d.nbins] = O;
+}
+
+// Overfull lists (Z), extra workgroup b of the self-mapped Ck launch: k_pyr_prepare's sort and cut of list b, then this pyramid's own Ck
+// terms from its sorted, cut list, chunk by chunk (no other workgroup's work is needed for either); the last workgroup to finish -- a
+// fence and a counter, nobody waits -- re-slots the arrivals of every dirty voxel (k_place_fix's pass).  Slow, exact, rare.
+__device__ __forceinline__ void pair_overfull_block(const MapDims& d, const DevState& s, const float p_det, const float cull_r, const float sigma_ob, const float inv_sigma_ob, const float pdf_c3, PairHead& H, int b, int pch, int* done,
+                                                    const float4* __restrict__ in_rec, const u64* __restrict__ omask, const int* __restrict__ refs,
+                                                    float4* s_z) {
+    const int tid = threadIdx.x;
+    int* s_sel = reinterpret_cast<int*>(s_z);   // 4096 bins of the selection, then the sort's two tables of PS_NBK range buckets
+    pyr_sort_block<CK_TPB, 12>(d, s, b, s_sel, s_sel + 4096, s_sel + 4096 + PS_NBK);
+    __syncthreads();   // (the sorted list was written by this workgroup; s_z is free again)
+    const int P = H.P[b];
+    if (head_obs(d, H, b) > 0) {
+        for (int start = 0; start < P; start += pch) {
+            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (tid < pch && start + tid < d.capp) r = s.fov_rec_s[(size_t)b * d.capp + start + tid];
+            __syncthreads();  // LDS reuse across chunks
+            ck_item_pairs<true>(d, s, p_det, cull_r, sigma_ob, inv_sigma_ob, pdf_c3, nullptr, &H, b, min(pch, P - start), r, s_z);
         }
+    }
+    __syncthreads();
+    __shared__ int s_last;
+    if (tid == 0) {
+        __threadfence();
+        const int q = atomicAdd(done, 1);
+        s_last = q == d.np - 1 ? 1 : 0;
+        if (s_last) *done = 0;   // (the next overfull frame counts from zero)
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    place_fix_block(d, s, in_rec, omask, refs, reinterpret_cast<int*>(s_z), 0, 1);
+}
+
+// k_ck_partial on the lists as they were registered.  One round of workgroups strides over the items; with overfull lists (Z) workgroup b < np
+// takes list b instead (gridDim.x >= np) and the others return.
+__global__ void __launch_bounds__(CK_TPB, 7) k_ck_partial_self(MapDims d, DevState s, FilterParams fp, int* __restrict__ n_items, int* __restrict__ wu_pre,
+                                                            const float4* __restrict__ in_rec, const u64* __restrict__ omask, const int* __restrict__ refs) {
+    extern __shared__ float4 s_z[];
+    __shared__ PairHead H;
+    const int tid = threadIdx.x;
+    const int GX = (int)gridDim.x, BX = (int)blockIdx.x;
+    int pch; bool Z;
+    const int total = ck_head(d, s, H, pch, Z, BX == 0 ? n_items : nullptr, wu_pre);
+    if (Z) {
+        if (BX >= d.np) return;
+        if (BX == 0 && tid == 0) s.hint_out[4] = 1;   // the handle prepares the lists from the next frames on (dspmap_device_frame)
+        pair_overfull_block(d, s, fp.p_det, fp.cull_r, fp.sigma_ob, fp.inv_sigma_ob, fp.pdf_c3, H, BX, pch, n_items + 3, in_rec, omask, refs, s_z);
+        return;
+    }
+    for (int it = BX; it < total; it += GX) {
+        __syncthreads();  // LDS reuse across items
+        head_find(H, it);
         __syncthreads();
-        const int O_all = s_off[d.nbins];
-        if (O_all == 0) continue;
-        {   // keep the observations whose range lies within 9 sigma of the chunk's (compacted, any order: Ck is order-free)
-            const float lo = s_rng[0], hi = s_rng[1];
-            for (int base = 0; base < O_all; base += CK_TPB) {
-                const int o = base + tid;
-                bool keep = false;
-                float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                int oi = 0;
-                if (o < O_all) {
-                    int k = 0;
-                    for (int q = 1; q < d.nbins; ++q) k += (o >= s_off[q]) ? 1 : 0;
-                    oi = s_bin[k] * DSP_OBS_CAP + (o - s_off[k]);
-                    z = s.obs[oi];
-                    keep = z.w >= lo && z.w <= hi;
-                }
-                const u64 bal = __ballot(keep);
-                int wbase = 0;
-                if (lane_id() == 0 && bal) wbase = atomicAdd(&s_n, (int)__popcll(bal));
-                wbase = __builtin_amdgcn_readfirstlane(wbase);
-                if (keep) {
-                    const int pos = wbase + (int)__popcll(bal & lanemask_lt());
-                    s_z[pos] = z;
-                    s_oi[pos] = oi;
-                }
-            }
-        }
-        __syncthreads();
-        const int O = s_n;
-        if (O == 0) continue;
-        // lanes = (observation, particle group): with few observations the 256 lanes split the particle
-        // chunk G ways so that every lane is busy and the loop is short; partial sums meet in the (fixed-point, order-independent) atomic
-        const int opad = O <= 64 ? 64 : (O <= 128 ? 128 : 256);
-        const int G = CK_TPB / opad;
-        const int g = tid / opad;
-        for (int o = tid % opad; o < O; o += opad) {
-            const int oi = s_oi[o];
-            const float4 z = s_z[o];
-            // every term is snapped to the 2^-34 grid before it is added, so the (double) partial sum is exact and the
-            // total does not depend on the order of the particles in the pyramid's list either (built with atomics)
-            double acc = 0.0;
-            int i = g;
-            for (; i + G < npart; i += 2 * G) {   // two particles per iteration: packed fp32
-                const float4 p = s_p[i], p2 = s_p[i + G];
-                const f2v gk = pair_gk2(f2v{p.x, p2.x}, f2v{p.y, p2.y}, f2v{p.z, p2.z}, f2v{z.x, z.x}, f2v{z.y, z.y}, f2v{z.z, z.z},
-                                        fp.sigma_ob, fp.inv_sigma_ob, fp.pdf_c3);
-                acc = __dadd_rn(acc, ck_snap(p.w * gk.x));
-                acc = __dadd_rn(acc, ck_snap(p2.w * gk.y));
-            }
-            if (i < npart) {
-                const float4 p = s_p[i];
-                acc = __dadd_rn(acc, ck_snap(p.w * pair_gk(p.x, p.y, p.z, z.x, z.y, z.z, fp.sigma_ob, fp.inv_sigma_ob, fp.pdf_c3)));
-            }
-            atomicAdd(reinterpret_cast<unsigned long long*>(&s.obs_ck[oi]), (unsigned long long)__double2ll_rn(acc * CK_FIX_SCALE));
-        }
+        const int b = H.cur, chunk = it - H.pre[b], P = H.P[b];
+        const int start = chunk * pch;
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < pch && start + tid < d.capa) r = s.fov_rec[(size_t)b * d.capa + start + tid];
+        ck_item_pairs<true>(d, s, fp.p_det, fp.cull_r, fp.sigma_ob, fp.inv_sigma_ob, fp.pdf_c3, nullptr, &H, b, min(pch, P - start), r, s_z);
     }
 }
 
@@ -923,9 +1131,12 @@ __global__ void __launch_bounds__(512) k_ck_sum(MapDims d, DevState s, FilterPar
 // SKIP: far pairs are branched over (maps much larger than 9 sigma: most pairs are far and a wave's range-sorted
 // particles agree about it); otherwise every pair is evaluated two at a time with packed fp32 and far ones are
 // masked to zero.  Both variants add exactly the same terms.
-template <bool SKIP>
+// SELF (with SKIP false only): the self-mapped instantiation -- no item list, no neighbourhood table, the particles from the lists as they
+// were registered unless one was overfull (see pair_head)
+template <bool SKIP, bool SELF = false>
 __global__ void __launch_bounds__(WU_TPB) k_weight(MapDims d, DevState s, FilterParams fp, const int* __restrict__ items,
                                                    const int* __restrict__ n_items, const int* __restrict__ nb_tab) {
+    static_assert(!(SKIP && SELF), "the self-mapped k_weight evaluates every pair");
     extern __shared__ float4 s_o[];   // [nbins * DSP_OBS_CAP]: the neighbourhood's observations {x, y, z, P_d/Ck} ...
     float* s_len = reinterpret_cast<float*>(s_o + (size_t)d.nbins * DSP_OBS_CAP);   // ... and their ranges
     __shared__ int s_bin[DSP_MAX_NBINS];
@@ -933,14 +1144,29 @@ __global__ void __launch_bounds__(WU_TPB) k_weight(MapDims d, DevState s, Filter
     __shared__ float s_inv[WU_TPB / 64];
     __shared__ float s_mm[2 * WU_TPB / 64];
     __shared__ int s_wc[64];   // [2][4 waves][8 classes] per-wave kept counts of a staging round (double-buffered)
+    __shared__ PairHead H;   // (SELF)
     const int tid = threadIdx.x;
-    const int total = n_items[1];
+    int total; bool Z = true;
+    if (SELF) total = wu_head(d, s, H, Z, items);   // (items: the prefix k_ck_partial_self's workgroup 0 left)
+    else total = n_items[1];
+    // the lists this launch reads: sorted and cut (capp entries per pyramid), or as registered (capa)
+    const float4* __restrict__ rec = SELF && !Z ? s.fov_rec : s.fov_rec_s;
+    const int* __restrict__ rec_slot = SELF && !Z ? s.fov_slot : s.fov_slot_s;
+    const int rec_stride = SELF && !Z ? d.capa : d.capp;
     const float add = frame_lambda(s, fp) + fp.kappa;  // :737
     for (int it = blockIdx.x; it < total; it += gridDim.x) {
-        const int item = items[it];
-        const int b = item >> 12, chunk = item & 0xfff;
-        const int P = pyr_len(d, s, b);
-        __syncthreads();  // LDS reuse across items
+        int b, chunk, P;
+        if (SELF) {
+            __syncthreads();  // LDS reuse across items
+            head_find(H, it);
+            __syncthreads();
+            b = H.cur; chunk = it - H.pre[b]; P = H.P[b];
+        } else {
+            const int item = items[it];
+            b = item >> 12; chunk = item & 0xfff;
+            P = pyr_len(d, s, b);
+            __syncthreads();  // LDS reuse across items
+        }
         if (chunk == 0) {
             // final Ck of this pyramid's own observations + their sum of 1/Ck (:799-804)
             const int nob = s.obs_cnt[b];
@@ -956,7 +1182,8 @@ __global__ void __launch_bounds__(WU_TPB) k_weight(MapDims d, DevState s, Filter
             if (tid == 0) s.part_inv[b] = (s_inv[0] + s_inv[1]) + (s_inv[2] + s_inv[3]);
             if (P == 0) continue;
         }
-        neighbor_load(d, nb_tab, b, s_bin, s_off);
+        if (!SELF) neighbor_load(d, nb_tab, b, s_bin, s_off);
+        else if (tid < 64) neighbor_self(d, H, b, s_bin, s_off);
         __syncthreads();
         const int O = s_off[d.nbins];
         // SPL adjacent lanes share one particle and split the observation loop (short critical path when
@@ -972,8 +1199,8 @@ __global__ void __launch_bounds__(WU_TPB) k_weight(MapDims d, DevState s, Filter
         bool occluded = false;
         float dist = 0.f;
         if (valid) {
-            ri = (size_t)b * d.capp + i;
-            p = s.fov_rec_s[ri];
+            ri = (size_t)b * rec_stride + i;
+            p = rec[ri];
             const float maxlen = s.obs_maxlen[b];
             dist = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);
             occluded = maxlen > 0.f && dist > maxlen + fp.occl_margin;  // :761-765
@@ -1064,7 +1291,7 @@ __global__ void __launch_bounds__(WU_TPB) k_weight(MapDims d, DevState s, Filter
         if (spl >= 2) sum += __shfl_xor(sum, 1, WAVE);
         if (spl >= 4) sum += __shfl_xor(sum, 2, WAVE);
         if (spl >= 8) sum += __shfl_xor(sum, 4, WAVE);
-        if (valid && !occluded && sub == 0) s.w[s.fov_slot_s[ri]] = p.w * ((1.f - fp.p_det) + sum);  // :786
+        if (valid && !occluded && sub == 0) s.w[rec_slot[ri]] = p.w * ((1.f - fp.p_det) + sum);  // :786
     }
 }
 
@@ -1638,13 +1865,26 @@ void launch_ck_partial(const LaunchCtx& c, bool prepared, bool with_fix) {
     hipLaunchKernelGGL(k_ck_partial, dim3(4096 + PF_WG), dim3(CK_TPB), (sizeof(float4) + sizeof(int)) * (size_t)c.d.nbins * DSP_OBS_CAP, c.stream, c.d, c.s, c.fp, c.k.ck_items, c.k.n_items, c.k.nb_tab,
                        c.k.in_rec, c.k.omask, reinterpret_cast<const int*>(c.k.mv_rec), with_fix ? 1 : 0);
 }
+// can this configuration run the self-mapped pair kernels (k_ck_partial_self, k_weight<false, true>)?  Every pair evaluated, an unsharded map,
+// and tables that fit: PairHead's, and the overfull path's selection histogram and range buckets in the Ck launch's dynamic LDS
+bool pair_self_legal(const LaunchCtx& c) {
+    return !weight_culls(c) && !c.s.pyr_kstar && !c.s.pyr_kept && c.d.np <= PH_MAXNP && c.d.capp < 65536 &&
+           (sizeof(float4) + sizeof(int)) * (size_t)c.d.nbins * DSP_OBS_CAP >= sizeof(int) * (4096 + 2 * PS_NBK);
+}
+// every workgroup of the self-mapped kernels pays for the head whether it finds an item or not: one round of workgroups (7 / 8 per CU), not 4096
+static int pair_self_grid(const LaunchCtx& c, int per_cu) { const int g = (c.n_cu > 0 ? c.n_cu : 256) * per_cu; return g < c.d.np ? c.d.np : (g > 4096 ? 4096 : g); }
+void launch_ck_partial_self(const LaunchCtx& c) {   // instead of launch_pyr_prepare + launch_ck_partial; with overfull lists its first np workgroups sort, cut and re-slot
+    hipLaunchKernelGGL(k_ck_partial_self, dim3(pair_self_grid(c, 7)), dim3(CK_TPB), (sizeof(float4) + sizeof(int)) * (size_t)c.d.nbins * DSP_OBS_CAP, c.stream, c.d, c.s, c.fp,
+                       c.k.n_items, c.k.wu_items, c.k.in_rec, c.k.omask, reinterpret_cast<const int*>(c.k.mv_rec));
+}
 void launch_ck_finalize(const LaunchCtx& c) {  // after launch_weight_update: reduces the per-pyramid 1/Ck sums
     hipLaunchKernelGGL(k_ck_sum, dim3(1), dim3(512), 0, c.stream, c.d, c.s, c.fp);
 }
-int launch_weight_update(const LaunchCtx& c) {  // after launch_ck_partial (which also builds the item lists); returns the instantiation it launched
+int launch_weight_update(const LaunchCtx& c, bool self) {  // after launch_ck_partial (which also builds the item lists) / launch_ck_partial_self; returns the instantiation it launched
     const bool skip = weight_culls(c);
     const size_t lds = (sizeof(float4) + sizeof(float)) * (size_t)c.d.nbins * DSP_OBS_CAP;
-    if (skip) hipLaunchKernelGGL(k_weight<true>, dim3(4096), dim3(WU_TPB), lds, c.stream, c.d, c.s, c.fp, c.k.wu_items, c.k.n_items, c.k.nb_tab);
+    if (self) hipLaunchKernelGGL((k_weight<false, true>), dim3(pair_self_grid(c, 8)), dim3(WU_TPB), lds, c.stream, c.d, c.s, c.fp, c.k.wu_items, c.k.n_items, c.k.nb_tab);
+    else if (skip) hipLaunchKernelGGL(k_weight<true>, dim3(4096), dim3(WU_TPB), lds, c.stream, c.d, c.s, c.fp, c.k.wu_items, c.k.n_items, c.k.nb_tab);
     else hipLaunchKernelGGL(k_weight<false>, dim3(4096), dim3(WU_TPB), lds, c.stream, c.d, c.s, c.fp, c.k.wu_items, c.k.n_items, c.k.nb_tab);
     return skip ? 2 : 1;
 }

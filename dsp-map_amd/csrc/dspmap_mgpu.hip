@@ -258,6 +258,7 @@ extern "C" int dspmap_mgpu_weights_and_split(dspmap_t* m) {
     dspmap_snapshots_stale(m);
     LaunchCtx c = dspmap_ctx_of(m);
     m->last_weight_variant = launch_weight_update(c);
+    m->last_pair_path = 1;
     if (m->mgpu_side_pending) { HIPCHK(m, hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->mgpu_side_pending = false; }   // the side placement
     if (m->last_n_birth > 0) launch_birth_split_cksum(c, m->last_n_birth);   // split + the 1/Ck reduction in one launch
     else launch_ck_finalize(c);

@@ -212,7 +212,8 @@ struct DevState {
     FrameScalars* fs;
     FrameParams* fpar;
     int* hint_out;      // host-mapped words for the caller's thread: [0] FrameScalars::live_hint (which k_predict variant to launch),
-                        // [1] last frame's tiles with many moving particles (inline rollout or k_rollout)
+                        // [1] last frame's tiles with many moving particles (inline rollout or k_rollout), [2] / [3] see xq,
+                        // [4] set by a self-mapped Ck launch that found a pyramid list past its capacity (k_ck_partial_self)
     int* ring_seq;      // read position of the pinned parameter ring (frames replayed as a captured graph)
 #define XQ_NDEC 64       // DevState::xq: counters of the first birth kernel's workgroups that have decided, one per 256-byte block from XQ_DEC on
 #define XQ_DEC 64

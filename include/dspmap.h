@@ -219,6 +219,12 @@ enum dspmap_param {
     DSPMAP_P_FRONTIER_MERGE = 32,   /* dspmap_build_frontiers: 1 (default) = the frontier lanes of a wave that fall into one block are summed with
                                        ballots and popcounts and added to the block's record by one lane (five integer atomics per wave and block);
                                        0 = every frontier lane adds its own cell (five per cell).  For measurement: integer sums, the same result */
+    DSPMAP_P_PAIR_PREPARE = 33,     /* whole frames (dspmap_update_device, dspmap_update with the device estimator) of an unsharded map whose weight update evaluates
+                                       every pair (dspmap_debug_weight_variant 1) and that neither split their placement nor run as two branches: 0 (default) = the
+                                       pair kernels map their work items themselves and read the pyramid lists as they were registered -- no k_pyr_prepare launch --
+                                       until a frame finds a list past SAFE_PARTICLE_NUM_PYRAMID: that frame sorts and cuts inside its Ck launch, and the handle
+                                       prepares its lists from the next frames on, until dspmap_clear_state / dspmap_load_checkpoint; 1 = always k_pyr_prepare;
+                                       2 = self-mapped wherever legal, overfull lists or not (for tests).  Same result bit for bit; dspmap_debug_pair_path */
     DSPMAP_P_PAIR_CULL_SIGMAS = 13  /* mapUpdate evaluates a (particle, observation) pair only if their ranges differ by at most this many
                                        sigma_ob (default 9: the dropped terms are < 1e-19 and zero on the fixed-point Ck grid);
                                        a huge value evaluates every pair of the neighbourhood like the reference's loops */
@@ -1067,6 +1073,9 @@ int dspmap_debug_pair_items(dspmap_t* m, int out[3]);
  * 2 = only the observations within range of the item staged and far pairs branched over (maps whose corner is farther than 12 cull
  * radii), 0 = none yet.  Both add the same terms (DSPMAP_P_PAIR_CULL_SIGMAS) */
 int dspmap_debug_weight_variant(dspmap_t* m);
+/* how the last frame (or dspmap_stage_update) gave its pair kernels their work (DSPMAP_P_PAIR_PREPARE): 1 = k_pyr_prepare sorted and cut the
+ * pyramid lists and wrote the item lists, 2 = self-mapped pair kernels on the lists as registered, 0 = none yet */
+int dspmap_debug_pair_path(dspmap_t* m);
 /* diagnostics: the window plan k_rollout gets on this handle (a function of the configuration and the storage order alone; no device
  * needed): halo_out[t] = rows of the grid horizon t's LDS window reaches beyond its group of tiles, either side (-1 past the last
  * horizon), *lds_cells_out = 32-bit cells of all windows together (may be NULL).  All halos 0 = the collapsed plan of a grid too wide
