@@ -100,6 +100,9 @@ REACH_UNREACHED = 65535      # DSPMAP_REACH_UNREACHED
 REACH_WITH_CURRENT = 2       # DSPMAP_REACH_WITH_CURRENT
 REACH_DEVICE_SETS = 4        # DSPMAP_REACH_DEVICE_SETS
 REACH_TIMELINE_MAX_BYTES = 1 << 30   # DSPMAP_REACH_TIMELINE_MAX_BYTES
+# dspmap_path_info (dspmap_shorten_paths)
+PATH_INFO_DTYPE = np.dtype([("n_cells", "i4"), ("n_segments", "i4"), ("n_blocked", "i4"), ("truncated", "i4")])
+SHORTEN_MAX_WINDOW = 64      # DSPMAP_SHORTEN_MAX_WINDOW
 FORECAST_MAX_TIMES = 64      # DSPMAP_FORECAST_MAX_TIMES
 FORECAST_LERP = 2            # DSPMAP_FORECAST_LERP
 # dspmap_view / dspmap_view_score (dspmap_score_views) and the DSPMAP_VIEW_* statuses
@@ -181,6 +184,8 @@ SIGNATURES = {
     "dspmap_reach_timeline_paths": (_i, [_P, _i, _P, _i, _i, _P, _P]),
     "dspmap_reach_timeline_paths_device": (_i, [_P, _i, _P, _i, _i, _P, _P]),
     "dspmap_debug_set_cast_grid": (_i, [_P, _P]),
+    "dspmap_shorten_paths": (_i, [_P, _i, _i, _P, _P, _f, _f, _i, _i, _i, _P, _P, _P]),
+    "dspmap_shorten_paths_device": (_i, [_P, _i, _i, _P, _P, _f, _f, _i, _i, _i, _P, _P, _P]),
     "dspmap_build_forecast": (_i, [_P, _i, _P, _i]),
     "dspmap_forecast_device": (_P, [_P]),
     "dspmap_forecast_times": (_i, [_P, _P, _i]),
@@ -952,6 +957,50 @@ class DSPMap:
         self._chk(self.L.dspmap_reach_timeline_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags,
                                                      _ptr(steps) if len(q) else None, _ptr(cells) if max_len > 0 else None))
         return steps, cells
+
+    # -- shortened paths (extension; semantics in include/dspmap.h next to dspmap_shorten_paths)
+    def shorten_paths(self, steps, cells, t_start=-1.0, step_seconds=0.0, window=SHORTEN_MAX_WINDOW, max_seg=None):
+        """cut cell paths (steps [n] int32, cells [n, max_len] int32: what reach_paths and reach_timeline_paths return, or any polyline
+        of voxel indices ended by -1) down to line-of-sight waypoints in the cast grid: from each anchor the farthest of the next `window`
+        (1 .. 64) cells that cast_segments calls free, the next cell where none is.  With the t_start and step_seconds of the build the
+        paths came from, cell j gets the time of the step it is occupied at (t_start < 0: the current layer).  Returns (info, segments,
+        ends): info PATH_INFO_DTYPE [n] (n_cells, n_segments, n_blocked, truncated), segments float32 [n, max_seg, 8] -- the records
+        cast_segments and grow_boxes take, all zero behind n_segments -- and ends int32 [n, max_seg], the path position each segment ends
+        at (-1 behind n_segments).  max_seg=None: max_len - 1, which never truncates.  numpy in -> numpy out, synchronous; torch tensors
+        on the GPU -> tensors on the same device (info as int32 [n, 4]), enqueued on the handle's stream and ordered with torch's current
+        stream like cast_segments."""
+        if self._is_device_tensor(cells):
+            import torch
+            if cells.dtype != torch.int32 or cells.dim() != 2 or not self._is_device_tensor(steps) or steps.dtype != torch.int32 or \
+                    steps.device != cells.device or steps.numel() != cells.shape[0]:
+                raise ValueError("shorten_paths: int32 tensors steps [n] and cells [n, max_len] on one device")
+            c, s = cells.contiguous(), steps.contiguous().view(-1)
+            n, max_len = int(c.shape[0]), int(c.shape[1])
+            ms = max(max_len - 1, 0) if max_seg is None else int(max_seg)
+            info = torch.empty((n, 4), dtype=torch.int32, device=c.device)
+            seg = torch.empty((n, max(ms, 0), 8), dtype=torch.float32, device=c.device)
+            end = torch.empty((n, max(ms, 0)), dtype=torch.int32, device=c.device)
+            before, after = self._handle_stream_order(c.device)
+            before()
+            self._chk(self.L.dspmap_shorten_paths_device(self.h, n, max_len, s.data_ptr() if n else None, c.data_ptr() if n else None,
+                                                         float(t_start), float(step_seconds), int(window), ms, 0,
+                                                         info.data_ptr() if n else None, seg.data_ptr() if n and ms > 0 else None,
+                                                         end.data_ptr() if n and ms > 0 else None))
+            after()
+            return info, seg, end
+        c = np.ascontiguousarray(cells, np.int32)
+        s = np.ascontiguousarray(steps, np.int32).reshape(-1)
+        if c.ndim != 2 or len(s) != c.shape[0]:
+            raise ValueError("shorten_paths: steps [n] and cells [n, max_len]")
+        n, max_len = c.shape
+        ms = max(max_len - 1, 0) if max_seg is None else int(max_seg)
+        info = np.zeros(n, PATH_INFO_DTYPE)
+        seg = np.zeros((n, max(ms, 0), 8), np.float32)
+        end = np.zeros((n, max(ms, 0)), np.int32)
+        self._chk(self.L.dspmap_shorten_paths(self.h, n, max_len, _ptr(s) if n else None, _ptr(c) if n else None, float(t_start),
+                                              float(step_seconds), int(window), ms, 0, _ptr(info) if n else None,
+                                              _ptr(seg) if n and ms > 0 else None, _ptr(end) if n and ms > 0 else None))
+        return info, seg, end
 
     # -- occupancy forecast at caller-chosen times (extension; semantics in include/dspmap.h next to dspmap_build_forecast)
     def build_forecast(self, times):

@@ -241,6 +241,17 @@ void launch_reach(const LaunchCtx& c, const ReachArgs& a, const struct dspmap_re
 void launch_reach_timeline_paths(const LaunchCtx& c, const ReachTimelinePathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out,
                                  int* cells_out);
 void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out, int* cells_out);
+// cell paths shortened to line-of-sight waypoints, one wave per path (dspmap_shorten.hip; semantics in include/dspmap.h, dspmap_shorten_paths)
+struct ShortenArgs {
+    float cx, cy, cz;    // as QueryArgs: dspmap_voxel_center
+    int timed;           // t_start >= 0 and T > 0: cell j has the time of step max(steps - j, 0); otherwise every vertex has time -1
+    float t_start, step_seconds;
+    int max_len, window, max_seg;
+    const u64* bits;     // [L][nz][ny][W]
+};
+struct dspmap_path_info;
+void launch_shorten(const LaunchCtx& c, const ShortenArgs& a, int n, const int* steps, const int* cells, struct dspmap_path_info* info,
+                    struct dspmap_segment* seg, int* end);
 // occupancy forecast at caller-chosen times from the live particle set (dspmap_forecast.hip; semantics in include/dspmap.h, dspmap_build_forecast)
 #define FORECAST_MAX_TIMES 64   // == DSPMAP_FORECAST_MAX_TIMES
 struct ForecastArgs {

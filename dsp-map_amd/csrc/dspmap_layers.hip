@@ -1,5 +1,5 @@
 // dspmap_layers.hip -- host side of the planning layers that read the map: point and trajectory queries, distance fields, the cast grid with
-// segment casts and free boxes, arrival-time fields with timeline and paths, the forecast, the known-space layer, view scores and frontiers.
+// segment casts and free boxes, arrival-time fields with timeline and paths, shortened paths, the forecast, the known-space layer, view scores and frontiers.
 // Their kernels are in a file each (named per section); their state is LayerState (dspmap_internal.h), and what makes a snapshot stale is
 // decided in ONE place, dspmap_layers_stale next to it.  An entry point that takes host arrays is: check -> stage -> enqueue -> read back,
 // around the same *_enqueue its _device twin calls.  Checks fire in this order: arguments, slab and state, then the device.
@@ -631,6 +631,65 @@ extern "C" int dspmap_reach_timeline_paths_device(dspmap_t* m, int n, const dspm
                                                   int* cells_out) {
     return reach_paths_device(m, true, n, start, max_len, flags, steps_out, cells_out);
 }
+// --------------------------------------------------- shortened paths (dspmap_shorten.hip; semantics in include/dspmap.h)
+// needs the cast grid only: the paths may come from a reach snapshot, from a stale one or from the caller
+static int shorten_check(dspmap* m, int n, int max_len, const void* steps, const void* cells, float t_start, float step_seconds, int window,
+                         int max_seg, int flags, const void* info, const void* seg, const void* end) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: negative path count %d", n);
+    if (max_len < 1 || max_len > DSPMAP_REACH_MAX_STEPS + 1)
+        return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: max_len %d outside [1, %d]", max_len, DSPMAP_REACH_MAX_STEPS + 1);
+    if (window < 1 || window > DSPMAP_SHORTEN_MAX_WINDOW)
+        return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: window %d outside [1, %d]", window, DSPMAP_SHORTEN_MAX_WINDOW);
+    if (max_seg < 0) return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: negative max_seg %d", max_seg);
+    if (flags != 0) return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: unknown flags 0x%x", flags);
+    if (t_start != t_start) return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: t_start is NaN");
+    if (!(step_seconds >= 0.f && step_seconds < INFINITY))
+        return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: step_seconds %g is NaN, negative or infinite", (double)step_seconds);
+    if (n > 0 && (!steps || !cells || !info)) return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: NULL steps, cells or info array");
+    if (n > 0 && max_seg > 0 && (!seg || !end)) return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: NULL seg_out or end_out array with max_seg %d", max_seg);
+    if ((unsigned long long)n * (unsigned long long)max_len > 0x80000000ull)
+        return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: %d paths of %d cells exceed 2^31 cells", n, max_len);
+    if ((unsigned long long)n * (unsigned long long)max_seg > 0x80000000ull)
+        return dspmap_fail(m, DSPMAP_E_ARG, "shorten paths: %d paths of %d segments exceed 2^31 segments", n, max_seg);
+    const int rc = whole_map_check(m, "shorten paths", "casts cross slabs");
+    if (rc != DSPMAP_OK) return rc;
+    return cast_grid_ready(m, "dspmap_shorten_paths");
+}
+static int shorten_enqueue(dspmap* m, int n, int max_len, const int* steps, const int* cells, float t_start, float step_seconds, int window, int max_seg,
+                           dspmap_path_info* info, dspmap_segment* seg, int* end) {
+    const MapDims& d = m->d;
+    ShortenArgs a;
+    a.cx = -d.half_x + d.res * 0.5f; a.cy = -d.half_y + d.res * 0.5f; a.cz = -d.half_z + d.res * 0.5f;   // dspmap_voxel_center
+    a.timed = (!(t_start < 0.f) && d.T > 0) ? 1 : 0;
+    a.t_start = t_start; a.step_seconds = step_seconds;
+    a.max_len = max_len; a.window = window; a.max_seg = max_seg;
+    a.bits = m->ly.cg_bits;
+    launch_shorten(dspmap_ctx_of(m), a, n, steps, cells, info, seg, end);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_shorten_paths(dspmap_t* m, int n, int max_len, const int* steps, const int* cells, float t_start, float step_seconds, int window,
+                                    int max_seg, int flags, dspmap_path_info* info_out, dspmap_segment* seg_out, int* end_out) {
+    int rc = shorten_check(m, n, max_len, steps, cells, t_start, step_seconds, window, max_seg, flags, info_out, seg_out, end_out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    const size_t ns = (size_t)n * max_seg;   // (max_seg == 0: no segment sections, the kernel gets NULL)
+    StageSec s[5] = {{steps, nullptr, sizeof(int) * (size_t)n}, {cells, nullptr, sizeof(int) * (size_t)n * max_len},
+                     {nullptr, info_out, sizeof(dspmap_path_info) * (size_t)n}, {nullptr, seg_out, sizeof(dspmap_segment) * ns},
+                     {nullptr, end_out, sizeof(int) * ns}};
+    if ((rc = stage_begin(m, s, 5)) != DSPMAP_OK) return rc;
+    if ((rc = shorten_enqueue(m, n, max_len, (const int*)s[0].dev, (const int*)s[1].dev, t_start, step_seconds, window, max_seg,
+                              (dspmap_path_info*)s[2].dev, (dspmap_segment*)s[3].dev, (int*)s[4].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 5);
+}
+extern "C" int dspmap_shorten_paths_device(dspmap_t* m, int n, int max_len, const int* steps, const int* cells, float t_start, float step_seconds,
+                                           int window, int max_seg, int flags, dspmap_path_info* info_out, dspmap_segment* seg_out, int* end_out) {
+    const int rc = shorten_check(m, n, max_len, steps, cells, t_start, step_seconds, window, max_seg, flags, info_out, seg_out, end_out);
+    if (rc != DSPMAP_OK) return rc;
+    return shorten_enqueue(m, n, max_len, steps, cells, t_start, step_seconds, window, max_seg, info_out, seg_out, end_out);
+}
+
 extern "C" int dspmap_debug_reach_storage(dspmap_t* m, long long out[2]) {
     if (!m) return DSPMAP_E_ARG;
     if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "reach storage: NULL output array");

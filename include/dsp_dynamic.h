@@ -313,6 +313,16 @@ public:
     int reachTimelinePaths(int n, const dspmap_reach_point* starts, int max_len, int* steps, int* cells, bool world = false) {
         return dspmap_reach_timeline_paths(h_, n, starts, max_len, world ? DSPMAP_QUERY_WORLD : 0, steps, cells);
     }
+    /* extension: paths cut down to line-of-sight waypoints (dspmap_shorten_paths in dspmap.h): steps and cells as reachPaths and
+     * reachTimelinePaths write them (or any polyline of voxel indices ended by -1); from each anchor the farthest of the next `window`
+     * cells that castSegments calls free.  With the build's t_start and step_seconds every cell keeps the time of its step.  info[i] =
+     * {n_cells, n_segments, n_blocked, truncated}, segs[i * max_seg + s] = records castSegments and growBoxes take, ends[i * max_seg + s] =
+     * the path position segment s ends at.  Needs a grid built by buildCastGrid() since the last update(); read-only.  Return DSPMAP_OK or
+     * a negative error code. */
+    int shortenPaths(int n, int max_len, const int* steps, const int* cells, float t_start, float step_seconds, int window, int max_seg,
+                     dspmap_path_info* info, dspmap_segment* segs, int* ends) {
+        return dspmap_shorten_paths(h_, n, max_len, steps, cells, t_start, step_seconds, window, max_seg, 0, info, segs, ends);
+    }
     /* extension: occupancy forecast at times of the caller's choosing (dspmap_build_forecast in dspmap.h): layer j = the mass of every live
      * particle, newborns included, rolled out to times[j] seconds after the last update() -- strictly ascending, at most
      * DSPMAP_FORECAST_MAX_TIMES.  Read-only towards the map; a snapshot that goes stale with the next update().  getForecast copies one

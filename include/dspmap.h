@@ -605,7 +605,9 @@ int dspmap_debug_reach_storage(dspmap_t* m, long long out[2]);
  *    DSPMAP_E_STATE; without a device a valid build is DSPMAP_E_DEVICE.  READ-ONLY towards the map and the grid like the rest of the family.
  *    The buffers are allocated by the first timeline build, grown by a larger one after the stream has drained, and freed with the device
  *    state; a handle that never builds one allocates nothing.
- *  - not offered: arriving at a chosen step instead of the first one, more than one workgroup per field, compressing waits out of a path. */
+ *  - not offered: arriving at a chosen step instead of the first one, more than one workgroup per field.  (dspmap_shorten_paths below
+ *    turns a path into the few straight pieces a planner takes, waits included; it offers neither any-angle optimality nor arrival at a
+ *    chosen step.) */
 #define DSPMAP_REACH_TIMELINE_MAX_BYTES (1ull << 30)
 /* grow the fields AND keep every step's set; synchronous */
 int dspmap_build_reach_timeline(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src_host, float t_start, float step_seconds,
@@ -628,6 +630,62 @@ int dspmap_reach_timeline_paths_device(dspmap_t* m, int n, const dspmap_reach_po
 /* test hook: replace all L layers ([L][nz][ny][W] words) of the VALID cast grid.  A NULL pointer or a set bit at x >= nx is DSPMAP_E_ARG, no
  * valid grid DSPMAP_E_STATE.  The grid stays valid; arrival fields built before the call are stale.  Synchronous. */
 int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long* words_host);
+
+/* ---- shortened paths: a cell path cut down to line-of-sight waypoints (no counterpart in the reference).  A path from the wavefront is a
+ * 6-connected staircase with one voxel per step; what a corridor generator or a trajectory optimiser takes is the few straight pieces
+ * behind it.  dspmap_shorten_paths* returns, per path, a greedy farthest-visible subsequence of its cells as dspmap_segment records --
+ * what dspmap_cast_segments* and dspmap_grow_boxes* take unchanged -- where the map lives, instead of a copy of the paths and the grid to the
+ * host, a DDA per candidate shortcut there and an upload of the result.
+ *
+ *  - path i: n paths in the layout dspmap_reach_paths* and dspmap_reach_timeline_paths* produce (steps[n], cells[n * max_len]), or any
+ *    caller-made polyline of cells.  v = steps[i]; v < 0: the path has no cells.  Otherwise its cells are the leading entries c_0 ..
+ *    c_{m-1} of cells[i * max_len ..] that lie in [0, V): the first -1, the first out-of-range index or max_len ends the path, and
+ *    m = n_cells.  Consecutive cells need not be neighbours, and equal consecutive cells (waits) are legal.
+ *  - vertex: the vertex of cell c is its voxel centre, dspmap_voxel_center's expression per axis, fl(fl((float)i * res) + (-half + res / 2))
+ *    (the one the query section spells out).
+ *  - time: if t_start < 0 or T == 0 every vertex has the time -1.0f, so casts and boxes test layer 0.  Otherwise cell j is occupied at
+ *    step e_j = max(v - j, 0) and its time is tau_j = fl(t_start + fl((float)e_j * step_seconds)), the schedule expression of
+ *    dspmap_build_reach_fields: with the build's t_start and step_seconds a timeline path's cells get the times they were reached at.
+ *  - cast: C(p, k) is the result dspmap_cast_segments steps 2 - 4 give for {centre(c_p), tau_p, centre(c_k), tau_k} without
+ *    DSPMAP_QUERY_WORLD in the valid cast grid, inflated as that grid is -- the same instructions, not a restatement.  A wait (c_p == c_k)
+ *    is a zero-length cast: it tests the layers between the two times in that one cell and nothing else.
+ *  - greedy rule: start with p = 0, s = 0.  While p < m - 1: if s == max_seg, truncated = 1 and the path stops.  The candidates are
+ *    k = p + 1 .. min(p + window, m - 1); q is the LARGEST candidate with C(p, k).status == DSPMAP_CAST_FREE.  If there is none, q = p + 1
+ *    and n_blocked += 1: this can happen when the layer changes between two adjacent steps (or with a caller-made path through occupied
+ *    cells); it is reported, not hidden.  seg_out[i * max_seg + s] = {centre(c_p), tau_p, centre(c_q), tau_q}, end_out[i * max_seg + s] = q;
+ *    then p = q, s += 1.  At the end n_segments = s.
+ *  - unused entries: every entry behind n_segments is written -- the segment all-zero bits, end -1 -- and so is every entry of a path with
+ *    m <= 1.
+ *  - consequences: the emitted vertices are a subsequence of the path, from c_0 to c_{m-1} unless truncated.  Every segment not counted
+ *    in n_blocked is DSPMAP_CAST_FREE under dspmap_cast_segments bit for bit.  On a path whose consecutive cells are equal or face
+ *    neighbours a segment from step e to step e' is at most |e - e'| voxels long in the sum over the axes, so the mean speed never
+ *    exceeds the wavefront's one voxel per step.  On a time-invariant build the result does not depend on step_seconds.  (All of this
+ *    presumes dspmap_point_voxel_index(centre(i)) == i for every voxel, which holds for the usual resolutions and is cheap to check.)
+ *  - arguments, checked before the device is touched, DSPMAP_E_ARG with a text, in this order: a NULL handle, n < 0, max_len outside
+ *    1 .. DSPMAP_REACH_MAX_STEPS + 1, window outside 1 .. DSPMAP_SHORTEN_MAX_WINDOW, max_seg < 0, flags != 0, a NaN t_start, a step_seconds
+ *    that is NaN, negative or infinite, a NULL steps, cells or info array with n > 0, a NULL seg_out or end_out with n > 0 and max_seg > 0,
+ *    n * max_len or n * max_seg > 2^31.
+ *  - state, in dspmap_grow_boxes' order: a sharded handle (slab) is DSPMAP_E_STATE; a stale or never-built grid is DSPMAP_E_STATE with a
+ *    text naming dspmap_build_cast_grid; a device call that fails is DSPMAP_E_DEVICE.
+ *  - independence: the call needs the cast grid only, not a reach snapshot -- the paths may come from anywhere, also from a snapshot that
+ *    has gone stale since.  READ-ONLY towards the map and the grid like dspmap_grow_boxes; it makes nothing stale and allocates nothing
+ *    but the staging of the host variant.  Enqueued on the handle's stream behind the grid's build, the frame and the paths.
+ *  - not offered: any-angle optimality (the vertices stay cell centres of the path, and the rule is greedy), arrival at a chosen step. */
+#define DSPMAP_SHORTEN_MAX_WINDOW 64
+typedef struct dspmap_path_info {
+    int n_cells;      /* m: the cells the path was read with */
+    int n_segments;   /* segments written, <= max_seg */
+    int n_blocked;    /* of them: rounds in which no candidate was visible and the next cell was taken */
+    int truncated;    /* 1: max_seg segments did not reach the last cell */
+} dspmap_path_info; /* 16 bytes */
+/* info_out_host[n], seg_out_host[n * max_seg], end_out_host[n * max_seg] (the last two may be NULL when max_seg == 0); synchronous */
+int dspmap_shorten_paths(dspmap_t* m, int n, int max_len, const int* steps_host, const int* cells_host, float t_start, float step_seconds,
+                         int window, int max_seg, int flags /* must be 0 */, dspmap_path_info* info_out_host, dspmap_segment* seg_out_host,
+                         int* end_out_host);
+/* the same on device arrays; enqueued on the handle's stream, no synchronisation */
+int dspmap_shorten_paths_device(dspmap_t* m, int n, int max_len, const int* steps_dev, const int* cells_dev, float t_start, float step_seconds,
+                                int window, int max_seg, int flags /* must be 0 */, dspmap_path_info* info_out_dev, dspmap_segment* seg_out_dev,
+                                int* end_out_dev);
 
 /* ---- occupancy forecast at caller-chosen times from the live particle set (no counterpart in the reference, whose horizons are the
  * PREDICTION_TIMES it was compiled with; everything above snaps a time t to the next configured horizon k(t), and the future status is a
