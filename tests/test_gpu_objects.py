@@ -149,6 +149,45 @@ def test_objects_match_the_restatement(dsp, shape, handle):
     m.close()
 
 
+PADDED = (18, 14, 6)      # 4 x 4 x 4 cubes padded on all three axes
+
+
+def _moving_stored(dsp, shape, tiling):
+    """_moving under a chosen storage order (DSPMAP_P_TILING: 1 = 4 x 4 x 4 cubes, 0 = runs in index order), read back after the first use"""
+    m = _map(dsp, shape, seed=99)
+    m.set_param(dsp.capi.P_TILING, tiling)
+    m.set_tables(*common.tables(5))
+    m.seed_uniform(2, 0.01, 17, vmax=0.8)
+    m.occupancy_resample()
+    assert int(m.get_param(dsp.capi.P_TILING)) == tiling
+    return _with_grid(m, shape)
+
+
+@pytest.mark.parametrize("shape", [WIDE, PADDED], ids=["66x12x8", "18x14x6"])
+def test_objects_under_cube_storage(dsp, shape):
+    """k_objects_accumulate reads mass and momentum through lv_of_true: records, label grid and counts under cube storage equal the
+    restatement fed with that handle's results(), and the records equal, byte for byte, those of a twin in index order"""
+    (cubes, lay), (runs, lay_r) = _moving_stored(dsp, shape, 1), _moving_stored(dsp, shape, 0)
+    res = cubes.results()
+    assert np.array_equal(res, runs.results()) and np.array_equal(lay, lay_r)
+    assert np.array_equal(CR_unpack(cubes.cast_grid(), shape[0]), lay)
+    _non_degenerate(shape, lay, res, True)
+    V = shape[0] * shape[1] * shape[2]
+    for t, layer in TIMES.items():
+        for conn in (6, 26):
+            for min_cells in (1, 4):
+                got = []
+                for m in (cubes, runs):
+                    m.build_objects(t=t, connectivity=conn, min_cells=min_cells, max_objects=V)
+                    got.append(_read(m))
+                want = _want(shape, layer, lay[layer], res, conn, min_cells)
+                assert len(want[0]) > 0 and (want[0]["mass_q"] > 0).any() and (want[0]["mom_q"] != 0).any()   # records that carry mass and momentum
+                _same(got[0], want, (shape, "cubes", t, conn, min_cells))
+                assert got[0][0].tobytes() == got[1][0].tobytes() and got[0][1].tobytes() == got[1][1].tobytes() and got[0][2] == got[1][2]
+    assert int(cubes.get_param(dsp.capi.P_TILING)) == 1 and int(runs.get_param(dsp.capi.P_TILING)) == 0
+    cubes.close(), runs.close()
+
+
 @pytest.mark.parametrize("shape", [WIDE, BIG], ids=["66x12x8", "130x40x24"])
 def test_max_objects_cuts_the_list_not_the_counts_or_the_grid(dsp, shape):
     m, lay = _moving(dsp, shape)

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from tests import common
+from tests import readout_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -452,6 +453,9 @@ def test_single_frame_from_same_state(dsp, orc):
     xo, fo = o.get_occupancy_with_future(0.2)
     inter = len(set(map(tuple, np.round(xg, 3))) & set(map(tuple, np.round(xo, 3))))
     assert inter >= 0.98 * max(len(xo), 1)
+    # the exact statement: the list is the restatement's over the masses this handle hands out -- count, order and bits
+    n_ref, x_ref = readout_ref.occupied_list(m.cfg, res_g[:, 0], 0.2)
+    assert n_ref > 0 and ng == len(xg) == n_ref and xg.tobytes() == x_ref.tobytes()
     assert np.allclose(fg.sum(0), fo.sum(0), rtol=5e-3)
     assert o.cursors()[0] == m.cursors()[0]
     o.close(); m.close()

@@ -1,6 +1,7 @@
 """GPU tests of the point / trajectory queries (dspmap_query_occupancy*, dspmap_trajectory_risk*): bit parity of the host and device
 entry points with the numpy restatement (tests/query_ref.py) over what the map hands out, read-only behaviour, the per-trajectory
-risk, slab handles merged with max, and stream order behind the frame."""
+risk (also past one 32-sample chunk and one 256-trajectory block of k_risk_reduce, at radius 0, with an infinite outside value, at a
+threshold that occurs, and across regrowth of the handle's scratch), slab handles merged with max, and stream order behind the frame."""
 import ctypes as C
 import importlib
 
@@ -194,6 +195,214 @@ def test_trajectory_risk(dsp):
     assert s.tobytes() == got[0]["sum"].tobytes()
     assert np.array_equal(mx, got[0]["max"]) and np.array_equal(first, got[0]["first_over"]) and np.array_equal(nout, got[0]["n_outside"])
     assert 50 < (nout > 0).sum() < K and (first >= 0).sum() > 50
+    m.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# k_risk_reduce past one chunk of RISK_CHUNK = 32 samples and one block of 256 trajectories, and k_query<false, true> (radius 0 with flags).
+# One map (40 x 40 x 24, 12 particles per voxel, seeded with moving particles, eight frames of the corridor scene) and one pool of
+# RISK_POOL samples whose values the restatement computes ONCE per radius; every case's trajectories are rows of pool indices, so its
+# reference is a gather.  The first rows are designed from the restatement's values (LOW: inside, value <= threshold at radius 0.3 and
+# so at radius 0; HIGH: inside, own voxel > threshold, so over at both radii; OUT: flagged) so that first_over falls where k_risk_reduce
+# can go wrong: at the last sample, never, in chunk 0, at 31 | 32 | 33, at 63 | 64 | 65 and beyond, and n_outside is 0 and n_samples.
+RISK_KW = dict(nx=40, ny=40, nz=24, res=0.15, ppv=12)
+RISK_POOL = 600 * 100
+RISK_OUTSIDE = 0.75
+RISK_RADII = [0.0, 0.3]
+RISK_S, RISK_K = [1, 31, 32, 33, 64, 65, 100], [1, 255, 256, 257, 600]
+RISK_SHAPES = sorted(set([(k, s) for s in RISK_S for k in (257, 1)] + [(k, s) for k in RISK_K for s in (33, 100)]))
+# row -> the designed first_over (S - 1: the last sample; None: all LOW; "out": all OUT); a design applies where its row and sample exist
+RISK_DESIGN = ["last", None, "out", 32, 0, 31, 33, 64, 65, 63, 70, 5]
+
+
+def _risk_map(dsp, frames):
+    m = dsp.DSPMap(dsp.make_config(seed=99, **RISK_KW))
+    m.set_tables(*common.tables(5))
+    m.seed_uniform(2, 0.01, 17, vmax=0.8)
+    return m, _run(m, frames)
+
+
+def _future_in_place(dsp, m):
+    """the [V, T] future status without the readout's side effect (dspmap_future_device: no clear is armed)"""
+    ptr = m.L.dspmap_future_device(m.h)
+    assert ptr
+    fut = torch.as_tensor(dsp.capi._DeviceSpan(ptr, (m.V, m.T), "<f4"), device="cuda")
+    m.sync()
+    return fut.cpu().numpy()
+
+
+class _Risk:
+    pass
+
+
+@pytest.fixture(scope="module")
+def risk(dsp):
+    """the handle, what it hands out, the pool and the restatement's values of the pool at both radii"""
+    r = _Risk()
+    r.frames = _scene_frames(dsp, RISK_KW, 8, seed=77)
+    r.m, r.cur = _risk_map(dsp, r.frames)
+    twin, _ = _risk_map(dsp, r.frames)
+    m, cfg = r.m, r.m.cfg
+    r.res, r.fut = m.results(), _future_in_place(dsp, m)
+    assert np.array_equal(r.res, twin.results()) and np.array_equal(r.fut, twin.getFutureStatus())   # the in-place view IS what the readout gives
+    twin.close()
+    mass = r.res[:, 0]
+    assert (mass > 0.2).any() and len(np.unique(mass)) > 50 and (r.fut[:, 0] != r.fut[:, -1]).sum() > 100   # masses and horizons non-trivial
+    r.pool = _samples(cfg, RISK_POOL, 4)
+    r.vals, r.flags = {}, None
+    for rad in RISK_RADII:
+        v, f = Q.query(cfg, r.res, r.fut, r.pool, radius=rad, cur_pos=r.cur, outside=RISK_OUTSIDE)
+        assert r.flags is None or np.array_equal(f, r.flags)
+        r.vals[rad], r.flags = v, f
+    v0, v3, inside = r.vals[0.0], r.vals[0.3], ~r.flags
+    assert (v3[inside] >= v0[inside]).all()
+    r.thr = float(np.quantile(v3[inside], 0.5))                          # half of the inside samples are LOW at radius 0.3: non-empty by construction
+    assert r.thr < RISK_OUTSIDE                                          # a flagged sample is over the threshold
+    r.low = np.flatnonzero(inside & (v3 <= F(r.thr)))
+    r.high = np.flatnonzero(inside & (v0 > F(r.thr)))
+    r.out = np.flatnonzero(r.flags)
+    assert len(r.low) > 1000 and len(r.high) >= 20 and len(r.out) > 1000
+    yield r
+    r.m.close()
+
+
+def _risk_rows(r, K, S, seed=0):
+    """[K, S] pool indices: consecutive pool samples, the first rows overwritten by the designs that fit"""
+    rng = np.random.default_rng(1000 * K + S + seed)
+    src = np.arange(K * S).reshape(K, S)
+    designed = {}
+    for row, what in enumerate(RISK_DESIGN[:K]):
+        f = S - 1 if what == "last" else what
+        if what == "out":
+            src[row] = rng.choice(r.out, S)
+        elif f is None:
+            src[row] = rng.choice(r.low, S)
+        elif f < S:
+            src[row, :f] = rng.choice(r.low, f)
+            src[row, f] = rng.choice(r.high)
+        else:
+            continue
+        designed[row] = what
+    return src, designed
+
+
+def _risk_want(r, src, radius, threshold):
+    S = src.shape[1]
+    return Q.risk(r.vals[radius][src.ravel()], r.flags[src.ravel()], S, threshold=threshold)
+
+
+def _risk_covered(K, S, designed, first, nout):
+    """the coverage conditions, on the restatement's output"""
+    for row, what in designed.items():
+        if what == "out":
+            assert nout[row] == S and first[row] == 0, (row, what)
+        elif what is None:
+            assert nout[row] == 0 and first[row] == -1, (row, what)
+        else:
+            assert first[row] == (S - 1 if what == "last" else what), (row, what, first[row])
+    if K >= len(RISK_DESIGN):
+        assert (first == -1).any() and ((first >= 0) & (first <= 31)).any() and (nout == S).any() and (nout == 0).any()
+        if S > 32:
+            assert (first == 32).any()
+        if S > 33:
+            assert (first > 32).any()
+        if S > 65:
+            assert (first > 64).any()
+
+
+def _risk_both(m, traj, **kw):
+    """host and device entry points: identical bytes; returns the host's records"""
+    host = m.trajectory_risk(traj, **kw)
+    td = torch.from_numpy(traj).cuda()
+    torch.cuda.synchronize()
+    dev = m.trajectory_risk(td, **kw)
+    m.sync()
+    for k in ("sum", "max", "first_over", "n_outside"):
+        assert dev[k].cpu().numpy().tobytes() == np.ascontiguousarray(host[k]).tobytes(), k
+    return host
+
+
+def _risk_same(got, want, tag):
+    s, mx, first, nout = want
+    assert got["sum"].tobytes() == s.tobytes(), (tag, "sum", np.flatnonzero(got["sum"].view(np.uint32) != s.view(np.uint32))[:5])
+    assert np.array_equal(mx, got["max"]), (tag, "max", np.flatnonzero(mx != got["max"])[:5])
+    assert np.array_equal(first, got["first_over"]), (tag, "first_over", np.flatnonzero(first != got["first_over"])[:5])
+    assert np.array_equal(nout, got["n_outside"]), (tag, "n_outside", np.flatnonzero(nout != got["n_outside"])[:5])
+
+
+@pytest.mark.parametrize("radius", RISK_RADII)
+@pytest.mark.parametrize("K,S", RISK_SHAPES, ids=["%dx%d" % ks for ks in RISK_SHAPES])
+def test_trajectory_risk_chunks_and_blocks(dsp, risk, K, S, radius):
+    r = risk
+    src, designed = _risk_rows(r, K, S)
+    want = _risk_want(r, src, radius, r.thr)
+    _risk_covered(K, S, designed, want[2], want[3])
+    traj = np.ascontiguousarray(r.pool[src])
+    got = _risk_both(r.m, traj, radius=radius, outside=RISK_OUTSIDE, threshold=r.thr)
+    _risk_same(got, want, (K, S, radius))
+    assert np.array_equal(r.m.results(), r.res) and np.array_equal(_future_in_place(dsp, r.m), r.fut)   # what the reference was computed from
+
+
+@pytest.mark.parametrize("radius", RISK_RADII)
+def test_trajectory_risk_threshold_is_strict(dsp, risk, radius):
+    """a threshold equal to a value that occurs: that sample is not over"""
+    r = risk
+    K, S = 257, 33
+    src, _ = _risk_rows(r, K, S)
+    v = r.vals[radius][src.ravel()].reshape(K, S)
+    vals, counts = np.unique(v[(v > 0) & (v < F(RISK_OUTSIDE))], return_counts=True)
+    thr = float(vals[counts.argmax()])                                   # the most frequent positive value of these trajectories
+    want = _risk_want(r, src, radius, thr)
+    ge = v >= F(thr)
+    first_ge = np.where(ge.any(1), ge.argmax(1), -1)
+    assert (first_ge != want[2]).sum() >= 5                              # trajectories that a >= in place of > would answer differently
+    got = _risk_both(r.m, np.ascontiguousarray(r.pool[src]), radius=radius, outside=RISK_OUTSIDE, threshold=thr)
+    _risk_same(got, want, ("strict", radius))
+
+
+@pytest.mark.parametrize("radius", RISK_RADII)
+def test_trajectory_risk_outside_infinite(dsp, risk, radius):
+    """outside = +inf: sum and max are inf where a sample lies outside; first_over is the first such sample unless one is over earlier"""
+    r = risk
+    K, S = 257, 33
+    src, _ = _risk_rows(r, K, S)
+    traj = np.ascontiguousarray(r.pool[src])
+    vals, flags = Q.query(r.m.cfg, r.res, r.fut, traj.reshape(-1, 4), radius=radius, cur_pos=r.cur, outside=np.inf)
+    want = Q.risk(vals, flags, S, threshold=r.thr)
+    s, mx, first, nout = want
+    fl = flags.reshape(K, S)
+    has = fl.any(1)
+    assert has.sum() > 20 and (~has).sum() >= 1
+    assert np.isinf(s[has]).all() and np.isinf(mx[has]).all() and (s[has] > 0).all()
+    if radius == 0.0:
+        assert np.isfinite(s[~has]).all()                                # (with a radius, a lattice point outside the map reads inf too)
+    first_out = fl.argmax(1)
+    assert (first[has] <= first_out[has]).all() and (first[has] == first_out[has]).any() and (first[has] < first_out[has]).any()
+    got = _risk_both(r.m, traj, radius=radius, outside=float("inf"), threshold=r.thr)
+    _risk_same(got, want, ("inf", radius))
+
+
+def test_trajectory_risk_scratch_regrows(dsp, risk):
+    """a fresh handle: a small K x S, a large one, the small one again through the device entry point (which regrows the handle's scratch),
+    then the same through the host entry point"""
+    r = risk
+    m, _ = _risk_map(dsp, r.frames)
+    assert np.array_equal(m.results(), r.res) and np.array_equal(_future_in_place(dsp, m), r.fut)   # the fixture's state: its values hold here
+    shapes = [(3, 5), (600, 100), (3, 5), (257, 65), (1, 1)]
+    for device in (True, False):
+        for K, S in shapes:
+            src, _ = _risk_rows(r, K, S, seed=7)
+            traj = np.ascontiguousarray(r.pool[src])
+            want = _risk_want(r, src, 0.3, r.thr)
+            if device:
+                td = torch.from_numpy(traj).cuda()
+                torch.cuda.synchronize()
+                d = m.trajectory_risk(td, radius=0.3, outside=RISK_OUTSIDE, threshold=r.thr)
+                m.sync()
+                got = {k: d[k].cpu().numpy() for k in d}
+            else:
+                got = m.trajectory_risk(traj, radius=0.3, outside=RISK_OUTSIDE, threshold=r.thr)
+            _risk_same(got, want, ("regrow", device, K, S))
     m.close()
 
 
