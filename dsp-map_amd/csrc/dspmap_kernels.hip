@@ -811,7 +811,7 @@ __device__ __forceinline__ void ck_item_pairs(const MapDims& d, const DevState& 
     __shared__ float4 s_p[CK_PCH];
     __shared__ int s_bin[DSP_MAX_NBINS];
     __shared__ int s_off[DSP_MAX_NBINS + 1];
-    __shared__ float s_rng[2];
+    __shared__ float s_rng[3];   // the range interval of the observations that matter; [2] != 0: every pair is tested on its own
     __shared__ int s_n;
     const int tid = threadIdx.x;
     if (!SELF) neighbor_load(d, nb_tab, b, s_bin, s_off);
@@ -827,12 +827,18 @@ __device__ __forceinline__ void ck_item_pairs(const MapDims& d, const DevState& 
         // s >= (1000 R / sigma - sqrt(3))^2 for the truncated table indices (u in (1000 z - 1, 1000 z]).  With the chunk's
         // largest weight: s > (log2(c3 w) + 35) / K  <=>  R > sigma * (sqrt(.) / 1000 + 0.0018); 0.01 sigma of margin covers
         // the roundings of the two ranges.  Never wider than the handle's cull radius (which also bounds the +-9.9 clamp).
+        // A cull radius INSIDE that radius (DSPMAP_P_PAIR_CULL_SIGMAS below about 6) drops terms that are not zero: then the interval
+        // only pre-selects, and every pair is tested on its own below (s_rng[2]), as k_weight tests it -- what is added must not depend on
+        // which particles share a chunk (the lists are built with atomics: their order changes from run to run).
         float wm = tid < npart ? r.w : 0.f;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) wm = fmaxf(wm, __shfl_xor(wm, o, WAVE));
         const float need = (__log2f(pdf_c3 * wm) + 35.f) * (1.f / 7.213475204444817e-07f);
-        const float rad = fminf(cull_r, sigma_ob * (sqrtf(fmaxf(need, 0.f)) * 0.001f + 0.01f));
-        if (tid == 0) { s_rng[0] = lo - rad; s_rng[1] = hi + rad; s_n = 0; }
+        const float zero_r = sigma_ob * (sqrtf(fmaxf(need, 0.f)) * 0.001f + 0.01f);
+        const bool pp = cull_r < zero_r;
+        // (pp: the interval is a little wider than the pair test, so that the roundings of lo - rad and of |z.w - len| cannot disagree)
+        const float rad = pp ? cull_r * 1.0001f + 1e-6f : zero_r;
+        if (tid == 0) { s_rng[0] = lo - rad; s_rng[1] = hi + rad; s_rng[2] = pp ? 1.f : 0.f; s_n = 0; }
         s_p[tid] = r;
     }
     __syncthreads();
@@ -871,6 +877,7 @@ __device__ __forceinline__ void ck_item_pairs(const MapDims& d, const DevState& 
     const int opad = O <= 64 ? 64 : (O <= 128 ? 128 : 256);
     const int G = CK_TPB / opad;
     const int g = tid / opad;
+    const bool per_pair = s_rng[2] != 0.f;
     for (int o = tid % opad; o < O; o += opad) {
         const int oi = s_oi[o];
         const float4 z = s_z[o];
@@ -878,6 +885,13 @@ __device__ __forceinline__ void ck_item_pairs(const MapDims& d, const DevState& 
         // total does not depend on the order of the particles in the pyramid's list either (built with atomics)
         double acc = 0.0;
         int i = g;
+        if (per_pair) {   // the handle's cull radius cuts terms that are not zero: the per-pair rule of k_weight (ranges within cull_r)
+            for (; i < npart; i += G) {
+                const float4 p = s_p[i];
+                if (fabsf(z.w - sqrtf(p.x * p.x + p.y * p.y + p.z * p.z)) > cull_r) continue;   // (the particle's range, as k_weight forms it)
+                acc = __dadd_rn(acc, ck_snap(p.w * pair_gk(p.x, p.y, p.z, z.x, z.y, z.z, sigma_ob, inv_sigma_ob, pdf_c3)));
+            }
+        }
         for (; i + G < npart; i += 2 * G) {   // two particles per iteration: packed fp32
             const float4 p = s_p[i], p2 = s_p[i + G];
             const f2v gk = pair_gk2(f2v{p.x, p2.x}, f2v{p.y, p2.y}, f2v{p.z, p2.z}, f2v{z.x, z.x}, f2v{z.y, z.y}, f2v{z.z, z.z},

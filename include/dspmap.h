@@ -1174,7 +1174,10 @@ int dspmap_export_state(dspmap_t* m, int cap, int* voxel_out_host, int* slot_out
  * slot, the function statics of update() and of the birth stage, the table cursors, the result grid and the future
  * accumulators; the random tables come from the configuration's seed (or are re-injected by the caller).  Loading
  * requires a handle created with the same configuration.  The host velocity estimator's previous clusters are not
- * saved: the first frame after a restore matches no cluster, like the first frame of a run. */
+ * saved: the first frame after a restore matches no cluster, like the first frame of a run.  Nor is the cloud of the
+ * last view that had points: a frame with an empty view re-uses it for its births (:1379-1381), so a restored handle
+ * whose FIRST frames have an empty view gives birth to nothing until a frame with points has come.  The filter
+ * parameters of dspmap_set_param are saved and restored, DSPMAP_P_PAIR_CULL_SIGMAS excepted (the loading handle's). */
 int dspmap_save_checkpoint(dspmap_t* m, const char* path);
 int dspmap_load_checkpoint(dspmap_t* m, const char* path);
 /* ---- caller-side pre-processing on the device (next to the hot path; reference src/map_sim_example.cpp:309-336)

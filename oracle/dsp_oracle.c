@@ -369,6 +369,9 @@ float* dspo_obs_max_length(dsp_oracle* o) { return o->obs_maxlen; }
 float dspo_expected_newborn(const dsp_oracle* o) { return o->expected_new_born_objects; }
 void dspo_set_expected_newborn(dsp_oracle* o, float v) { o->expected_new_born_objects = v; }
 void dspo_set_occlusion_margin(dsp_oracle* o, float v) { o->occl_margin = v; }
+/* members next to sigma_ob without a setter in the reference (:156-158, declared :477,486) */
+void dspo_set_kappa(dsp_oracle* o, float v) { o->kappa = v; }                    /* :157, read at :737 */
+void dspo_set_detection_probability(dsp_oracle* o, float v) { o->P_detection = v; } /* :158, read at :732,779,786 */
 float dspo_update_time(const dsp_oracle* o) { return o->update_time; }
 void dspo_use_velocity_estimator(dsp_oracle* o, int on) { o->use_vel_est = on; }
 void dspo_set_current_position(dsp_oracle* o, float x, float y, float z) {
@@ -701,6 +704,12 @@ void dspo_compute_nstatic(dsp_oracle* o, int* out) {
     }
 }
 void dspo_set_nstatic_override(dsp_oracle* o, const int* arr) { o->nstatic_override = arr; }
+/* the frozen function statics of :808-811 as they stand; returns 0 before the first birth call */
+int dspo_birth_statics(const dsp_oracle* o, int* min_static, int* model_generated) {
+    if (min_static) *min_static = o->min_static_nb;
+    if (model_generated) *model_generated = o->model_generated_nb;
+    return o->nb_statics_init;
+}
 
 /* ------------------------------------------------------------------- birth */
 /* mapAddNewBornParticlesByObservation :796-921 */

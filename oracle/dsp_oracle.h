@@ -116,6 +116,7 @@ void dspo_map_update_ck(dsp_oracle* o);      /* pass 1 (:709-735) without the co
 void dspo_map_update_weights(dsp_oracle* o); /* += lambda+kappa (:737), then pass 2 (:743-790) */
 void dspo_compute_nstatic(dsp_oracle* o, int* out);
 void dspo_set_nstatic_override(dsp_oracle* o, const int* arr);
+int dspo_birth_statics(const dsp_oracle* o, int* min_static, int* model_generated); /* the statics of :808-811; 0 = not frozen yet */
 void dspo_occupancy_resample(dsp_oracle* o);                                    /* :924-1057 */
 void dspo_velocity_estimation(dsp_oracle* o);                                   /* :1377-1544 */
 
@@ -151,6 +152,8 @@ float* dspo_obs_max_length(dsp_oracle* o);  /* [NP]           point_cloud_max_le
 float dspo_expected_newborn(const dsp_oracle* o); /* expected_new_born_objects :292 */
 void dspo_set_expected_newborn(dsp_oracle* o, float v);
 void dspo_set_occlusion_margin(dsp_oracle* o, float v); /* obstacle_thickness_for_occlusion :70 (0.3); the variants use voxel_resolution */
+void dspo_set_kappa(dsp_oracle* o, float v);                 /* kappa :157 (0.01): the clutter term of Ck (:737); the reference has no setter */
+void dspo_set_detection_probability(dsp_oracle* o, float v); /* P_detection :158 (0.95), read at :732,779,786; the reference has no setter */
 float dspo_update_time(const dsp_oracle* o);
 int dspo_count_live(const dsp_oracle* o);
 

@@ -78,6 +78,7 @@ def _load(fast=False):
         "dspo_map_update_weights": (None, [P]),
         "dspo_compute_nstatic": (None, [P, P]),
         "dspo_set_nstatic_override": (None, [P, P]),
+        "dspo_birth_statics": (i, [P, ip, ip]),
         "dspo_add_newborn": (None, [P]),
         "dspo_occupancy_resample": (None, [P]),
         "dspo_velocity_estimation": (None, [P]),
@@ -101,6 +102,7 @@ def _load(fast=False):
         "dspo_obs": (fp, [P]), "dspo_obs_count": (ip, [P]), "dspo_obs_max_length": (fp, [P]),
         "dspo_expected_newborn": (f, [P]), "dspo_set_expected_newborn": (None, [P, f]),
         "dspo_set_occlusion_margin": (None, [P, f]),
+        "dspo_set_kappa": (None, [P, f]), "dspo_set_detection_probability": (None, [P, f]),   # dsp_dynamic.h:156-158
         "dspo_update_time": (f, [P]), "dspo_count_live": (i, [P]),
         "dspo_fill_gaussian_tables": (None, [P, P, i, f, f, C.c_uint]),
         "dspo_preprocess_cloud": (i, [i, P, i, f, i, f, f, f, i, P, ip]),

@@ -228,6 +228,55 @@ def test_cube_storage_and_two_branch_frame_change_nothing(dsp, case):
         m.close()
 
 
+def test_two_branch_frame_under_table_swap_and_sigma_change(dsp):
+    """The depth stream with the device estimator on the 66 x 66 x 40 map, 12 frames, parameters changed WHILE the maps run.  After frame 5
+    every map gets new tables whose position table reaches more than three voxels farther than the first one's: FrameParams::birth_reach,
+    by which k_tile_class grows a tile's box before it tests it against the field of view, has to follow -- with the first table's value the
+    two-branch frame would leave newborns of the wider table outside Q, in tiles its main chain does not resample.  After frame 8 sigma_ob
+    goes from 0.1 to 0.05, across weight_culls() (the map's corner lies 7.6 m out: 12 x 9 sigma is 10.8 m, then 5.4 m): another k_weight and
+    the prepared pair path from one frame to the next.  The two-branch map, the split-placement map and both serial maps stay equal frame by
+    frame: every slot, every float, results, future status, counters."""
+    scene_mod = __import__("dsp-map_amd.scene", fromlist=["CorridorScene"])
+    cfg = dict(nx=66, ny=66, nz=40, res=0.15, ppv=24)
+    maps = _trio(dsp, cfg, estimator=2)
+    first = common.tables(21)
+    wider = common.tables(22, n=150001, sigma_p=0.2, nrand=40009)
+    reach0, reach1 = float(np.abs(first[0]).max()), float(np.abs(wider[0]).max())
+    assert reach1 >= reach0 + 3 * cfg["res"], (reach0, reach1)
+    corner = float(np.linalg.norm([0.5 * cfg["res"] * cfg[k] for k in ("nx", "ny", "nz")]))
+    assert 12 * 9 * 0.05 < corner < 12 * 9 * 0.1
+    for m in maps:
+        m.set_tables(*first)
+    sc = scene_mod.CorridorScene(66 * 0.15, 66 * 0.15, 40 * 0.15, seed=1234, device="cuda")
+    frames = [sc.frame(f / 30.0) for f in range(12)]
+    torch.cuda.synchronize()
+    variants, born = [], 0
+    for f, (pts, pos, q) in enumerate(frames):
+        for m in maps:
+            if f == 6:
+                m.set_tables(*wider)
+            if f == 9:
+                m.setObservationStdDev(0.05)
+            assert m.update_device(pts.data_ptr(), pts.shape[0], pos, f / 30.0, q) == 1
+        snaps = [_snapshot(m) for m in maps]
+        _same(snaps[1], snaps[2], (f, "cube storage against index-order storage"))
+        _same(snaps[0], snaps[2], (f, "... and the two-branch frame on top of it"))
+        _same(snaps[3], snaps[2], (f, "... and the serial frame with its placement and its resampling split"))
+        assert len({m.cursors() for m in maps}) == 1, f
+        variants.append(maps[2].weight_variant())
+        if f >= 6:
+            born += snaps[0][4]["n_born"]
+    br = [m.frame_branches() for m in maps]
+    print("table swap: branches", br, "variants", variants, "born behind the swap", born)
+    assert br[0][0] == len(frames) and br[1][0] == 0 and br[2][0] == 0 and br[3][0] == 0, br
+    assert maps[3].resample_split_frames() == len(frames)
+    assert 0 < br[0][1] <= br[0][2] <= br[0][3], br
+    assert variants[:9] == ["mask"] * 9 and variants[9:] == ["skip"] * 3, variants
+    assert born > 10000
+    for m in maps:
+        m.close()
+
+
 def test_two_branch_frame_changes_nothing_at_config_c_full_size(dsp):
     """the same at the size the branches are built for: 132x132x60 @ 0.15 m, every voxel seeded with 24 particles (the benchmark's
     C_sat), the depth stream's clouds and poses; map 0 runs what the handle chooses by itself (cube storage, two branches), map 1
