@@ -100,6 +100,18 @@ REACH_UNREACHED = 65535      # DSPMAP_REACH_UNREACHED
 REACH_WITH_CURRENT = 2       # DSPMAP_REACH_WITH_CURRENT
 REACH_DEVICE_SETS = 4        # DSPMAP_REACH_DEVICE_SETS
 REACH_TIMELINE_MAX_BYTES = 1 << 30   # DSPMAP_REACH_TIMELINE_MAX_BYTES
+# dspmap_cost_bands (dspmap_build_cost_fields) and the DSPMAP_COST_* constants
+COST_MAX_BANDS = 4           # DSPMAP_COST_MAX_BANDS
+COST_MAX_WEIGHT = 8          # DSPMAP_COST_MAX_WEIGHT
+COST_MAX_FIELDS = 64         # DSPMAP_COST_MAX_FIELDS
+COST_MAX_COST = 16384        # DSPMAP_COST_MAX_COST
+COST_UNREACHED = 65535       # DSPMAP_COST_UNREACHED
+
+
+class CostBands(C.Structure):
+    _fields_ = [("n_bands", C.c_int), ("clearance", C.c_float * 4), ("penalty", C.c_int * 4)]
+
+
 # dspmap_path_info (dspmap_shorten_paths)
 PATH_INFO_DTYPE = np.dtype([("n_cells", "i4"), ("n_segments", "i4"), ("n_blocked", "i4"), ("truncated", "i4")])
 SHORTEN_MAX_WINDOW = 64      # DSPMAP_SHORTEN_MAX_WINDOW
@@ -184,6 +196,15 @@ SIGNATURES = {
     "dspmap_reach_timeline_paths": (_i, [_P, _i, _P, _i, _i, _P, _P]),
     "dspmap_reach_timeline_paths_device": (_i, [_P, _i, _P, _i, _i, _P, _P]),
     "dspmap_debug_set_cast_grid": (_i, [_P, _P]),
+    "dspmap_build_cost_fields": (_i, [_P, _i, _i, _P, _f, _P, _i, _i]),
+    "dspmap_build_cost_fields_device": (_i, [_P, _i, _i, _P, _f, _P, _i, _i]),
+    "dspmap_cost_fields_device": (_P, [_P]),
+    "dspmap_get_cost_field": (_i, [_P, _i, _P]),
+    "dspmap_cost_weights_device": (_P, [_P]),
+    "dspmap_get_cost_weights": (_i, [_P, _P]),
+    "dspmap_cost_paths": (_i, [_P, _i, _P, _i, _i, _P, _P]),
+    "dspmap_cost_paths_device": (_i, [_P, _i, _P, _i, _i, _P, _P]),
+    "dspmap_debug_set_distance_field": (_i, [_P, _P]),
     "dspmap_shorten_paths": (_i, [_P, _i, _i, _P, _P, _f, _f, _i, _i, _i, _P, _P, _P]),
     "dspmap_shorten_paths_device": (_i, [_P, _i, _i, _P, _P, _f, _f, _i, _i, _i, _P, _P, _P]),
     "dspmap_build_forecast": (_i, [_P, _i, _P, _i]),
@@ -958,6 +979,85 @@ class DSPMap:
                                                      _ptr(steps) if len(q) else None, _ptr(cells) if max_len > 0 else None))
         return steps, cells
 
+    # -- cost-to-go fields (extension; semantics in include/dspmap.h next to dspmap_build_cost_fields)
+    @staticmethod
+    def _cost_bands(bands):
+        """a sequence of (clearance, penalty) as dspmap_cost_bands; more than COST_MAX_BANDS of them keep their count, for the library to refuse"""
+        bands = list(bands)
+        b = CostBands()
+        b.n_bands = len(bands)
+        for i, (clearance, penalty) in enumerate(bands[:COST_MAX_BANDS]):
+            b.clearance[i], b.penalty[i] = float(clearance), int(penalty)
+        return b
+
+    def build_cost_fields(self, sources, n_fields=1, t=-1.0, bands=(), max_cost=COST_MAX_COST, world=False):
+        """grow n_fields cost-to-go fields from sources {x, y, z, field} through ONE layer of the cast grid (t < 0: the current one, else
+        the horizon of t): entering a free cell costs 1 plus the penalty of every band (clearance, penalty) whose clearance the cell's
+        value in the distance field lies under; a cell's value is its exact minimum cost if <= max_cost, else COST_UNREACHED.  Needs the
+        cast grid and, with bands, the distance field.  numpy sources -> synchronous; a torch tensor on the GPU -> enqueued like
+        build_reach_fields.  Read the result with cost_field / cost_fields_ptr / cost_weights, descend it with cost_paths."""
+        flags = QUERY_WORLD if world else 0
+        b = self._cost_bands(bands)
+        if self._is_device_tensor(sources):
+            q = self._reach_points_device(sources, "build_cost_fields")
+            n = q.numel() // 4
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_build_cost_fields_device(self.h, int(n_fields), n, q.data_ptr(), float(t), C.addressof(b), int(max_cost), flags))
+            after()
+            return
+        q = self._reach_points(sources, "build_cost_fields")
+        self._chk(self.L.dspmap_build_cost_fields(self.h, int(n_fields), len(q), _ptr(q) if len(q) else None, float(t), C.addressof(b),
+                                                  int(max_cost), flags))
+
+    def cost_field(self, field=None, n_fields=None):
+        """the values of one field of the last cost build as numpy uint16 [nz, ny, nx] (COST_UNREACHED where the cost exceeds max_cost or
+        no path exists), or with field=None those of the first n_fields fields [n_fields, nz, ny, nx] (synchronous host copies)"""
+        shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
+        if field is None and n_fields is None:
+            raise ValueError("cost_field: a field, or n_fields for all of them")
+        fields = range(int(n_fields)) if field is None else [int(field)]
+        out = np.zeros((len(fields),) + shape, np.uint16)
+        for j, f in enumerate(fields):
+            self._chk(self.L.dspmap_get_cost_field(self.h, f, _ptr(out[j])))
+        return out if field is None else out[0]
+
+    def cost_fields_ptr(self):
+        """device address of the [n_fields][V] uint16 values, or None when there are none / they are stale"""
+        return self.L.dspmap_cost_fields_device(self.h) or None
+
+    def cost_weights(self):
+        """the weights of the last cost build as numpy uint8 [nz, ny, nx]: 0 blocked, else what entering the cell costs"""
+        out = np.zeros((self.cfg.nz, self.cfg.ny, self.cfg.nx), np.uint8)
+        self._chk(self.L.dspmap_get_cost_weights(self.h, _ptr(out)))
+        return out
+
+    def cost_paths(self, starts, max_len, world=False):
+        """descend the last cost build from starts {x, y, z, field}: (cost [n] int32: the start's value, -1 unreached, -2 outside the
+        map, -3 invalid; cells [n, max_len] int32: voxel indices from the start's cell to a cell of value 0, -1 behind the end) -- what
+        shorten_paths takes as (steps, cells).  numpy in -> numpy out, synchronous; a torch tensor on the GPU -> tensors on the same
+        device, enqueued like build_cost_fields."""
+        flags = QUERY_WORLD if world else 0
+        max_len = int(max_len)
+        if self._is_device_tensor(starts):
+            import torch
+            q = self._reach_points_device(starts, "cost_paths")
+            n = q.numel() // 4
+            cost = torch.empty(n, dtype=torch.int32, device=q.device)
+            cells = torch.empty((n, max(max_len, 0)), dtype=torch.int32, device=q.device)
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_cost_paths_device(self.h, n, q.data_ptr(), max_len, flags, cost.data_ptr(),
+                                                      cells.data_ptr() if max_len > 0 else None))
+            after()
+            return cost, cells
+        q = self._reach_points(starts, "cost_paths")
+        cost = np.zeros(len(q), np.int32)
+        cells = np.zeros((len(q), max(max_len, 0)), np.int32)
+        self._chk(self.L.dspmap_cost_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags, _ptr(cost) if len(q) else None,
+                                           _ptr(cells) if max_len > 0 else None))
+        return cost, cells
+
     # -- shortened paths (extension; semantics in include/dspmap.h next to dspmap_shorten_paths)
     def shorten_paths(self, steps, cells, t_start=-1.0, step_seconds=0.0, window=SHORTEN_MAX_WINDOW, max_seg=None):
         """cut cell paths (steps [n] int32, cells [n, max_len] int32: what reach_paths and reach_timeline_paths return, or any polyline
@@ -1397,6 +1497,15 @@ class DSPMap:
         if w.shape != shape:
             raise ValueError("set_cast_grid: words of shape %s" % (shape,))
         self._chk(self.L.dspmap_debug_set_cast_grid(self.h, _ptr(w)))
+
+    def set_distance_field(self, layers):
+        """test hook: replace all layers of the valid distance field with layers (float32 [L, nz, ny, nx], what distance_field() returns
+        per layer)"""
+        a = np.ascontiguousarray(layers, np.float32)
+        shape = (self.T + 1, self.cfg.nz, self.cfg.ny, self.cfg.nx)
+        if a.shape != shape:
+            raise ValueError("set_distance_field: layers of shape %s" % (shape,))
+        self._chk(self.L.dspmap_debug_set_distance_field(self.h, _ptr(a)))
 
     def getVoxelPositionFromIndexPublic(self, index):
         x, y, z = C.c_float(), C.c_float(), C.c_float()

@@ -44,6 +44,16 @@ struct LayerState {
     int* tl_last = nullptr;
     bool tl_valid = false;
     int tl_max_steps = 0;            // max_steps of the build that wrote it
+    // cost-to-go fields (dspmap_build_cost_fields): the values [cf_n][V] uint16, the wavefront's scratch [cf_n][COST_SET_COUNT][nz * ny * W],
+    // and what all fields of a build share -- the weight bytes [V], the sets W_1 .. W_8 [8][nz * ny * W] and the word of occurring weights;
+    // allocated by the first build (the first two grown by a larger one), freed with the device state.  cf_valid: a snapshot of the cast
+    // grid AND of the distance field -- cleared with cg_valid, by every call that changes the grid, by every dspmap_build_distance_field
+    // and dspmap_debug_set_distance_field (also when the build had no bands: one rule) and by a new cost build; not by a reach build
+    unsigned short* cf_field = nullptr; size_t cf_field_cells = 0;
+    u64* cf_sets = nullptr; size_t cf_sets_words = 0;
+    unsigned char* cf_weight = nullptr; u64* cf_wk = nullptr; int* cf_occ = nullptr;
+    bool cf_valid = false;
+    int cf_n = 0;                    // fields of the last build
     // occupancy forecast (dspmap_build_forecast): the layers [fc_n][V] floats and the sweep's accumulators [fc_n + 1][v_loc] (the moving
     // particles' per layer, then the static sums); allocated (and grown) by a build, freed with the device state.  fc_valid: the life cycle
     // of df_valid (dspmap_snapshots_stale)
@@ -97,7 +107,8 @@ struct LayerState {
     bool tk_have = false, tk_valid = false;
 };
 // What a change makes stale.  The snapshots depend on each other like this:
-//     map -> distance field, forecast, cast grid, objects;   cast grid -> arrival fields, frontiers, objects;   arrival fields -> timeline;
+//     map -> distance field, forecast, cast grid, objects;   cast grid -> arrival fields, frontiers, objects, cost fields;
+//     arrival fields -> timeline;                   distance field -> cost fields;
 //     known-space layer -> frontiers;               position -> frontiers
 // LAYERS_x_CHANGED: x has changed under the snapshots taken of it.  LAYERS_x_REBUILD: a build of x starts -- x itself is stale too, until the
 // build sets its flag behind its launch.  dspmap_layers_stale is the ONLY place that clears a *_valid flag, so a reader tests its own flag alone.
@@ -110,6 +121,8 @@ enum LayerChange {
     LAYERS_POSITION_CHANGED,
     LAYERS_FRONTIERS_REBUILD,
     LAYERS_DISTANCE_REBUILD,
+    LAYERS_DISTANCE_CHANGED,    // replaced in place (dspmap_debug_set_distance_field): the field itself stays valid
+    LAYERS_COST_REBUILD,
     LAYERS_FORECAST_REBUILD,
     LAYERS_OBJECTS_REBUILD
 };
@@ -117,12 +130,14 @@ inline void dspmap_layers_stale(LayerState& l, LayerChange c) {
     switch (c) {   // (the first four cases are one chain: each falls through to what depends on it)
     case LAYERS_MAP_CHANGED: l.df_valid = false; l.fc_valid = false; [[fallthrough]];
     case LAYERS_CAST_GRID_REBUILD: l.cg_valid = false; [[fallthrough]];
-    case LAYERS_CAST_GRID_CHANGED: l.fr_valid = false; l.ob_valid = false; [[fallthrough]];
+    case LAYERS_CAST_GRID_CHANGED: l.fr_valid = false; l.ob_valid = false; l.cf_valid = false; [[fallthrough]];
     case LAYERS_REACH_REBUILD: l.rf_valid = false; l.tl_valid = false; break;
     case LAYERS_KNOWN_CHANGED:
     case LAYERS_POSITION_CHANGED:
     case LAYERS_FRONTIERS_REBUILD: l.fr_valid = false; break;
-    case LAYERS_DISTANCE_REBUILD: l.df_valid = false; break;
+    case LAYERS_DISTANCE_REBUILD: l.df_valid = false; [[fallthrough]];
+    case LAYERS_DISTANCE_CHANGED:
+    case LAYERS_COST_REBUILD: l.cf_valid = false; break;
     case LAYERS_FORECAST_REBUILD: l.fc_valid = false; break;
     case LAYERS_OBJECTS_REBUILD: l.ob_valid = false; break;
     }

@@ -241,6 +241,41 @@ void launch_reach(const LaunchCtx& c, const ReachArgs& a, const struct dspmap_re
 void launch_reach_timeline_paths(const LaunchCtx& c, const ReachTimelinePathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out,
                                  int* cells_out);
 void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out, int* cells_out);
+// clearance-weighted cost-to-go fields: a bucketed wavefront through one layer of the cast grid, one workgroup per field (dspmap_cost.hip;
+// semantics in include/dspmap.h, dspmap_build_cost_fields)
+#define COST_MAX_BANDS 4    // == DSPMAP_COST_MAX_BANDS
+#define COST_MAX_WEIGHT 8   // == DSPMAP_COST_MAX_WEIGHT
+#define COST_SET_COUNT 11   // sets of nz * ny * W words a field's scratch holds: 8 grown level sets, 2 level sets, settled
+struct CostWeightArgs {
+    int n_bands;
+    float clearance[COST_MAX_BANDS];
+    int penalty[COST_MAX_BANDS];
+    const u64* bits;         // [nz][ny][W] the build's layer of the cast grid
+    const float* dist;       // [V] the build's layer of the distance field; not read when n_bands == 0
+    unsigned char* weight;   // [V] 0 blocked, else w
+    u64* wk;                 // [COST_MAX_WEIGHT][nz][ny][W] the cells of weight k, k = 1 ..
+    int* occ;                // bit k: weight k occurs (zeroed on the stream before the launch)
+};
+struct CostArgs {
+    float ox, oy, oz;    // as QueryArgs
+    int world;
+    int max_cost;
+    int n_fields, n_src;
+    const u64* wk;       // as CostWeightArgs
+    const int* occ;
+    unsigned short* field;   // [n_fields][V], preset to DSPMAP_COST_UNREACHED
+    u64* sets;           // [n_fields][COST_SET_COUNT][nz * ny * W] device scratch
+};
+struct CostPathArgs {
+    float ox, oy, oz;
+    int world;
+    int n_fields, max_len;
+    const unsigned short* field;
+    const unsigned char* weight;
+};
+void launch_cost_weights(const LaunchCtx& c, const CostWeightArgs& a);
+void launch_cost_wave(const LaunchCtx& c, const CostArgs& a, const struct dspmap_reach_point* src);
+void launch_cost_paths(const LaunchCtx& c, const CostPathArgs& a, int n, const struct dspmap_reach_point* start, int* cost_out, int* cells_out);
 // cell paths shortened to line-of-sight waypoints, one wave per path (dspmap_shorten.hip; semantics in include/dspmap.h, dspmap_shorten_paths)
 struct ShortenArgs {
     float cx, cy, cz;    // as QueryArgs: dspmap_voxel_center

@@ -1,5 +1,5 @@
 // dspmap_layers.hip -- host side of the planning layers that read the map: point and trajectory queries, distance fields, the cast grid with
-// segment casts and free boxes, arrival-time fields with timeline and paths, shortened paths, the forecast, the known-space layer, view scores and frontiers.
+// segment casts and free boxes, arrival-time fields with timeline and paths, shortened paths, cost-to-go fields, the forecast, the known-space layer, view scores and frontiers.
 // Their kernels are in a file each (named per section); their state is LayerState (dspmap_internal.h), and what makes a snapshot stale is
 // decided in ONE place, dspmap_layers_stale next to it.  An entry point that takes host arrays is: check -> stage -> enqueue -> read back,
 // around the same *_enqueue its _device twin calls.  Checks fire in this order: arguments, slab and state, then the device.
@@ -1539,11 +1539,188 @@ extern "C" int dspmap_get_tracks(dspmap_t* m, int cap, dspmap_track* out, int* n
 extern "C" const dspmap_track* dspmap_tracks_device(dspmap_t* m) { return (m && m->ly.tk_valid) ? m->ly.tk_tracks[m->ly.tk_cur] : nullptr; }
 extern "C" const long long* dspmap_track_counts_device(dspmap_t* m) { return (m && m->ly.tk_valid) ? m->ly.tk_counts : nullptr; }
 
+// --------------------------------------------------- cost-to-go fields (dspmap_cost.hip; semantics in include/dspmap.h)
+static_assert(COST_MAX_BANDS == DSPMAP_COST_MAX_BANDS && COST_MAX_WEIGHT == DSPMAP_COST_MAX_WEIGHT, "CostWeightArgs holds DSPMAP_COST_MAX_BANDS bands");
+static_assert(sizeof(dspmap_cost_bands) == 36, "dspmap_cost_bands is 36 bytes");
+// the checks of both builds, in the header's order: arguments, then slab, cast grid and (with bands) distance field
+static int cost_build_check(dspmap* m, int n_fields, int n_src, const void* src, float t, const dspmap_cost_bands* bands, int max_cost, int flags) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n_fields < 1 || n_fields > DSPMAP_COST_MAX_FIELDS)
+        return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: n_fields %d outside [1, %d]", n_fields, DSPMAP_COST_MAX_FIELDS);
+    if (n_src < 0) return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: negative source count %d", n_src);
+    if (n_src > 0 && !src) return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: NULL source array");
+    if (t != t) return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: t is NaN");
+    if (!bands) return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: NULL bands");
+    if (bands->n_bands < 0 || bands->n_bands > DSPMAP_COST_MAX_BANDS)
+        return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: n_bands %d outside [0, %d]", bands->n_bands, DSPMAP_COST_MAX_BANDS);
+    for (int i = 0; i < bands->n_bands; ++i)
+        if (!(bands->clearance[i] > 0.f && bands->clearance[i] < INFINITY))
+            return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: clearance[%d] = %g is NaN, infinite or not positive", i, (double)bands->clearance[i]);
+    int total = 1;
+    for (int i = 0; i < bands->n_bands; ++i) {
+        if (bands->penalty[i] < 0 || bands->penalty[i] > DSPMAP_COST_MAX_WEIGHT - 1)
+            return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: penalty[%d] = %d outside [0, %d]", i, bands->penalty[i], DSPMAP_COST_MAX_WEIGHT - 1);
+        total += bands->penalty[i];
+    }
+    if (total > DSPMAP_COST_MAX_WEIGHT)
+        return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: the largest weight 1 + sum of penalty = %d exceeds DSPMAP_COST_MAX_WEIGHT = %d", total,
+                           DSPMAP_COST_MAX_WEIGHT);
+    if (max_cost < 1 || max_cost > DSPMAP_COST_MAX_COST)
+        return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: max_cost %d outside [1, %d]", max_cost, DSPMAP_COST_MAX_COST);
+    int rc = flags_check(m, "cost fields", flags, DSPMAP_QUERY_WORLD);
+    if (rc != DSPMAP_OK) return rc;
+    const unsigned long long cells = (unsigned long long)n_fields * (unsigned long long)m->d.v_glob;
+    if (cells > 0x80000000ull) return dspmap_fail(m, DSPMAP_E_ARG, "cost fields: %d fields of %d cells exceed 2^31 cells", n_fields, m->d.v_glob);
+    if ((rc = whole_map_check(m, "cost fields", "a wavefront crosses slabs")) != DSPMAP_OK) return rc;
+    if ((rc = cast_grid_ready(m, "dspmap_build_cost_fields")) != DSPMAP_OK) return rc;
+    return bands->n_bands > 0 ? dist_field_ready(m, "dspmap_build_cost_fields") : DSPMAP_OK;
+}
+// the two launches behind both build entry points; src_dev may be NULL with n_src == 0
+static int cost_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_point* src_dev, float t, const dspmap_cost_bands* bands, int max_cost,
+                      int flags) {
+    const MapDims& d = m->d;
+    dspmap_layers_stale(m->ly, LAYERS_COST_REBUILD);
+    const size_t V = (size_t)d.v_glob, cells = (size_t)n_fields * V, lw = cast_layer_words(d);
+    const size_t set_words = (size_t)COST_SET_COUNT * lw * (size_t)n_fields;
+    if (!m->ly.cf_weight || cells > m->ly.cf_field_cells || set_words > m->ly.cf_sets_words) {   // grown only after the stream has drained (an earlier call may still read them)
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        if (!m->ly.cf_weight) HIPCHK(m, hipMalloc(&m->ly.cf_weight, V));
+        if (!m->ly.cf_wk) HIPCHK(m, hipMalloc(&m->ly.cf_wk, sizeof(u64) * COST_MAX_WEIGHT * lw));
+        if (!m->ly.cf_occ) HIPCHK(m, hipMalloc(&m->ly.cf_occ, sizeof(int)));
+        if (cells > m->ly.cf_field_cells) {
+            if (m->ly.cf_field) { HIPCHK(m, hipFree(m->ly.cf_field)); m->ly.cf_field = nullptr; m->ly.cf_field_cells = 0; }
+            HIPCHK(m, hipMalloc(&m->ly.cf_field, sizeof(unsigned short) * cells));
+            m->ly.cf_field_cells = cells;
+        }
+        if (set_words > m->ly.cf_sets_words) {
+            if (m->ly.cf_sets) { HIPCHK(m, hipFree(m->ly.cf_sets)); m->ly.cf_sets = nullptr; m->ly.cf_sets_words = 0; }
+            HIPCHK(m, hipMalloc(&m->ly.cf_sets, sizeof(u64) * set_words));
+            m->ly.cf_sets_words = set_words;
+        }
+    }
+    const int l = frontier_layer_host(d, t);   // ONE layer for the whole build: dspmap_build_objects' rule
+    CostWeightArgs w;
+    w.n_bands = bands->n_bands;
+    for (int i = 0; i < COST_MAX_BANDS; ++i) {
+        w.clearance[i] = i < bands->n_bands ? bands->clearance[i] : 0.f;
+        w.penalty[i] = i < bands->n_bands ? bands->penalty[i] : 0;
+    }
+    w.bits = m->ly.cg_bits + lw * (size_t)l;
+    w.dist = bands->n_bands > 0 ? m->ly.df_field + V * (size_t)l : nullptr;
+    w.weight = m->ly.cf_weight; w.wk = m->ly.cf_wk; w.occ = m->ly.cf_occ;
+    CostArgs a;
+    origin_fill(m, flags, &a);
+    a.max_cost = max_cost; a.n_fields = n_fields; a.n_src = n_src;
+    a.wk = m->ly.cf_wk; a.occ = m->ly.cf_occ; a.field = m->ly.cf_field; a.sets = m->ly.cf_sets;
+    const LaunchCtx c = dspmap_ctx_of(m);
+    HIPCHK(m, hipMemsetAsync(m->ly.cf_occ, 0, sizeof(int), m->stream));
+    launch_cost_weights(c, w);
+    HIPCHK(m, hipMemsetAsync(m->ly.cf_field, 0xff, sizeof(unsigned short) * cells, m->stream));   // every value DSPMAP_COST_UNREACHED
+    launch_cost_wave(c, a, src_dev);
+    HIPCHK(m, hipGetLastError());
+    m->ly.cf_n = n_fields;
+    m->ly.cf_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_build_cost_fields(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t, const dspmap_cost_bands* bands,
+                                        int max_cost, int flags) {
+    int rc = cost_build_check(m, n_fields, n_src, src, t, bands, max_cost, flags);
+    if (rc != DSPMAP_OK) return rc;
+    StageSec s[1] = {{src, nullptr, sizeof(dspmap_reach_point) * (size_t)n_src}};   // (no sources: no section, the kernel gets NULL)
+    if ((rc = stage_begin(m, s, 1)) != DSPMAP_OK) return rc;
+    if ((rc = cost_build(m, n_fields, n_src, (const dspmap_reach_point*)s[0].dev, t, bands, max_cost, flags)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 1);
+}
+extern "C" int dspmap_build_cost_fields_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src, float t,
+                                               const dspmap_cost_bands* bands, int max_cost, int flags) {
+    const int rc = cost_build_check(m, n_fields, n_src, src, t, bands, max_cost, flags);
+    if (rc != DSPMAP_OK) return rc;
+    return cost_build(m, n_fields, n_src, src, t, bands, max_cost, flags);
+}
+extern "C" const unsigned short* dspmap_cost_fields_device(dspmap_t* m) { return (m && m->ly.cf_valid) ? m->ly.cf_field : nullptr; }
+extern "C" const unsigned char* dspmap_cost_weights_device(dspmap_t* m) { return (m && m->ly.cf_valid) ? m->ly.cf_weight : nullptr; }
+static int cost_ready(dspmap* m, const char* what) {
+    const int rc = whole_map_check(m, what, "a wavefront crosses slabs");
+    if (rc != DSPMAP_OK) return rc;
+    return snapshot_ready(m, m->ly.cf_valid, what,
+                          "no cost fields, or the map, its cast grid or its distance field has changed since they were built (dspmap_build_cost_fields)");
+}
+extern "C" int dspmap_get_cost_field(dspmap_t* m, int field, unsigned short* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "cost field: NULL output array");
+    if (field < 0 || field >= DSPMAP_COST_MAX_FIELDS) return dspmap_fail(m, DSPMAP_E_ARG, "cost field: field %d outside [0, %d)", field, DSPMAP_COST_MAX_FIELDS);
+    const int rc = cost_ready(m, "dspmap_get_cost_field");
+    if (rc != DSPMAP_OK) return rc;
+    if (field >= m->ly.cf_n) return dspmap_fail(m, DSPMAP_E_ARG, "cost field: field %d outside [0, %d), the fields of the last build", field, m->ly.cf_n);
+    return read_back(m, out, m->ly.cf_field + (size_t)field * m->d.v_glob, sizeof(unsigned short) * (size_t)m->d.v_glob);
+}
+extern "C" int dspmap_get_cost_weights(dspmap_t* m, unsigned char* out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "cost weights: NULL output array");
+    const int rc = cost_ready(m, "dspmap_get_cost_weights");
+    if (rc != DSPMAP_OK) return rc;
+    return read_back(m, out, m->ly.cf_weight, (size_t)m->d.v_glob);
+}
+// the checks of dspmap_cost_paths*: the arguments of dspmap_reach_paths, then the snapshot
+static int cost_paths_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* cost_out, const void* cells_out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: negative start count %d", n);
+    if (max_len < 0 || max_len > DSPMAP_REACH_MAX_STEPS + 1)
+        return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: max_len %d outside [0, %d]", max_len, DSPMAP_REACH_MAX_STEPS + 1);
+    if (n > 0 && (!start || !cost_out)) return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: NULL start or cost_out array");
+    if (n > 0 && max_len > 0 && !cells_out) return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: NULL cells_out array with max_len %d", max_len);
+    const int rc = flags_check(m, "cost paths", flags, DSPMAP_QUERY_WORLD);
+    if (rc != DSPMAP_OK) return rc;
+    if ((unsigned long long)n * (unsigned long long)max_len > 0x80000000ull)
+        return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: %d paths of %d cells exceed 2^31 cells", n, max_len);
+    return cost_ready(m, "dspmap_cost_paths");
+}
+static int cost_paths_enqueue(dspmap* m, int n, const dspmap_reach_point* ds, int max_len, int flags, int* dt, int* dc) {
+    CostPathArgs a;
+    origin_fill(m, flags, &a);
+    a.n_fields = m->ly.cf_n; a.max_len = max_len;
+    a.field = m->ly.cf_field; a.weight = m->ly.cf_weight;
+    launch_cost_paths(dspmap_ctx_of(m), a, n, ds, dt, dc);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_cost_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* cost_out, int* cells_out) {
+    int rc = cost_paths_check(m, n, start, max_len, flags, cost_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[3] = {{start, nullptr, sizeof(dspmap_reach_point) * (size_t)n}, {nullptr, cost_out, sizeof(int) * (size_t)n},
+                     {nullptr, cells_out, sizeof(int) * (size_t)n * max_len}};   // (max_len == 0: no cells section, the kernel gets NULL)
+    if ((rc = stage_begin(m, s, 3)) != DSPMAP_OK) return rc;
+    if ((rc = cost_paths_enqueue(m, n, (const dspmap_reach_point*)s[0].dev, max_len, flags, (int*)s[1].dev, (int*)s[2].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 3);
+}
+extern "C" int dspmap_cost_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* cost_out, int* cells_out) {
+    const int rc = cost_paths_check(m, n, start, max_len, flags, cost_out, cells_out);
+    if (rc != DSPMAP_OK) return rc;
+    return cost_paths_enqueue(m, n, start, max_len, flags, cost_out, cells_out);
+}
+// test hook: all L layers of the VALID distance field are replaced by the caller's floats
+extern "C" int dspmap_debug_set_distance_field(dspmap_t* m, const float* layers) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!layers) return dspmap_fail(m, DSPMAP_E_ARG, "set distance field: NULL layer array");
+    const size_t total = (size_t)(m->d.T + 1) * (size_t)m->d.v_glob;
+    for (size_t i = 0; i < total; ++i)
+        if (!(layers[i] >= 0.f && layers[i] < INFINITY))
+            return dspmap_fail(m, DSPMAP_E_ARG, "set distance field: value %zu = %g is NaN, negative or infinite", i, (double)layers[i]);
+    int rc = whole_map_check(m, "set distance field", "");
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = dist_field_ready(m, "dspmap_debug_set_distance_field")) != DSPMAP_OK) return rc;
+    dspmap_layers_stale(m->ly, LAYERS_DISTANCE_CHANGED);
+    HIPCHK(m, hipMemcpyAsync(m->ly.df_field, layers, sizeof(float) * total, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));   // (the caller's array is free again)
+    return DSPMAP_OK;
+}
+
 // --------------------------------------------------- the end of the handle
 void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const char*)>& chk) {
     const LayerState& l = m->ly;
     for (void* q : {(void*)l.q_buf, (void*)l.df_field, (void*)l.df_g8, (void*)l.df_h16, (void*)l.cg_bits, (void*)l.cg_tmp, (void*)l.rf_field,
-                    (void*)l.rf_sets, (void*)l.tl_hist, (void*)l.tl_last, (void*)l.fc_field, (void*)l.fc_acc, (void*)l.kn_stamp, (void*)l.vw_dirs0,
+                    (void*)l.rf_sets, (void*)l.tl_hist, (void*)l.tl_last, (void*)l.cf_field, (void*)l.cf_sets, (void*)l.cf_weight, (void*)l.cf_wk, (void*)l.cf_occ, (void*)l.fc_field, (void*)l.fc_acc, (void*)l.kn_stamp, (void*)l.vw_dirs0,
                     (void*)l.fr_grid, (void*)l.fr_cells, (void*)l.fr_counts, (void*)l.fr_item_free, (void*)l.fr_dense, (void*)l.fr_blocks,
                     (void*)l.fr_tiles, (void*)l.ob_parent, (void*)l.ob_root, (void*)l.ob_labels, (void*)l.ob_tiles, (void*)l.ob_counts,
                     (void*)l.ob_objects, (void*)l.tk_labels, (void*)l.tk_objects, (void*)l.tk_tracks[0], (void*)l.tk_tracks[1], (void*)l.tk_shift,

@@ -323,6 +323,21 @@ public:
                      dspmap_path_info* info, dspmap_segment* segs, int* ends) {
         return dspmap_shorten_paths(h_, n, max_len, steps, cells, t_start, step_seconds, window, max_seg, 0, info, segs, ends);
     }
+    /* extension: clearance-weighted cost-to-go fields (dspmap_build_cost_fields in dspmap.h): the wavefront of buildReachFields through ONE
+     * layer (t < 0: the current one), the step into a free cell costing 1 plus the penalty of every band whose clearance the cell's value
+     * in the distance field lies under.  Needs buildCastGrid() and, with bands, buildDistanceField() since the last update(); read-only.
+     * getCostField copies one field's V uint16 values (DSPMAP_COST_UNREACHED above max_cost), getCostWeights the V weight bytes (0 blocked);
+     * costPaths descends from starts[i] (cost[i] = the start's value or a negative cause, cells as reachPaths) -- what shortenPaths takes.
+     * Return DSPMAP_OK or a negative error code. */
+    int buildCostFields(int n_fields, int n_src, const dspmap_reach_point* src, float t, const dspmap_cost_bands& bands, int max_cost,
+                        bool world = false) {
+        return dspmap_build_cost_fields(h_, n_fields, n_src, src, t, &bands, max_cost, world ? DSPMAP_QUERY_WORLD : 0);
+    }
+    int getCostField(int field, unsigned short* values) { return dspmap_get_cost_field(h_, field, values); }
+    int getCostWeights(unsigned char* weights) { return dspmap_get_cost_weights(h_, weights); }
+    int costPaths(int n, const dspmap_reach_point* starts, int max_len, int* cost, int* cells, bool world = false) {
+        return dspmap_cost_paths(h_, n, starts, max_len, world ? DSPMAP_QUERY_WORLD : 0, cost, cells);
+    }
     /* extension: occupancy forecast at times of the caller's choosing (dspmap_build_forecast in dspmap.h): layer j = the mass of every live
      * particle, newborns included, rolled out to times[j] seconds after the last update() -- strictly ascending, at most
      * DSPMAP_FORECAST_MAX_TIMES.  Read-only towards the map; a snapshot that goes stale with the next update().  getForecast copies one

@@ -687,6 +687,102 @@ int dspmap_shorten_paths_device(dspmap_t* m, int n, int max_len, const int* step
                                 int window, int max_seg, int flags /* must be 0 */, dspmap_path_info* info_out_dev, dspmap_segment* seg_out_dev,
                                 int* end_out_dev);
 
+/* ---- cost-to-go fields: the wavefront weighted by clearance (no counterpart in the reference).  dspmap_build_reach_fields is a unit-cost
+ * wavefront, so the paths it hands to dspmap_shorten_paths and dspmap_grow_boxes are the shortest 6-connected ones, and those hug the
+ * obstacles at exactly the grid's inflation radius.  The clearance that pushes a path into the open is on the device already, per layer
+ * and exact (dspmap_build_distance_field).  A build of cost fields joins the two snapshots: the step into a cell costs 1 plus a penalty from
+ * the clearance band the cell lies in, the integer cost-to-go is exact, and the descent paths go out in the layout dspmap_shorten_paths*
+ * takes -- instead of three copies to the host and Dijkstra there.
+ *
+ *  - inputs: the valid cast grid of the last dspmap_build_cast_grid (the blocked cells) and, when n_bands > 0, the valid distance field of
+ *    the last dspmap_build_distance_field (the clearance).  The two are independent snapshots and may have been built with different
+ *    thresholds; that is the caller's business.
+ *  - layer: ONE layer l for the whole build, by the rule dspmap_build_objects has for its t: t < 0 or T == 0 selects layer 0, otherwise
+ *    l = 1 + k(t) with the k(t) of dspmap_query_occupancy.  The cost fields are static in that layer.
+ *  - weight of a cell c: w(c) = 0 if the bit of c is set in layer l of the cast grid (blocked); otherwise
+ *    w(c) = 1 + sum over i < n_bands of penalty[i] * [F_l(c) < clearance[i]], where F_l(c) is the float the distance field stores for c in
+ *    layer l and the comparison is in fp32.  Bands may nest, their order does not matter.  The distance field is truncated at
+ *    R * voxel_resolution (R = its max_voxels), so a clearance above that applies to EVERY free cell -- it raises all weights alike and
+ *    steers nothing.
+ *  - sources: dspmap_reach_point {x, y, z, field}; the cell rule, the frame rule, DSPMAP_QUERY_WORLD and "ignored if non-finite, outside
+ *    the map or with `field` outside [0, n_fields)" are those of dspmap_build_reach_fields.  A source in a blocked cell is ignored.  S_f =
+ *    the free source cells of field f.
+ *  - cost: the cost of a 6-connected path c_0 .. c_m inside the map with c_0 in S_f and every w(c_j) > 0 is the sum over j = 1 .. m of
+ *    w(c_j), the weight of every cell ENTERED.  cost_f(c) is the minimum over such paths; a free source cell has cost 0.
+ *  - value of a cell, uint16: cost_f(c) if that is <= max_cost, else DSPMAP_COST_UNREACHED.  Fields are [n_fields][nz][ny][nx] in the
+ *    reference's voxel index order, whatever DSPMAP_P_TILING stores.
+ *  - consequences: with n_bands == 0 the fields equal, uint16 for uint16, those of a static dspmap_build_reach_fields build of the same
+ *    layer with max_steps = max_cost and without DSPMAP_REACH_WITH_CURRENT.  A cell of value v > 0 has a face neighbour of value exactly
+ *    v - w(c).  For face neighbours a, b that are both reached, v(b) <= v(a) + w(b).
+ *  - paths, dspmap_cost_paths*: starts and the codes of cost_out[i] are dspmap_reach_paths': the value of the start's cell, -1 if that is
+ *    DSPMAP_COST_UNREACHED, -2 if the point is outside the map, -3 if a coordinate is non-finite or `field` is outside [0, n_fields)
+ *    (-3 wins over -2).  cells_out[i * max_len + 0] is the start's cell; from a cell c_j of value v_j > 0 the next cell is the FIRST face
+ *    neighbour inside the map, in the order -x, +x, -y, +y, -z, +z, whose value is exactly v_j - w(c_j).  The path ends at a cell of value 0
+ *    or after max_len cells; the remaining entries, and all of them when cost_out[i] < 0, are -1.  Should no neighbour qualify the path
+ *    stops there and the rest is -1: no loop is unbounded.  (cost_out, cells_out) is what dspmap_shorten_paths* takes as (steps, cells): use
+ *    t_start = t, step_seconds = 0 for a predicted layer and t_start < 0 for layer 0.
+ *  - known answer: a 10 x 3 x 1 map with nothing blocked, F = 0.05 in row y = 0 and F = 1.0 in the other rows, one band {clearance 0.1,
+ *    penalty 4}, the source at cell (0, 0, 0), max_cost 100.  The values are
+ *        y = 0:   0  5  8  9 10 11 12 13 14 15
+ *        y = 1:   1  2  3  4  5  6  7  8  9 10
+ *        y = 2:   2  3  4  5  6  7  8  9 10 11
+ *    and the path from (9, 0, 0) has 12 cells: (9,0), (9,1), (8,1), ..., (0,1), (0,0).  The unweighted field reads 9 at (9, 0, 0), and its
+ *    path stays in row 0.
+ *  - arguments, checked before the device is touched, DSPMAP_E_ARG with a text, in this order: a NULL handle, n_fields outside
+ *    1 .. DSPMAP_COST_MAX_FIELDS, n_src < 0, a NULL array with n_src > 0, a NaN t, a NULL bands, n_bands outside 0 .. DSPMAP_COST_MAX_BANDS,
+ *    a clearance[i] with i < n_bands that is NaN, infinite or <= 0, a penalty[i] with i < n_bands outside 0 .. DSPMAP_COST_MAX_WEIGHT - 1,
+ *    1 + sum of penalty > DSPMAP_COST_MAX_WEIGHT, max_cost outside 1 .. DSPMAP_COST_MAX_COST, flags other than DSPMAP_QUERY_WORLD,
+ *    n_fields * V > 2^31.  Paths: the argument checks of dspmap_reach_paths, max_len in 0 .. DSPMAP_REACH_MAX_STEPS + 1.
+ *    DSPMAP_COST_MAX_COST is a condition, not a measurement: DSPMAP_REACH_MAX_STEPS hops at a mean weight of 4; the level loop is bounded
+ *    by it.
+ *  - state, after the arguments and in this order: a sharded handle (slab) is DSPMAP_E_STATE; a stale or never-built cast grid is
+ *    DSPMAP_E_STATE with a text naming dspmap_build_cast_grid; with n_bands > 0 a stale or never-built distance field is DSPMAP_E_STATE
+ *    with a text naming dspmap_build_distance_field (without a usable device there is neither).  The accessors and the paths on a stale or
+ *    never-built snapshot are DSPMAP_E_STATE with a text naming dspmap_build_cost_fields, and the two *_device accessors return NULL.  A
+ *    device call that fails is DSPMAP_E_DEVICE.
+ *  - life cycle: the snapshot goes stale with everything that makes the cast grid stale, with every rebuild or in-place change of the grid
+ *    (dspmap_build_cast_grid, dspmap_mask_cast_grid, dspmap_debug_set_cast_grid), with every dspmap_build_distance_field and
+ *    dspmap_debug_set_distance_field -- also when the last build had n_bands == 0, so that there is one rule -- and with every new cost
+ *    build.  A reach build does not touch it, and a cost build does not touch the reach snapshot.  READ-ONLY towards the map, the grid and
+ *    the distance field in every sense listed for dspmap_grow_boxes.  The buffers are allocated by the first build (grown by a larger
+ *    one) and freed with the device state; a handle that never builds one allocates nothing.  Enqueued on the handle's stream behind the
+ *    builds of the grid and the distance field and the frame.
+ *  - not offered: weights above DSPMAP_COST_MAX_WEIGHT, costs that change with time (a schedule as dspmap_build_reach_fields has), more
+ *    than one workgroup per field, 26-connected or any-angle costs. */
+#define DSPMAP_COST_MAX_BANDS 4
+#define DSPMAP_COST_MAX_WEIGHT 8
+#define DSPMAP_COST_MAX_FIELDS 64
+#define DSPMAP_COST_MAX_COST 16384
+#define DSPMAP_COST_UNREACHED 65535
+typedef struct dspmap_cost_bands {
+    int n_bands;
+    float clearance[4];   /* metres, the unit of the distance field */
+    int penalty[4];
+} dspmap_cost_bands;   /* 36 bytes */
+/* grow n_fields fields from src_host[0 .. n_src) in the layer t selects; synchronous */
+int dspmap_build_cost_fields(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src_host, float t, const dspmap_cost_bands* bands,
+                             int max_cost, int flags);
+/* the same on a device array (src_dev: n_src x 16 B; bands stays host memory and goes by value into the launch); enqueued on the handle's
+ * stream, no synchronisation */
+int dspmap_build_cost_fields_device(dspmap_t* m, int n_fields, int n_src, const dspmap_reach_point* src_dev, float t, const dspmap_cost_bands* bands,
+                                    int max_cost, int flags);
+/* device address of the [n_fields][V] uint16 values of the last build; NULL if there is none or it is stale */
+const unsigned short* dspmap_cost_fields_device(dspmap_t* m);
+/* out_host[0 .. V) = the values of one field of the last build; synchronous */
+int dspmap_get_cost_field(dspmap_t* m, int field, unsigned short* out_host);
+/* device address of the [V] uint8 weights of the last build (0 blocked, else w); NULL if there is none or it is stale */
+const unsigned char* dspmap_cost_weights_device(dspmap_t* m);
+/* out_host[0 .. V) = the weights of the last build; synchronous */
+int dspmap_get_cost_weights(dspmap_t* m, unsigned char* out_host);
+/* paths of n starts down the last build: cost_out[n], cells_out[n * max_len] (may be NULL when max_len == 0); synchronous */
+int dspmap_cost_paths(dspmap_t* m, int n, const dspmap_reach_point* start_host, int max_len, int flags, int* cost_out_host, int* cells_out_host);
+/* the same on device arrays; enqueued on the handle's stream, no synchronisation */
+int dspmap_cost_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start_dev, int max_len, int flags, int* cost_out_dev, int* cells_out_dev);
+/* test hook, the twin of dspmap_debug_set_cast_grid: replace all [L][V] floats of the VALID distance field.  A NULL pointer or a value that
+ * is NaN, negative or infinite is DSPMAP_E_ARG, no valid field DSPMAP_E_STATE.  The field stays valid; cost fields built before the call
+ * are stale.  Synchronous. */
+int dspmap_debug_set_distance_field(dspmap_t* m, const float* layers_host);
+
 /* ---- occupancy forecast at caller-chosen times from the live particle set (no counterpart in the reference, whose horizons are the
  * PREDICTION_TIMES it was compiled with; everything above snaps a time t to the next configured horizon k(t), and the future status is a
  * by-product of the resampling loop: taken from the weights before resampling, without the particles born in that frame (:944), kept in
