@@ -121,6 +121,11 @@ FORECAST_LERP = 2            # DSPMAP_FORECAST_LERP
 VIEW_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("qw", "f4"), ("qx", "f4"), ("qy", "f4"), ("qz", "f4"), ("max_range", "f4"), ("t", "f4")])
 VIEW_SCORE_DTYPE = np.dtype([("n_seen", "i4"), ("n_unknown", "i4"), ("n_returns", "i4"), ("status", "i4")])
 VIEW_OK, VIEW_BLOCKED, VIEW_OUTSIDE, VIEW_INVALID = 0, 1, 3, 4
+# dspmap_view_set_score (dspmap_score_view_sets), dspmap_view_pick (dspmap_select_views) and their limits
+VIEW_SET_SCORE_DTYPE = np.dtype([("n_seen", "i4"), ("n_unknown", "i4"), ("n_ok", "i4"), ("reserved", "i4")])
+VIEW_PICK_DTYPE = np.dtype([("view", "i4"), ("gain", "i4"), ("covered", "i4"), ("reserved", "i4")])
+VIEW_MAX_PICKS = 64                 # DSPMAP_VIEW_MAX_PICKS
+VIEW_MASK_MAX_BYTES = 1 << 30       # DSPMAP_VIEW_MASK_MAX_BYTES
 # dspmap_frontier_block (dspmap_build_frontiers)
 FRONTIER_BLOCK_DTYPE = np.dtype([("block", "i4"), ("count", "i4"), ("sum_x", "i4"), ("sum_y", "i4"), ("sum_z", "i4"), ("unknown_faces", "i4")])
 FRONTIER_MAX_BLOCK = 32
@@ -223,6 +228,10 @@ SIGNATURES = {
     "dspmap_get_view": (_i, [_P, _P, _P, _P]),
     "dspmap_score_views": (_i, [_P, _i, _P, _i, _i, _P]),
     "dspmap_score_views_device": (_i, [_P, _i, _P, _i, _i, _P]),
+    "dspmap_score_view_sets": (_i, [_P, _i, _i, _P, _i, _i, _P, _P]),
+    "dspmap_score_view_sets_device": (_i, [_P, _i, _i, _P, _i, _i, _P, _P]),
+    "dspmap_select_views": (_i, [_P, _i, _P, _i, _i, _i, _i, _i, _P, _P]),
+    "dspmap_select_views_device": (_i, [_P, _i, _P, _i, _i, _i, _i, _i, _P, _P]),
     "dspmap_view_rays": (_i, [_P, _P, _P, _P, _P]),
     "dspmap_debug_view_cells": (_i, [_P, _P, _i, _P, _P]),
     "dspmap_build_frontiers": (_i, [_P, _f, _i, _i, _i, _i]),
@@ -1243,6 +1252,70 @@ class DSPMap:
         out = np.zeros(n, VIEW_SCORE_DTYPE)
         self._chk(self.L.dspmap_score_views(self.h, n, _ptr(q), int(max_age), flags, _ptr(out)))
         return out
+
+    # -- joint gain of views (extension; semantics in include/dspmap.h next to dspmap_score_view_sets)
+    def score_view_sets(self, views, max_age, world=False, scores=False):
+        """what every SET of views sees together: views [n_sets, set_size, 9] float32 -> per set the voxels in the union of the members'
+        seen sets (n_seen), those of them that are unknown (n_unknown) and the members whose status is VIEW_OK (n_ok); a short set is
+        padded with views whose max_range is 0.  scores=True: also every view's score_views score.  numpy in -> structured numpy
+        (VIEW_SET_SCORE_DTYPE [n_sets], and VIEW_SCORE_DTYPE [n_sets, set_size]) out, synchronous; a torch tensor on the GPU -> int32
+        tensors [n_sets, 4] (and [n_sets, set_size, 4]) on the same device, enqueued on the handle's stream and ordered with torch's
+        current stream like score_views."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(views):
+            import torch
+            q = self._device_samples(views, (9,), "score_view_sets")
+            if q.dim() != 3:
+                raise ValueError("score_view_sets: views of shape [n_sets, set_size, 9]")
+            ns, sz = int(q.shape[0]), int(q.shape[1])
+            out = torch.empty((ns, 4), dtype=torch.int32, device=q.device)
+            sc = torch.empty((ns, sz, 4), dtype=torch.int32, device=q.device) if scores else None
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_score_view_sets_device(self.h, ns, sz, q.data_ptr(), int(max_age), flags, out.data_ptr(),
+                                                           sc.data_ptr() if scores else None))
+            after()
+            return (out, sc) if scores else out
+        q = np.ascontiguousarray(views, np.float32)
+        if q.ndim != 3 or q.shape[-1] != 9:
+            raise ValueError("score_view_sets: views of shape [n_sets, set_size, 9]")
+        ns, sz = q.shape[:2]
+        out = np.zeros(ns, VIEW_SET_SCORE_DTYPE)
+        sc = np.zeros((ns, sz), VIEW_SCORE_DTYPE) if scores else None
+        self._chk(self.L.dspmap_score_view_sets(self.h, ns, sz, _ptr(q), int(max_age), flags, _ptr(out), _ptr(sc) if scores else None))
+        return (out, sc) if scores else out
+
+    def select_views(self, views, k, max_age, n_fixed=0, min_gain=1, world=False, scores=False):
+        """the greedy choice of k of the views [n, 9] float32 that see the most unknown space TOGETHER: views [0, n_fixed) are committed
+        already, every round picks the candidate of [n_fixed, n) that adds the most unknown voxels to what is covered (the smallest
+        index among equals) until a round's best adds fewer than min_gain; VIEW_PICK_DTYPE [k] {view, gain, covered}, view = -1 from
+        the first empty round on.  scores=True: also every view's score_views score [n].  numpy in -> structured numpy out,
+        synchronous; a torch tensor on the GPU -> int32 tensors [k, 4] (and [n, 4]) on the same device, every round enqueued on the
+        handle's stream without a host read in between, ordered with torch's current stream like score_views."""
+        flags = QUERY_WORLD if world else 0
+        if self._is_device_tensor(views):
+            import torch
+            q = self._device_samples(views, (9,), "select_views")
+            if q.dim() != 2:
+                raise ValueError("select_views: views of shape [n, 9]")
+            n = int(q.shape[0])
+            out = torch.empty((max(int(k), 0), 4), dtype=torch.int32, device=q.device)
+            sc = torch.empty((n, 4), dtype=torch.int32, device=q.device) if scores else None
+            before, after = self._handle_stream_order(q.device)
+            before()
+            self._chk(self.L.dspmap_select_views_device(self.h, n, q.data_ptr(), int(n_fixed), int(max_age), flags, int(k), int(min_gain),
+                                                        out.data_ptr(), sc.data_ptr() if scores else None))
+            after()
+            return (out, sc) if scores else out
+        q = np.ascontiguousarray(views, np.float32)
+        if q.ndim != 2 or q.shape[1] != 9:
+            raise ValueError("select_views: views of shape [n, 9]")
+        n = q.shape[0]
+        out = np.zeros(max(int(k), 0), VIEW_PICK_DTYPE)
+        sc = np.zeros(n, VIEW_SCORE_DTYPE) if scores else None
+        self._chk(self.L.dspmap_select_views(self.h, n, _ptr(q), int(n_fixed), int(max_age), flags, int(k), int(min_gain), _ptr(out),
+                                             _ptr(sc) if scores else None))
+        return (out, sc) if scores else out
 
     def view_rays(self, quat):
         """(planes_h [np_h + 1, 3], planes_v [np_v + 1, 3], dirs [NP, 3]) of an attitude (w, x, y, z): the rotated boundary-plane normals a

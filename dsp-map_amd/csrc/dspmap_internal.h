@@ -72,6 +72,12 @@ struct LayerState {
     // with the device state.  vw_chunks: DSPMAP_P_VIEW_CHUNKS
     float* vw_dirs0 = nullptr;
     int vw_chunks = 0;
+    // joint gain of views (dspmap_score_view_sets, dspmap_select_views): one seen-set mask [nz * ny * W] per view of the call, and what
+    // is small beside them in ONE allocation -- the grids UNK and avail, the fixed views' set score, the per-view scores and the
+    // candidates' gains (view_sel_scratch in dspmap_layers.hip); allocated by the first call, grown on demand after the stream has
+    // drained, freed with the device state
+    u64* vs_masks = nullptr; size_t vs_masks_words = 0;
+    char* vs_aux = nullptr; size_t vs_aux_bytes = 0;
     // frontiers (dspmap_build_frontiers): the bit grid [nz][ny][W], the cell list [V], the counts {n_cells, n_blocks, n_free} and the
     // per-word free counts, allocated by the first build; the blocks' accumulators and records [fr_nb_cap] each and the compaction's tile
     // scratch, allocated by the first build and again when a smaller block needs more; all freed with the device state.  fr_valid: a

@@ -343,6 +343,20 @@ void launch_view_score(const MapDims& d, const DevState& s, hipStream_t stream, 
                        struct dspmap_view_score* out, u64* dbg_words, float* dbg_ml);
 // out: planes_h [(np_h + 1) * 3], planes_v [(np_v + 1) * 3], dirs [np * 3] of attitude q, consecutively
 void launch_view_rays(const MapDims& d, const DevState& s, hipStream_t stream, const ViewArgs& a, const float q[4], float* out);
+// joint gain of views (dspmap_viewsel.hip; semantics in include/dspmap.h, dspmap_score_view_sets).  lw: the words of a layer, nz * ny * W
+// launch_view_score, and every view's seen set into masks [n][lw], CLEARED by the caller (only non-zero words are stored)
+void launch_view_masks(const MapDims& d, const DevState& s, hipStream_t stream, const ViewArgs& a, int n, int chunks, const struct dspmap_view* views,
+                       struct dspmap_view_score* out, u64* masks);
+struct dspmap_view_set_score;
+struct dspmap_view_pick;
+int viewsel_chunks(int lw, int n, int n_cu, int forced);   // workgroups per set / candidate for a batch of n (forced > 0: that many, capped)
+void launch_viewsel_unknown(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, u64* unk);   // unk [lw]: bit = age -1 or > max_age
+// out [n_sets] zeroed by the caller; avail (NULL, or [lw] with n_sets == 1): unk & ~union
+void launch_viewsel_sets(hipStream_t stream, int lw, int n_sets, int set_size, int chunks, const u64* masks, const u64* unk,
+                         const struct dspmap_view_score* scores, struct dspmap_view_set_score* out, u64* avail);
+// round r of the greedy selection among views [n_fixed, n_fixed + n_cand): gain (zero on entry, zero on exit), picks[r], avail &= ~picked mask
+void launch_viewsel_round(hipStream_t stream, int lw, int n_fixed, int n_cand, int chunks, int r, int min_gain, const u64* masks, u64* avail,
+                          int* gain, const struct dspmap_view_set_score* fixed, struct dspmap_view_pick* picks);
 // frontier cells and blocks (dspmap_frontier.hip; semantics in include/dspmap.h, dspmap_build_frontiers).  As the known-space launchers: the
 // dimensions and the stream, no LaunchCtx
 struct dspmap_frontier_block;

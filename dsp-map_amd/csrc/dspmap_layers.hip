@@ -1,5 +1,5 @@
 // dspmap_layers.hip -- host side of the planning layers that read the map: point and trajectory queries, distance fields, the cast grid with
-// segment casts and free boxes, arrival-time fields with timeline and paths, shortened paths, cost-to-go fields, the forecast, the known-space layer, view scores and frontiers.
+// segment casts and free boxes, arrival-time fields with timeline and paths, shortened paths, cost-to-go fields, the forecast, the known-space layer, view scores, view sets and selection, and frontiers.
 // Their kernels are in a file each (named per section); their state is LayerState (dspmap_internal.h), and what makes a snapshot stale is
 // decided in ONE place, dspmap_layers_stale next to it.  An entry point that takes host arrays is: check -> stage -> enqueue -> read back,
 // around the same *_enqueue its _device twin calls.  Checks fire in this order: arguments, slab and state, then the device.
@@ -1127,6 +1127,167 @@ extern "C" int dspmap_debug_view_cells(dspmap_t* m, const dspmap_view* view, int
     return stage_end(m, s, 4);
 }
 
+// --------------------------------------------------- joint gain of views (dspmap_viewsel.hip; semantics in include/dspmap.h)
+// what both calls check behind their own counts, in view_check's order: max_age, flags, the byte cap of the masks; then the state
+static int view_sel_check(dspmap* m, const char* what, long long n, int max_age, int flags) {
+    if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative max_age %d", what, max_age);
+    int rc = flags_check(m, what, flags, DSPMAP_QUERY_WORLD);
+    if (rc != DSPMAP_OK) return rc;
+    const unsigned long long mask = (unsigned long long)cast_layer_words(m->d) * sizeof(u64);   // (> 0)
+    if ((unsigned long long)n > DSPMAP_VIEW_MASK_MAX_BYTES / mask)   // (a division: n * mask is formed only where it is known to be small)
+        return dspmap_fail(m, DSPMAP_E_ARG, "%s: the masks of %lld views take %llu bytes, more than DSPMAP_VIEW_MASK_MAX_BYTES = %llu", what, n,
+                           (unsigned long long)n > ~0ull / mask ? ~0ull : (unsigned long long)n * mask, (unsigned long long)DSPMAP_VIEW_MASK_MAX_BYTES);
+    if ((rc = whole_map_check(m, what, "a view crosses slabs")) != DSPMAP_OK) return rc;
+    if ((rc = cast_grid_ready(m, what)) != DSPMAP_OK) return rc;
+    if (!m->ly.kn_stamp || !m->ly.kn_integrated)
+        return dspmap_fail(m, DSPMAP_E_STATE, "%s: no frame has been integrated into the known-space layer (dspmap_known_integrate)", what);
+    return DSPMAP_OK;
+}
+static int view_sets_check(dspmap* m, int n_sets, int set_size, const void* views, int max_age, int flags, const void* out) {
+    const char* what = "dspmap_score_view_sets";
+    if (!m) return DSPMAP_E_ARG;
+    if (n_sets < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative set count %d", what, n_sets);
+    if (n_sets > 0 && (!views || !out)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL view or output array", what);
+    if (n_sets > 0 && set_size < 1) return dspmap_fail(m, DSPMAP_E_ARG, "%s: %d views per set", what, set_size);
+    const long long n = (long long)n_sets * (n_sets > 0 ? set_size : 0);
+    if (n > 0x7fffffffll) return dspmap_fail(m, DSPMAP_E_ARG, "%s: %d x %d views exceed INT_MAX", what, n_sets, set_size);
+    return view_sel_check(m, what, n, max_age, flags);
+}
+static int view_select_check(dspmap* m, int n, const void* views, int n_fixed, int max_age, int flags, int k, int min_gain, const void* picks) {
+    const char* what = "dspmap_select_views";
+    if (!m) return DSPMAP_E_ARG;
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative view count %d", what, n);
+    if ((n > 0 && !views) || (k > 0 && !picks)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL view or pick array", what);
+    if (n_fixed < 0 || n_fixed > n) return dspmap_fail(m, DSPMAP_E_ARG, "%s: n_fixed %d outside [0, %d]", what, n_fixed, n);
+    if (k < 0 || k > DSPMAP_VIEW_MAX_PICKS) return dspmap_fail(m, DSPMAP_E_ARG, "%s: k %d outside [0, %d]", what, k, DSPMAP_VIEW_MAX_PICKS);
+    if (min_gain < 1) return dspmap_fail(m, DSPMAP_E_ARG, "%s: min_gain %d below 1", what, min_gain);
+    return view_sel_check(m, what, n, max_age, flags);
+}
+// the scratch of a call with n views: the masks, and behind them in one allocation (256-byte aligned sections, in this order)
+struct ViewSelScratch { u64* masks; u64* unk; u64* avail; dspmap_view_set_score* fixed; dspmap_view_score* scores; int* gain; };
+static int view_sel_scratch(dspmap* m, int n, ViewSelScratch* s) {
+    LayerState& l = m->ly;
+    const size_t lw = cast_layer_words(m->d);
+    const size_t words = (size_t)n * lw;
+    const size_t o_avail = q_align(sizeof(u64) * lw), o_fixed = o_avail + q_align(sizeof(u64) * lw), o_scores = o_fixed + q_align(sizeof(dspmap_view_set_score));
+    const size_t o_gain = o_scores + q_align(sizeof(dspmap_view_score) * (size_t)n), bytes = o_gain + q_align(sizeof(int) * (size_t)n + sizeof(int));
+    if (words > l.vs_masks_words || bytes > l.vs_aux_bytes) HIPCHK(m, hipStreamSynchronize(m->stream));   // (an earlier call may still use them)
+    // (half as much again, as query_buf: a batch that creeps up does not drain the stream every time; the masks never beyond their cap)
+    if (words > l.vs_masks_words) {
+        if (l.vs_masks) { HIPCHK(m, hipFree(l.vs_masks)); l.vs_masks = nullptr; l.vs_masks_words = 0; }
+        const size_t most = (size_t)(DSPMAP_VIEW_MASK_MAX_BYTES / sizeof(u64));
+        size_t cap = words + words / 2;
+        if (cap > most) cap = most;   // (words <= most: view_sel_check)
+        HIPCHK(m, hipMalloc(&l.vs_masks, sizeof(u64) * cap));
+        l.vs_masks_words = cap;
+    }
+    if (bytes > l.vs_aux_bytes) {
+        if (l.vs_aux) { HIPCHK(m, hipFree(l.vs_aux)); l.vs_aux = nullptr; l.vs_aux_bytes = 0; }
+        const size_t cap = bytes + bytes / 2;
+        HIPCHK(m, hipMalloc(&l.vs_aux, cap));
+        l.vs_aux_bytes = cap;
+    }
+    s->masks = l.vs_masks;
+    s->unk = (u64*)l.vs_aux; s->avail = (u64*)(l.vs_aux + o_avail);
+    s->fixed = (dspmap_view_set_score*)(l.vs_aux + o_fixed);
+    s->scores = (dspmap_view_score*)(l.vs_aux + o_scores);
+    s->gain = (int*)(l.vs_aux + o_gain);
+    return DSPMAP_OK;
+}
+// the masks and scores of n views and UNK.  ds: the caller's scores [n], or NULL for the scratch's; *scores: where they are.  The masks
+// are cleared first: k_view_score stores the non-zero words only (dspmap_view.hip says why)
+static int view_masks_enqueue(dspmap* m, const ViewArgs& a, int n, const dspmap_view* dv, dspmap_view_score* ds, ViewSelScratch* s,
+                              dspmap_view_score** scores) {
+    const int rc = view_sel_scratch(m, n, s);
+    if (rc != DSPMAP_OK) return rc;
+    *scores = ds ? ds : s->scores;
+    if (n > 0) {
+        HIPCHK(m, hipMemsetAsync(s->masks, 0, sizeof(u64) * (size_t)n * cast_layer_words(m->d), m->stream));
+        HIPCHK(m, hipMemsetAsync(*scores, 0, sizeof(dspmap_view_score) * (size_t)n, m->stream));
+        launch_view_masks(m->d, m->s, m->stream, a, n, view_chunks(m->d, n, m->n_cu, m->ly.vw_chunks), dv, *scores, s->masks);
+    }
+    launch_viewsel_unknown(m->d, m->stream, a.kn, a.max_age, s->unk);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+// (the caller has filled the arguments, as for view_score_enqueue)
+static int view_sets_enqueue(dspmap* m, const ViewArgs& a, int n_sets, int set_size, const dspmap_view* dv, dspmap_view_set_score* dout,
+                             dspmap_view_score* ds) {
+    ViewSelScratch s;
+    dspmap_view_score* scores;
+    const int rc = view_masks_enqueue(m, a, n_sets * set_size, dv, ds, &s, &scores);
+    if (rc != DSPMAP_OK) return rc;
+    const int lw = (int)cast_layer_words(m->d);
+    HIPCHK(m, hipMemsetAsync(dout, 0, sizeof(dspmap_view_set_score) * (size_t)n_sets, m->stream));
+    launch_viewsel_sets(m->stream, lw, n_sets, set_size, viewsel_chunks(lw, n_sets, m->n_cu, m->ly.vw_chunks), s.masks, s.unk, scores, dout, nullptr);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+// all k rounds are enqueued, whatever they pick: nothing is read back between them
+static int view_select_enqueue(dspmap* m, const ViewArgs& a, int n, const dspmap_view* dv, int n_fixed, int k, int min_gain, dspmap_view_pick* dp,
+                               dspmap_view_score* ds) {
+    ViewSelScratch s;
+    dspmap_view_score* scores;
+    const int rc = view_masks_enqueue(m, a, n, dv, ds, &s, &scores);
+    if (rc != DSPMAP_OK) return rc;
+    if (k == 0) return DSPMAP_OK;
+    const int lw = (int)cast_layer_words(m->d), n_cand = n - n_fixed;
+    HIPCHK(m, hipMemsetAsync(s.fixed, 0, sizeof(dspmap_view_set_score), m->stream));
+    HIPCHK(m, hipMemsetAsync(s.gain, 0, sizeof(int) * (size_t)n_cand + sizeof(int), m->stream));
+    launch_viewsel_sets(m->stream, lw, 1, n_fixed, viewsel_chunks(lw, 1, m->n_cu, m->ly.vw_chunks), s.masks, s.unk, scores, s.fixed, s.avail);
+    const int chunks = viewsel_chunks(lw, n_cand, m->n_cu, m->ly.vw_chunks);
+    for (int r = 0; r < k; ++r) launch_viewsel_round(m->stream, lw, n_fixed, n_cand, chunks, r, min_gain, s.masks, s.avail, s.gain, s.fixed, dp);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_score_view_sets(dspmap_t* m, int n_sets, int set_size, const dspmap_view* views, int max_age, int flags,
+                                      dspmap_view_set_score* out, dspmap_view_score* scores_out) {
+    int rc = view_sets_check(m, n_sets, set_size, views, max_age, flags, out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n_sets == 0) return DSPMAP_OK;
+    ViewArgs a;
+    if ((rc = view_args(m, max_age, flags, &a)) != DSPMAP_OK) return rc;
+    const size_t n = (size_t)n_sets * set_size;
+    StageSec s[3] = {{views, nullptr, sizeof(dspmap_view) * n}, {nullptr, out, sizeof(dspmap_view_set_score) * (size_t)n_sets},
+                     {nullptr, scores_out, scores_out ? sizeof(dspmap_view_score) * n : 0}};   // (no scores asked for: the scratch holds them)
+    if ((rc = stage_begin(m, s, 3)) != DSPMAP_OK) return rc;
+    if ((rc = view_sets_enqueue(m, a, n_sets, set_size, (const dspmap_view*)s[0].dev, (dspmap_view_set_score*)s[1].dev, (dspmap_view_score*)s[2].dev)) != DSPMAP_OK)
+        return rc;
+    return stage_end(m, s, 3);
+}
+extern "C" int dspmap_score_view_sets_device(dspmap_t* m, int n_sets, int set_size, const dspmap_view* views, int max_age, int flags,
+                                             dspmap_view_set_score* out, dspmap_view_score* scores_out) {
+    int rc = view_sets_check(m, n_sets, set_size, views, max_age, flags, out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n_sets == 0) return DSPMAP_OK;
+    ViewArgs a;
+    if ((rc = view_args(m, max_age, flags, &a)) != DSPMAP_OK) return rc;
+    return view_sets_enqueue(m, a, n_sets, set_size, views, out, scores_out);
+}
+extern "C" int dspmap_select_views(dspmap_t* m, int n, const dspmap_view* views, int n_fixed, int max_age, int flags, int k, int min_gain,
+                                   dspmap_view_pick* picks_out, dspmap_view_score* scores_out) {
+    int rc = view_select_check(m, n, views, n_fixed, max_age, flags, k, min_gain, picks_out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0 && k == 0) return DSPMAP_OK;
+    ViewArgs a;
+    if ((rc = view_args(m, max_age, flags, &a)) != DSPMAP_OK) return rc;
+    StageSec s[3] = {{views, nullptr, sizeof(dspmap_view) * (size_t)n}, {nullptr, picks_out, sizeof(dspmap_view_pick) * (size_t)k},
+                     {nullptr, scores_out, scores_out ? sizeof(dspmap_view_score) * (size_t)n : 0}};
+    if ((rc = stage_begin(m, s, 3)) != DSPMAP_OK) return rc;
+    if ((rc = view_select_enqueue(m, a, n, (const dspmap_view*)s[0].dev, n_fixed, k, min_gain, (dspmap_view_pick*)s[1].dev, (dspmap_view_score*)s[2].dev)) != DSPMAP_OK)
+        return rc;
+    return stage_end(m, s, 3);
+}
+extern "C" int dspmap_select_views_device(dspmap_t* m, int n, const dspmap_view* views, int n_fixed, int max_age, int flags, int k, int min_gain,
+                                          dspmap_view_pick* picks_out, dspmap_view_score* scores_out) {
+    int rc = view_select_check(m, n, views, n_fixed, max_age, flags, k, min_gain, picks_out);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0 && k == 0) return DSPMAP_OK;
+    ViewArgs a;
+    if ((rc = view_args(m, max_age, flags, &a)) != DSPMAP_OK) return rc;
+    return view_select_enqueue(m, a, n, views, n_fixed, k, min_gain, picks_out, scores_out);
+}
+
 // --------------------------------------------------- frontier cells and blocks (dspmap_frontier.hip; semantics in include/dspmap.h)
 // the layer t selects: the host twin of q_horizon (dspmap_device.h) + 1.  (t is not NaN here.)
 static int frontier_layer_host(const MapDims& d, float t) {
@@ -1720,7 +1881,7 @@ extern "C" int dspmap_debug_set_distance_field(dspmap_t* m, const float* layers)
 void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const char*)>& chk) {
     const LayerState& l = m->ly;
     for (void* q : {(void*)l.q_buf, (void*)l.df_field, (void*)l.df_g8, (void*)l.df_h16, (void*)l.cg_bits, (void*)l.cg_tmp, (void*)l.rf_field,
-                    (void*)l.rf_sets, (void*)l.tl_hist, (void*)l.tl_last, (void*)l.cf_field, (void*)l.cf_sets, (void*)l.cf_weight, (void*)l.cf_wk, (void*)l.cf_occ, (void*)l.fc_field, (void*)l.fc_acc, (void*)l.kn_stamp, (void*)l.vw_dirs0,
+                    (void*)l.rf_sets, (void*)l.tl_hist, (void*)l.tl_last, (void*)l.cf_field, (void*)l.cf_sets, (void*)l.cf_weight, (void*)l.cf_wk, (void*)l.cf_occ, (void*)l.fc_field, (void*)l.fc_acc, (void*)l.kn_stamp, (void*)l.vw_dirs0, (void*)l.vs_masks, (void*)l.vs_aux,
                     (void*)l.fr_grid, (void*)l.fr_cells, (void*)l.fr_counts, (void*)l.fr_item_free, (void*)l.fr_dense, (void*)l.fr_blocks,
                     (void*)l.fr_tiles, (void*)l.ob_parent, (void*)l.ob_root, (void*)l.ob_labels, (void*)l.ob_tiles, (void*)l.ob_counts,
                     (void*)l.ob_objects, (void*)l.tk_labels, (void*)l.tk_objects, (void*)l.tk_tracks[0], (void*)l.tk_tracks[1], (void*)l.tk_shift,

@@ -16,6 +16,13 @@
 //                  wedge leaves after four dot products.  Seen cells are counted with ballots; the age is read only by seen lanes.
 //                  Tail: one LDS reduction, then one integer atomic per workgroup and non-zero counter into the zero-initialised score.
 //                  All counts are integers of exactly defined predicates: the result does not depend on the chunking.
+//                  MASK instantiation (dspmap_score_view_sets / dspmap_select_views, dspmap_viewsel.hip): the same kernel, and lane 0 of
+//                  every wave stores the ballot of `seen` -- which IS the word of the view's seen set in the cast grid's layout -- into
+//                  the view's mask [nz][ny][W].  Only non-zero words are stored: the caller CLEARS all masks first (one hipMemsetAsync).
+//                  Storing zeros in the loop instead would not do: the loop walks the box of max_range only, a view that is not OK never
+//                  reaches it, and a wave that leaves at the wedge test would need a store of its own -- all words outside the box
+//                  would want a second loop over the whole layer per view, with its index arithmetic, where the memset writes the same
+//                  bytes at the full rate of the memory and knows nothing of views.
 //   k_view_rays    the same rotation for one attitude, written out (dspmap_view_rays).
 // Nothing of the map, the grid or the layer is written.
 #include "dspmap_cast_walk.h"
@@ -53,7 +60,7 @@ __device__ __forceinline__ void vw_axis_box(float p, float R, float half, float 
     hi = (int)fminf(fmaxf(b, -1.f), (float)(n - 1));
 }
 
-template <bool DEBUG>
+template <bool DEBUG, bool MASK = false>
 __global__ void __launch_bounds__(VW_TPB) k_view_score(MapDims d, DevState s, ViewArgs a, int n, int chunks, const float* __restrict__ views,
                                                         int4* __restrict__ out, u64* __restrict__ dbg_words, float* __restrict__ dbg_ml) {
     __shared__ float s_ph[DSP_MAX_PLANES_H * 3];
@@ -159,6 +166,7 @@ __global__ void __launch_bounds__(VW_TPB) k_view_score(MapDims d, DevState s, Vi
             seen_n += (int)__popcll(sb);   // (every lane carries the wave's count)
             unk_n += (int)__popcll(ub);
             if (DEBUG && l == 0 && sb) dbg_words[((size_t)z * d.ny + y) * W + w] = sb;
+            if (MASK && l == 0 && sb) dbg_words[((size_t)view * d.nz * d.ny + (size_t)z * d.ny + y) * W + w] = sb;   // (dbg_words: the masks [n][nz][ny][W])
         }
     }
     // ---- tail: wave -> workgroup -> score
@@ -210,6 +218,13 @@ void launch_view_score(const MapDims& d, const DevState& s, hipStream_t stream, 
     else
         hipLaunchKernelGGL(k_view_score<false>, grid, dim3(VW_TPB), lds, stream, d, s, a, n, chunks, (const float*)views, (int4*)out, (u64*)nullptr,
                            (float*)nullptr);
+}
+
+void launch_view_masks(const MapDims& d, const DevState& s, hipStream_t stream, const ViewArgs& a, int n, int chunks, const dspmap_view* views,
+                       dspmap_view_score* out, u64* masks) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL((k_view_score<false, true>), dim3((unsigned)((long long)n * chunks)), dim3(VW_TPB), sizeof(float) * (size_t)d.np, stream, d, s, a, n,
+                       chunks, (const float*)views, (int4*)out, masks, (float*)nullptr);
 }
 
 void launch_view_rays(const MapDims& d, const DevState& s, hipStream_t stream, const ViewArgs& a, const float q[4], float* out) {

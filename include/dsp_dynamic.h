@@ -369,6 +369,20 @@ public:
     int viewRays(const float quat_wxyz[4], float* planes_h, float* planes_v, float* dirs) {
         return dspmap_view_rays(h_, quat_wxyz, planes_h, planes_v, dirs);
     }
+    /* extension: joint gain of views (dspmap_score_view_sets in dspmap.h): scoreViewSets gives, for every set of set_size views
+     * (views [n_sets][set_size]; pad a short set with views of max_range 0), the voxels its members see TOGETHER (n_seen), those of them
+     * that are unknown now (n_unknown) and its usable members (n_ok).  selectViews picks greedily k of the n views: views [0, n_fixed)
+     * are committed already, every round takes the candidate that adds the most unknown voxels to what is covered, until a round's best
+     * adds fewer than min_gain (picks[r].view = -1 from there on).  view_scores (may be NULL) receives what scoreViews gives per view.
+     * Return DSPMAP_OK or a negative error code. */
+    int scoreViewSets(int n_sets, int set_size, const dspmap_view* views, int max_age, dspmap_view_set_score* set_scores,
+                      dspmap_view_score* view_scores = nullptr, bool world = false) {
+        return dspmap_score_view_sets(h_, n_sets, set_size, views, max_age, world ? DSPMAP_QUERY_WORLD : 0, set_scores, view_scores);
+    }
+    int selectViews(int n, const dspmap_view* views, int k, int max_age, dspmap_view_pick* picks, int n_fixed = 0, int min_gain = 1,
+                    dspmap_view_score* view_scores = nullptr, bool world = false) {
+        return dspmap_select_views(h_, n, views, n_fixed, max_age, world ? DSPMAP_QUERY_WORLD : 0, k, min_gain, picks, view_scores);
+    }
     /* extension: frontiers (dspmap_build_frontiers in dspmap.h): the known cells (0 <= age <= max_age) with a clear bit in the layer t
      * selects of the cast grid and at least min_unknown unknown face neighbours, as an ascending list of voxel indices and summed over
      * blocks of block^3 voxels, whose centroids (sum / count) are where a planner puts its candidate views.  buildFrontiers enqueues;

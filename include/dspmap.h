@@ -959,6 +959,58 @@ int dspmap_score_views_device(dspmap_t* m, int n, const dspmap_view* views_dev, 
 int dspmap_view_rays(dspmap_t* m, const float quat_wxyz[4], float* planes_h_host, float* planes_v_host, float* dirs_host);
 int dspmap_debug_view_cells(dspmap_t* m, const dspmap_view* view_host, int flags, unsigned long long* words_out_host, float* ml_out_host);
 
+/* ---- joint gain of views: what a SET of views sees together, and the greedy choice of k views (no counterpart in the reference).  The
+ * scores above count every view as if it stood alone; a planner takes a path of poses, or the best few of some hundred candidates, and
+ * views that look into the same pocket of unknown space must not be counted twice.  An extension beside the frame, like the sections
+ * above: the frame path, its launch chain and the captured graph do not know about it.
+ *
+ *  Everything is an integer count of the predicates of dspmap_score_views.  For a view i with status DSPMAP_VIEW_OK, S_i is the set of
+ *  voxels dspmap_score_views counts in n_seen (step 4; the grid dspmap_debug_view_cells returns, bit for bit) and U_i = S_i n UNK, with
+ *  UNK the voxels whose age is -1 or > max_age (ages synchronised to the current position first, like every known-space entry point).  A
+ *  view that is not OK has S_i = U_i = {}.  Views of one call may select different layers through t: each view's own set is defined by
+ *  its own layer, and sets are united voxel by voxel.
+ *
+ *  - dspmap_score_view_sets: views [n_sets][set_size], dspmap_trajectory_risk's layout; a caller pads a short set with views whose
+ *    max_range is 0, which are DSPMAP_VIEW_INVALID and add nothing.  Per set: n_seen = |U S_i|, n_unknown = |U U_i| (the unions over the
+ *    set's members), n_ok = its OK views, reserved = 0.  scores_out (may be NULL) receives per view exactly what dspmap_score_views gives.
+ *  - dspmap_select_views: views [0, n_fixed) are already committed (the rest of the plan being flown): C_0 = the union of their U_i.
+ *    The candidates are [n_fixed, n).  Round r = 0 .. k - 1 computes g_i = |U_i \ C_r| for every candidate; the pick i* is the
+ *    candidate with the largest g_i, among equals the one with the smallest index.  If g_i* >= min_gain, picks[r] = {i*, g_i*,
+ *    |C_r u U_i*|, 0} and C_(r+1) = C_r u U_i*; otherwise this round and every later one give {-1, 0, |C_r|, 0}.  min_gain >= 1: a picked
+ *    view's gain is 0 afterwards, so no view is picked twice.  n == n_fixed with k > 0 gives k empty picks.  scores_out (may be NULL)
+ *    receives the n views' dspmap_score_views scores.
+ *  - the _device variants take device arrays and enqueue on the handle's stream behind the build and the frame; all k rounds are
+ *    enqueued, and nothing is read back between them.  They do not synchronise -- EXCEPT a call that has to allocate or grow the
+ *    scratch (the handle's first call, and one with more views than the scratch holds): it waits for the stream once, because an
+ *    earlier call may still use the buffers it frees.  The scratch grows to half as much again as the call needs, so batches that
+ *    creep up do not wait every time.  The others take host arrays and are synchronous.
+ *  - arguments, checked before the device is touched, DSPMAP_E_ARG with a text, in this order: a NULL handle; n_sets < 0 or n < 0; a NULL
+ *    view, set-score or pick array with a positive count; set_size < 1 with n_sets > 0; n_sets * set_size beyond INT_MAX; n_fixed
+ *    outside [0, n]; k outside [0, DSPMAP_VIEW_MAX_PICKS]; min_gain < 1; max_age < 0; flags other than DSPMAP_QUERY_WORLD; masks beyond
+ *    DSPMAP_VIEW_MASK_MAX_BYTES (below).  Then the state checks of dspmap_score_views in its order: a sharded handle, a stale or
+ *    never-built grid, a layer without an integration since its last reset (all DSPMAP_E_STATE, the same texts); there is no grid
+ *    without a usable device.  n_sets == 0, or n == 0 with k == 0, returns DSPMAP_OK and queues nothing.
+ *  - scratch: one mask of nz * ny * W 64-bit words per view in the cast grid's word layout, and a few grids of that size; allocated by
+ *    the first call, grown on demand, freed with the device state; a handle that never calls allocates nothing.  A call whose masks,
+ *    views * nz * ny * W * 8 bytes, exceed DSPMAP_VIEW_MASK_MAX_BYTES is DSPMAP_E_ARG with a text that names both numbers.  The cap is a
+ *    condition, not a measurement; a 132 x 132 x 60 map holds about 5 600 views under it, a 66 x 66 x 40 map about 25 000.  Masks
+ *    restricted to the box of the view's max_range would lift the cap; they are not built.
+ *  - read-only in every sense dspmap_score_views is: nothing goes stale, the captured frame and its parameter ring are untouched.
+ *    DSPMAP_P_VIEW_CHUNKS forces the workgroups per set and per candidate too (as given, 1 .. 64, also where that is more than the
+ *    layer has words for); no result depends on it. */
+typedef struct dspmap_view_set_score { int n_seen, n_unknown, n_ok, reserved; } dspmap_view_set_score;
+typedef struct dspmap_view_pick { int view, gain, covered, reserved; } dspmap_view_pick;
+#define DSPMAP_VIEW_MAX_PICKS 64
+#define DSPMAP_VIEW_MASK_MAX_BYTES (1ull << 30)
+int dspmap_score_view_sets(dspmap_t* m, int n_sets, int set_size, const dspmap_view* views_host /* [n_sets][set_size] */, int max_age, int flags,
+                           dspmap_view_set_score* out_host /* [n_sets] */, dspmap_view_score* scores_out_host /* [n_sets * set_size], may be NULL */);
+int dspmap_score_view_sets_device(dspmap_t* m, int n_sets, int set_size, const dspmap_view* views_dev, int max_age, int flags,
+                                  dspmap_view_set_score* out_dev, dspmap_view_score* scores_out_dev);
+int dspmap_select_views(dspmap_t* m, int n, const dspmap_view* views_host, int n_fixed, int max_age, int flags, int k, int min_gain,
+                        dspmap_view_pick* picks_out_host /* [k] */, dspmap_view_score* scores_out_host /* [n], may be NULL */);
+int dspmap_select_views_device(dspmap_t* m, int n, const dspmap_view* views_dev, int n_fixed, int max_age, int flags, int k, int min_gain,
+                               dspmap_view_pick* picks_out_dev, dspmap_view_score* scores_out_dev);
+
 /* ---- frontier cells and frontier blocks: the known-free cells that touch unknown space (no counterpart in the reference).  Every
  * exploration planner starts from the frontier; block centroids are what it turns into dspmap_view candidates, so that the loop
  * update -> known_integrate -> build_cast_grid -> build_frontiers -> score_views never leaves the device.  An extension beside the
