@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(CAST_TPB) k_cast_pack(MapDims d, DevState s, C
     const int layer = blockIdx.y;
     if (row >= d.ny * d.nz) return;   // (wave-uniform: the ballots below see whole waves)
     const int z = row / d.ny, y = row - z * d.ny;
-    const int nw = (d.nx + 63) >> 6;
+    const int nw = (int)grid_row_words(d);
     u64* out = a.bits + ((size_t)layer * d.ny * d.nz + row) * nw;
     for (int w = 0; w < nw; ++w) {
         const u64 word = df_row_word(d, s, a.thr, a.fut_zero, layer, w * 64 + lane, y, z);
@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(CAST_TPB) k_cast_pack(MapDims d, DevState s, C
 __global__ void __launch_bounds__(CAST_TPB) k_cast_inflate_xy(MapDims d, CastGridArgs a, unsigned n_words) {
     const unsigned t = blockIdx.x * CAST_TPB + threadIdx.x;
     if (t >= n_words) return;
-    const unsigned nw = (unsigned)(d.nx + 63) >> 6;
+    const unsigned nw = grid_row_words(d);
     const unsigned w = t % nw, row = t / nw;          // row = y + ny * (z + nz * layer)
     const int y = (int)(row % (unsigned)d.ny);
     const int y0 = max(y - a.r, 0), y1 = min(y + a.r, d.ny - 1);
@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(CAST_TPB) k_cast_inflate_xy(MapDims d, CastGri
     }
     u64 o = c;
     for (int sft = 1; sft <= a.r; ++sft) o |= (c << sft) | (c >> sft) | (p >> (64 - sft)) | (q << (64 - sft));
-    if (w + 1 == nw && (d.nx & 63)) o &= ~0ull >> (64 - (d.nx & 63));   // bits at x >= nx stay 0
+    if (w + 1 == nw) o &= grid_row_mask(d);           // bits at x >= nx stay 0
     a.tmp[t] = o;
 }
 
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(CAST_TPB) k_cast_inflate_xy(MapDims d, CastGri
 __global__ void __launch_bounds__(CAST_TPB) k_cast_inflate_z(MapDims d, CastGridArgs a, unsigned n_words) {
     const unsigned t = blockIdx.x * CAST_TPB + threadIdx.x;
     if (t >= n_words) return;
-    const unsigned plane = (unsigned)d.ny * ((unsigned)(d.nx + 63) >> 6);
+    const unsigned plane = GridWords(d).plane;
     const int z = (int)((t / plane) % (unsigned)d.nz);
     const int z0 = max(z - a.r, 0), z1 = min(z + a.r, d.nz - 1);
     u64 o = 0;
@@ -82,14 +82,11 @@ __global__ void __launch_bounds__(CAST_TPB) k_cast(MapDims d, CastArgs a, int n,
     const float4 A = seg[2 * (size_t)i], B = seg[2 * (size_t)i + 1];   // {ax, ay, az, ta}, {bx, by, bz, tb}
     float s = 0.f;
     int voxel = -1, layer = -1, status = DSPMAP_CAST_INVALID;
-    const bool valid = cast_finite(A.x) && cast_finite(A.y) && cast_finite(A.z) && cast_finite(B.x) && cast_finite(B.y) && cast_finite(B.z) &&
+    const bool valid = grid_finite(A.x) && grid_finite(A.y) && grid_finite(A.z) && grid_finite(B.x) && grid_finite(B.y) && grid_finite(B.z) &&
                        A.w == A.w && B.w == B.w;
     if (valid) {
         float ax = A.x, ay = A.y, az = A.z, bx = B.x, by = B.y, bz = B.z;
-        if (a.world) {
-            ax = __fsub_rn(ax, a.ox); ay = __fsub_rn(ay, a.oy); az = __fsub_rn(az, a.oz);
-            bx = __fsub_rn(bx, a.ox); by = __fsub_rn(by, a.oy); bz = __fsub_rn(bz, a.oz);
-        }
+        origin_apply(a.org, ax, ay, az, bx, by, bz);
         cast_walk(d, a.bits, ax, ay, az, A.w, bx, by, bz, B.w, s, voxel, layer, status);
     }
     out[i] = make_int4(__float_as_int(s), voxel, layer, status);
@@ -100,7 +97,7 @@ void launch_cast_grid(const LaunchCtx& c, const CastGridArgs& a) {
     const int rows = d.ny * d.nz;
     hipLaunchKernelGGL(k_cast_pack, dim3((rows + CAST_WAVES - 1) / CAST_WAVES, a.L), dim3(CAST_TPB), 0, c.stream, d, c.s, a);
     if (a.r <= 0) return;
-    const unsigned n_words = (unsigned)((size_t)a.L * rows * ((d.nx + 63) >> 6));   // (< 2^31: dspmap_build_cast_grid refuses more)
+    const unsigned n_words = (unsigned)((size_t)a.L * grid_layer_words(d));   // (< 2^31: dspmap_build_cast_grid refuses more)
     const dim3 g((n_words + CAST_TPB - 1) / CAST_TPB);
     hipLaunchKernelGGL(k_cast_inflate_xy, g, dim3(CAST_TPB), 0, c.stream, d, a, n_words);
     hipLaunchKernelGGL(k_cast_inflate_z, g, dim3(CAST_TPB), 0, c.stream, d, a, n_words);

@@ -3,9 +3,11 @@
 // same instructions, so a view's rays are casts bit for bit.
 #pragma once
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "../../include/dspmap.h"
 
-// one axis of the DDA set-up (include/dspmap.h, steps 2 and 3); pa is inside the map along this axis
+// one axis of the DDA set-up (include/dspmap.h, steps 2 and 3); pa is inside the map along this axis.  (grid_axis_cell's quotient, which
+// the walk needs unrounded as well)
 __device__ __forceinline__ void cast_axis(float pa, float pb, float half, float res, int& i, int& st, float& tmax, float& tdelta) {
     const float ua = __fdiv_rn(__fadd_rn(pa, half), res), ub = __fdiv_rn(__fadd_rn(pb, half), res);
     i = (int)ua;
@@ -19,8 +21,6 @@ __device__ __forceinline__ void cast_axis(float pa, float pb, float half, float 
         tdelta = __fdiv_rn(1.0f, fabsf(dd));
     }
 }
-__device__ __forceinline__ bool cast_finite(float v) { return fabsf(v) < INFINITY; }   // (false for NaN)
-
 
 // The cast of the map-frame segment a -> b with times ta, tb (all finite / not NaN: step 1 is the caller's) through bits [L][nz][ny][W]:
 // s, voxel, layer, status as dspmap_cast_hit names them.  At most nx + ny + nz steps.
@@ -29,7 +29,7 @@ __device__ __forceinline__ void cast_walk(const MapDims& d, const u64* __restric
     s = 0.f; voxel = -1; layer = -1;
     int ix = 0, iy = 0, iz = 0, sx = 0, sy = 0, sz = 0;
     float tmx = INFINITY, tmy = INFINITY, tmz = INFINITY, tdx = 0.f, tdy = 0.f, tdz = 0.f;
-    bool inside = !(fabsf(ax) >= d.half_x || fabsf(ay) >= d.half_y || fabsf(az) >= d.half_z);   // dspmap_point_voxel_index's test
+    bool inside = !grid_beyond(d, ax, ay, az);
     if (inside) {
         cast_axis(ax, bx, d.half_x, d.res, ix, sx, tmx, tdx);
         cast_axis(ay, by, d.half_y, d.res, iy, sy, tmy, tdy);
@@ -40,7 +40,7 @@ __device__ __forceinline__ void cast_walk(const MapDims& d, const u64* __restric
     if (inside) {
         const bool timed = !(ta < 0.f) && d.T > 0;
         const float dt = __fsub_rn(tb, ta);
-        const size_t nw = (size_t)(d.nx + 63) >> 6, rows = (size_t)d.ny * d.nz;
+        const size_t nw = (size_t)(d.nx + 63) >> 6, rows = (size_t)d.ny * d.nz;   // (the walk keeps its own 64-bit form of the word layout)
         int l_in = timed ? q_horizon(d, __fadd_rn(ta, __fmul_rn(0.f, dt))) + 1 : 0;
         size_t key = ~(size_t)0;
         u64 word = 0;

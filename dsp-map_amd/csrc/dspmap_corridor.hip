@@ -33,14 +33,12 @@
 //    to find the distinct pairs and a sort or an indirection per seed.  It would pay for batches of one time window; the entry point
 //    does not know that, and a caller who does can build its grid for that window and pass ta = tb.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 
 #define BOX_TPB 256
 #define BOX_WAVES (BOX_TPB / 64)
 #define BOX_ILP 4   // items per lane between two votes
-
-__device__ __forceinline__ int box_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ bool box_finite(float v) { return fabsf(v) < INFINITY; }   // (false for NaN)
 
 // the tested layers of a seed: [l0, l0 + nl - extra) and, if extra, layer 0 in front of them
 struct BoxLayers {
@@ -52,8 +50,8 @@ struct BoxLayers {
 __device__ __forceinline__ bool box_blocked(const MapDims& d, const u64* __restrict__ bits, int lane, int x0, int x1, int y0, int y1, int z0, int z1,
                                             const BoxLayers& ly) {
     const unsigned w0 = (unsigned)x0 >> 6, nwd = ((unsigned)x1 >> 6) - w0 + 1, nyr = (unsigned)(y1 - y0 + 1), nzr = (unsigned)(z1 - z0 + 1);
-    const unsigned nw = (unsigned)(d.nx + 63) >> 6;
-    const size_t layer_words = (size_t)d.nz * d.ny * nw;
+    const unsigned nw = grid_row_words(d);
+    const size_t layer_words = grid_layer_words(d);
     const unsigned items = nwd * nyr * nzr * (unsigned)ly.nl;   // (<= W * ny * nz * L < 2^31: dspmap_build_cast_grid refuses more)
     const u64 first = ~0ull << (x0 & 63), last = ~0ull >> (63 - (x1 & 63));
     for (unsigned base = 0; base < items; base += 64 * BOX_ILP) {
@@ -80,7 +78,7 @@ __device__ __forceinline__ bool box_blocked(const MapDims& d, const u64* __restr
 // one axis of the seed box (include/dspmap.h, step 2): both end points inside the map along it, the cells they lie in
 __device__ __forceinline__ bool box_axis(float pa, float pb, float half, float res, int n, int& lo, int& hi) {
     if (fabsf(pa) >= half || fabsf(pb) >= half) return false;   // dspmap_point_voxel_index's test (NaN-free here)
-    const int ia = (int)__fdiv_rn(__fadd_rn(pa, half), res), ib = (int)__fdiv_rn(__fadd_rn(pb, half), res);   // (both >= 0: p > -half)
+    const int ia = grid_axis_cell(pa, half, res), ib = grid_axis_cell(pb, half, res);
     lo = min(ia, ib);
     hi = max(ia, ib);
     return hi < n;
@@ -94,29 +92,26 @@ __global__ void __launch_bounds__(BOX_TPB) k_grow_boxes(MapDims d, BoxArgs a, in
     int lo[3] = {-1, -1, -1}, hi[3] = {-1, -1, -1};
     int status = DSPMAP_BOX_INVALID;
     unsigned stop = 0;
-    const bool valid = box_finite(A.x) && box_finite(A.y) && box_finite(A.z) && box_finite(B.x) && box_finite(B.y) && box_finite(B.z) &&
+    const bool valid = grid_finite(A.x) && grid_finite(A.y) && grid_finite(A.z) && grid_finite(B.x) && grid_finite(B.y) && grid_finite(B.z) &&
                        A.w == A.w && B.w == B.w;
     if (valid) {
         float ax = A.x, ay = A.y, az = A.z, bx = B.x, by = B.y, bz = B.z;
-        if (a.world) {
-            ax = __fsub_rn(ax, a.ox); ay = __fsub_rn(ay, a.oy); az = __fsub_rn(az, a.oz);
-            bx = __fsub_rn(bx, a.ox); by = __fsub_rn(by, a.oy); bz = __fsub_rn(bz, a.oz);
-        }
+        origin_apply(a.org, ax, ay, az, bx, by, bz);
         int l[3], h[3];
         bool inside = box_axis(ax, bx, d.half_x, d.res, d.nx, l[0], h[0]);
         inside = box_axis(ay, by, d.half_y, d.res, d.ny, l[1], h[1]) && inside;
         inside = box_axis(az, bz, d.half_z, d.res, d.nz, l[2], h[2]) && inside;
         status = DSPMAP_BOX_SEED_OUTSIDE;
-        if (box_uniform(inside ? 1 : 0)) {
+        if (grid_uniform(inside ? 1 : 0)) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) { lo[k] = box_uniform(l[k]); hi[k] = box_uniform(h[k]); }
+            for (int k = 0; k < 3; ++k) { lo[k] = grid_uniform(l[k]); hi[k] = grid_uniform(h[k]); }
             // the layers of cast step 4 with t_in = ta, t_out = tb: layer 0 only if ta < 0 (or T == 0, where q_horizon gives -1 for every t)
             int la = 0, lb = 0;
             if (!(A.w < 0.f)) { la = q_horizon(d, A.w) + 1; lb = q_horizon(d, B.w) + 1; }
             BoxLayers ly;
-            ly.l0 = box_uniform(min(la, lb));
+            ly.l0 = grid_uniform(min(la, lb));
             ly.extra = (a.with_current && ly.l0 > 0) ? 1 : 0;
-            ly.nl = box_uniform(max(la, lb)) - ly.l0 + 1 + ly.extra;
+            ly.nl = grid_uniform(max(la, lb)) - ly.l0 + 1 + ly.extra;
             if (box_blocked(d, a.bits, lane, lo[0], hi[0], lo[1], hi[1], lo[2], hi[2], ly)) {
                 status = DSPMAP_BOX_SEED_BLOCKED;
             } else {

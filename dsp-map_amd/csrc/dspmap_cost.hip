@@ -11,8 +11,10 @@
 // Chosen: k_cost_weights, a launch of its own ahead of the wavefront, one wave per word: a lane reads its cell's float of the distance
 // layer, the eight ballots of (w == k) ARE the words of W_1 .. W_8, and the weight byte goes out coalesced.  The weight values that occur
 // are ORed into one device word.  Then k_cost_wave, ONE WORKGROUP OF 1024 THREADS PER FIELD for every level in ONE launch, the owner-of-a-word
-// scheme and the three rotating verdict flags of k_reach (dspmap_reach.hip).  Per field the device scratch holds eleven sets: a ring of the
-// last eight GROWN level sets G_j = N6(N_j), two level sets N in ping-pong, and the settled set.  A level is
+// scheme of k_reach (dspmap_reach.hip) on the helpers both share (dspmap_grid.h: grid_cell, GridWords, grid_grow6, grid_store_bits)
+// and with its three rotating verdict flags.  The paths are launch_field_paths of dspmap_reach.hip, WEIGHTED.  Per field the
+// device scratch holds eleven sets: a ring of the last eight GROWN level sets G_j = N6(N_j), two level sets N in ping-pong, and the
+// settled set.  A level is
 //     phase A: own word only -- OR of G_{c-k}[t] & W_k[t] over the k that occur and whose ring slot is not known to be empty, and-not settled;
 //              the new bits go to N[i & 1] (i counts the levels executed), into settled, and their cells get the value c (a bit is new
 //              once, so no test of the field);
@@ -37,31 +39,17 @@
 //  - a heap or a per-cell bucket queue: serial per field, and the bit sets already are the buckets.
 //  - one launch per level: up to 16 384 launches, and the exit rule would need a read-back per level.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 
 #define COST_TPB 1024
 #define COST_W_TPB 256
-#define COST_PATH_TPB 256
-
-__device__ __forceinline__ bool cost_finite(float v) { return fabsf(v) < INFINITY; }   // (false for NaN)
-
-// the cell of a source / start point: reach_cell of dspmap_reach.hip, the rules of dspmap_build_reach_fields (0 = a cell, -2 = outside the
-// map, -3 = a non-finite coordinate)
-__device__ __forceinline__ int cost_cell(const MapDims& d, float ox, float oy, float oz, int world, float px, float py, float pz, int& x, int& y,
-                                         int& z) {
-    if (!(cost_finite(px) && cost_finite(py) && cost_finite(pz))) return -3;
-    if (world) { px = __fsub_rn(px, ox); py = __fsub_rn(py, oy); pz = __fsub_rn(pz, oz); }
-    if (fabsf(px) >= d.half_x || fabsf(py) >= d.half_y || fabsf(pz) >= d.half_z) return -2;
-    x = (int)__fdiv_rn(__fadd_rn(px, d.half_x), d.res);
-    y = (int)__fdiv_rn(__fadd_rn(py, d.half_y), d.res);
-    z = (int)__fdiv_rn(__fadd_rn(pz, d.half_z), d.res);
-    return (x < d.nx && y < d.ny && z < d.nz) ? 0 : -2;
-}
 
 // one wave per word of the layer: lane = bit = x & 63.  weight[V] bytes, wk[8][nwords] the sets W_1 .. W_8, *occ |= 1 << k for every k that occurs
 __global__ void __launch_bounds__(COST_W_TPB) k_cost_weights(MapDims d, CostWeightArgs a) {
     const unsigned lane = threadIdx.x & 63;
-    const unsigned W = (unsigned)(d.nx + 63) >> 6, nwords = (unsigned)d.nz * d.ny * W;
+    const GridWords gw(d);
+    const unsigned W = gw.W, nwords = gw.nwords;
     const unsigned t = blockIdx.x * (COST_W_TPB / 64) + (threadIdx.x >> 6);   // (the same for the whole wave)
     if (t >= nwords) return;
     const unsigned yz = t / W, w = t - yz * W, x = w * 64 + lane;
@@ -95,7 +83,8 @@ __global__ void __launch_bounds__(COST_W_TPB) k_cost_weights(MapDims d, CostWeig
 __global__ void __launch_bounds__(COST_TPB) k_cost_wave(MapDims d, CostArgs a, const float4* __restrict__ src) {
     __shared__ int s_flag[3];   // bit 0: the level is not empty
     const unsigned tid = threadIdx.x, f = blockIdx.x;
-    const unsigned W = (unsigned)(d.nx + 63) >> 6, plane = (unsigned)d.ny * W, nwords = (unsigned)d.nz * plane;   // (< 2^31: the cast grid exists)
+    const GridWords gw(d);
+    const unsigned W = gw.W, plane = gw.plane, nwords = gw.nwords;
     u64* ring = a.sets + (size_t)f * COST_SET_COUNT * nwords;
     u64* lvl = ring + (size_t)8 * nwords;
     u64* settled = ring + (size_t)10 * nwords;
@@ -110,8 +99,8 @@ __global__ void __launch_bounds__(COST_TPB) k_cost_wave(MapDims d, CostArgs a, c
         const float4 p = src[i];
         if ((unsigned)__float_as_int(p.w) != f) continue;   // (a field outside [0, n_fields) matches no workgroup)
         int x, y, z;
-        if (cost_cell(d, a.ox, a.oy, a.oz, a.world, p.x, p.y, p.z, x, y, z) != 0) continue;
-        atomicOr((unsigned long long*)&lvl[((unsigned)z * d.ny + y) * W + ((unsigned)x >> 6)], 1ull << (x & 63));
+        if (grid_cell(d, a.org, p.x, p.y, p.z, x, y, z) != 0) continue;
+        atomicOr((unsigned long long*)&lvl[gw.word_of(d, x, y, z)], GridWords::bit_of(x));
     }
     __syncthreads();
     unsigned live = 0;            // bit j: ring slot j holds a non-empty grown set (the same in every thread)
@@ -158,11 +147,7 @@ __global__ void __launch_bounds__(COST_TPB) k_cost_wave(MapDims d, CostArgs a, c
             if (fresh) {
                 verdict = 1;
                 const unsigned yz = t / W, w = t - yz * W;
-                unsigned short* cell = fld + (size_t)yz * d.nx + w * 64;
-                do {
-                    cell[__builtin_ctzll(fresh)] = (unsigned short)c;
-                    fresh &= fresh - 1;
-                } while (fresh);
+                grid_store_bits(fld + (size_t)yz * d.nx + w * 64, fresh, (unsigned short)c);
             }
         }
         if (verdict) atomicOr(&s_flag[it % 3], 1);
@@ -179,70 +164,14 @@ __global__ void __launch_bounds__(COST_TPB) k_cost_wave(MapDims d, CostArgs a, c
         u64* G = ring + (size_t)(c & 7) * nwords;
         for (unsigned t = tid; t < nwords; t += COST_TPB) {   // phase B: the grown set of this level into its slot
             const unsigned z = t / plane, r = t - z * plane, y = r / W, w = r - y * W;
-            const u64* cur = N + t;
-            const u64 n0 = cur[0];
-            u64 g = (n0 << 1) | (n0 >> 1);
-            if (w > 0) g |= cur[-1] >> 63;             // the carries of the row's neighbouring words, never across rows
-            if (w + 1 < W) g |= cur[1] << 63;
-            if (y > 0) g |= cur[-(int)W];
-            if (y + 1 < (unsigned)d.ny) g |= cur[W];
-            if (z > 0) g |= cur[-(int)plane];
-            if (z + 1 < (unsigned)d.nz) g |= cur[plane];
-            G[t] = g;                                  // (bits at x >= nx may be set here; no W_k holds them)
+            G[t] = grid_grow6<false>(N + t, N[t], w, y, z, gw, d);  // (bits at x >= nx may be set here; no W_k holds them)
         }
     }
-}
-
-// one lane per start: descent by the weight of the cell left, first neighbour of value v - w(c) in the order -x, +x, -y, +y, -z, +z
-__global__ void __launch_bounds__(COST_PATH_TPB) k_cost_paths(MapDims d, CostPathArgs a, int n, const float4* __restrict__ start,
-                                                              int* __restrict__ cost_out, int* __restrict__ cells_out) {
-    const unsigned i = blockIdx.x * COST_PATH_TPB + threadIdx.x;
-    if (i >= (unsigned)n) return;
-    const float4 p = start[i];
-    const int f = __float_as_int(p.w);
-    int x = 0, y = 0, z = 0;
-    int st = cost_cell(d, a.ox, a.oy, a.oz, a.world, p.x, p.y, p.z, x, y, z);
-    if ((unsigned)f >= (unsigned)a.n_fields) st = -3;   // (a non-finite coordinate is -3 as well; either wins over "outside")
-    const unsigned short* __restrict__ fld = a.field + (size_t)(st == 0 ? f : 0) * d.v_glob;
-    int v = 0;
-    if (st == 0) {
-        v = fld[((size_t)z * d.ny + y) * d.nx + x];
-        st = v == DSPMAP_COST_UNREACHED ? -1 : v;
-    }
-    cost_out[i] = st;
-    int* out = cells_out + (size_t)i * a.max_len;
-    int j = 0;
-    if (st >= 0) {
-        const int sy = d.nx, sz = d.nx * d.ny;
-        int g = (z * d.ny + y) * d.nx + x;
-        for (; j < a.max_len;) {                       // (bounded by max_len; v falls by at least one per cell)
-            out[j++] = g;
-            if (v == 0) break;
-            const int want = v - (int)a.weight[g];
-            // the six neighbour loads of a step are issued together: independent addresses, one wait
-            const bool ok[6] = {x > 0, x + 1 < d.nx, y > 0, y + 1 < d.ny, z > 0, z + 1 < d.nz};
-            const int off[6] = {-1, 1, -sy, sy, -sz, sz};
-            int nv[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) nv[k] = fld[g + (ok[k] ? off[k] : 0)];
-            int pick = -1;
-#pragma unroll
-            for (int k = 5; k >= 0; --k)
-                if (ok[k] && nv[k] == want) pick = k;
-            if (pick < 0) break;                       // no such neighbour (never in a field this build made): stop, the rest is -1
-            g += off[pick];
-            x += pick == 1 ? 1 : (pick == 0 ? -1 : 0);
-            y += pick == 3 ? 1 : (pick == 2 ? -1 : 0);
-            z += pick == 5 ? 1 : (pick == 4 ? -1 : 0);
-            v = want;
-        }
-    }
-    for (; j < a.max_len; ++j) out[j] = -1;
 }
 
 void launch_cost_weights(const LaunchCtx& c, const CostWeightArgs& a) {
     const MapDims& d = c.d;
-    const size_t nwords = (size_t)d.nz * d.ny * (size_t)((d.nx + 63) >> 6);
+    const size_t nwords = grid_layer_words(d);
     const unsigned per = COST_W_TPB / 64;
     hipLaunchKernelGGL(k_cost_weights, dim3((unsigned)((nwords + per - 1) / per)), dim3(COST_W_TPB), 0, c.stream, d, a);
 }
@@ -250,10 +179,4 @@ void launch_cost_weights(const LaunchCtx& c, const CostWeightArgs& a) {
 void launch_cost_wave(const LaunchCtx& c, const CostArgs& a, const dspmap_reach_point* src) {
     if (a.n_fields <= 0) return;
     hipLaunchKernelGGL(k_cost_wave, dim3(a.n_fields), dim3(COST_TPB), 0, c.stream, c.d, a, (const float4*)src);
-}
-
-void launch_cost_paths(const LaunchCtx& c, const CostPathArgs& a, int n, const dspmap_reach_point* start, int* cost_out, int* cells_out) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_cost_paths, dim3((unsigned)(((long long)n + COST_PATH_TPB - 1) / COST_PATH_TPB)), dim3(COST_PATH_TPB), 0, c.stream,
-                       c.d, a, n, (const float4*)start, cost_out, cells_out);
 }

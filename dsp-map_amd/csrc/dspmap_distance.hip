@@ -18,6 +18,7 @@
 // Lanes run along x in every pass: every global access is a run of consecutive cells, no transposes.  All L layers go in one launch per
 // pass (the layer is a grid dimension).  Nothing of the map is written.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 
 #define DF_TPB 256
@@ -32,7 +33,7 @@ __global__ void __launch_bounds__(DF_TPB) k_dist_x(MapDims d, DevState s, DistAr
     const int layer = blockIdx.y;
     if (row >= d.ny * d.nz) return;   // (wave-uniform: the ballots below see whole waves)
     const int z = row / d.ny, y = row - z * d.ny;
-    const int nw = (d.nx + 63) >> 6;
+    const int nw = (int)grid_row_words(d);
     const int cap = a.R + 1;
     unsigned char* out = a.g8 + ((size_t)layer * d.v_glob + (size_t)row * d.nx);
     u64 prev = 0, cur = df_row_word(d, s, a.thr, a.fut_zero, layer, lane, y, z);
@@ -57,7 +58,7 @@ __global__ void __launch_bounds__(DF_TPB) k_dist_axis(MapDims d, DistArgs a) {
     __shared__ unsigned short sq[(DF_TS + 2 * DF_RMAX) * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n_scan = FINAL ? d.nz : d.ny;
-    const int nxc = (d.nx + 63) >> 6;
+    const int nxc = (int)grid_row_words(d);
     const int xc = blockIdx.x % nxc, tile = blockIdx.x / nxc;
     const int oth = blockIdx.y, layer = blockIdx.z;
     const int x = xc * 64 + lane;
@@ -109,7 +110,7 @@ __global__ void __launch_bounds__(DF_TPB) k_dist_query(MapDims d, DistQueryArgs 
     float v = a.outside, gx = 0.f, gy = 0.f, gz = 0.f;
     if (!(s.x != s.x || s.y != s.y || s.z != s.z || s.w != s.w)) {
         float px = s.x, py = s.y, pz = s.z;
-        if (a.world) { px = __fsub_rn(px, a.ox); py = __fsub_rn(py, a.oy); pz = __fsub_rn(pz, a.oz); }
+        origin_apply(a.org, px, py, pz);
         int g;
         if (voxel_of(d, px, py, pz, g)) {
             const float* F = a.field + (size_t)(q_horizon(d, s.w) + 1) * d.v_glob;
@@ -143,7 +144,7 @@ __global__ void __launch_bounds__(DF_TPB) k_dist_query(MapDims d, DistQueryArgs 
 void launch_distance_field(const LaunchCtx& c, const DistArgs& a) {
     const MapDims& d = c.d;
     const int rows = d.ny * d.nz;
-    const int nxc = (d.nx + 63) / 64;
+    const int nxc = (int)grid_row_words(d);
     hipLaunchKernelGGL(k_dist_x, dim3((rows + DF_WAVES - 1) / DF_WAVES, a.L), dim3(DF_TPB), 0, c.stream, d, c.s, a);
     hipLaunchKernelGGL((k_dist_axis<false>), dim3(nxc * ((d.ny + DF_TS - 1) / DF_TS), d.nz, a.L), dim3(DF_TPB), 0, c.stream, d, a);
     hipLaunchKernelGGL((k_dist_axis<true>), dim3(nxc * ((d.nz + DF_TS - 1) / DF_TS), d.ny, a.L), dim3(DF_TPB), 0, c.stream, d, a);

@@ -13,6 +13,7 @@
 //   k_forecast_query    one thread per sample: the own voxel's value in the layer its t selects, or the fp32 interpolation of two layers.
 // Nothing of the map is written: no accumulator, no per-tile flag.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 
 #define FC_TPB 256
@@ -114,7 +115,7 @@ __global__ void __launch_bounds__(FC_TPB) k_forecast_query(MapDims d, ForecastQu
     float v = a.outside;
     if (!(s.x != s.x || s.y != s.y || s.z != s.z || s.w != s.w)) {
         float px = s.x, py = s.y, pz = s.z;
-        if (a.world) { px = __fsub_rn(px, a.ox); py = __fsub_rn(py, a.oy); pz = __fsub_rn(pz, a.oz); }
+        origin_apply(a.org, px, py, pz);
         int g;
         if (voxel_of(d, px, py, pz, g)) {
             int j = a.n;   // the smallest index with times[j] >= t

@@ -18,6 +18,7 @@
 //                      (row, x0 + lane) at base + popcount(word & lanes below); for the blocks a thread writes its record at base + rank.
 //                      Items, bits and blocks are visited in ascending order, so the lists are ascending whatever the launch.
 // No kernel waits for another workgroup: the three steps are three launches.  Nothing of the map, the grid or the layer is written.
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 #include "dspmap_block_scan.h"    // block_incl_scan_i
 #include "dspmap_known_slots.h"   // kn_cell, kn_age
@@ -36,7 +37,7 @@ __global__ void __launch_bounds__(FR_TPB) k_frontier_mark(MapDims d, FrontierArg
     const int item = (int)blockIdx.x * FR_WAVES + ((int)threadIdx.x >> 6);
     if (item >= n_items) return;   // (wave-uniform)
     const int l = lane_id();
-    const int W = (d.nx + 63) >> 6;
+    const int W = (int)grid_row_words(d);
     const int w = item % W, row = item / W, y = row % d.ny, z = row / d.ny;
     const int x0 = w * 64, x = x0 + l;
     const bool in = x < d.nx;
@@ -167,7 +168,7 @@ __global__ void __launch_bounds__(FR_TPB) k_frontier_emit(MapDims d, FrontierArg
     s_base[tid] = at;
     __syncthreads();
     const int l = lane_id(), wv = tid >> 6;
-    const int W = (d.nx + 63) >> 6;
+    const int W = (int)grid_row_words(d);
     for (int k = 0; k < 64; ++k) {
         const long long item = (long long)tile * FR_TILE + wv * 64 + k;
         if (item >= n_items) break;   // (wave-uniform)
@@ -181,7 +182,7 @@ __global__ void __launch_bounds__(FR_TPB) k_frontier_emit(MapDims d, FrontierArg
 }
 
 void launch_frontiers(const MapDims& d, hipStream_t stream, const FrontierArgs& a) {
-    const int n_items = d.nz * d.ny * ((d.nx + 63) >> 6);
+    const int n_items = (int)grid_layer_words(d);
     const int ntc = frontier_tiles(n_items), ntb = frontier_tiles(a.nb);
     const dim3 grid((unsigned)((n_items + FR_WAVES - 1) / FR_WAVES));
     if (a.merge) hipLaunchKernelGGL(k_frontier_mark<true>, grid, dim3(FR_TPB), 0, stream, d, a, n_items);

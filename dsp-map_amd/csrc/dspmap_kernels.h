@@ -1,6 +1,9 @@
 // dspmap_kernels.h -- launchers of the gfx950 kernels (host-callable).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
+
 #include "dspmap_types.h"
 
 // scratch owned by the runtime
@@ -139,10 +142,16 @@ void launch_clear_future(const LaunchCtx& c);
 void launch_future_combine(const LaunchCtx& c);  // fold the static-particle future mass into the [V][T] grid
 void launch_results_true(const LaunchCtx& c, float4* out);   // res4 (storage order) -> the reference's voxel order
 // point / trajectory queries (dspmap_query.hip; semantics in include/dspmap.h, dspmap_query_occupancy)
-struct QueryArgs {
+// the frame of a batch's samples.  It opens every argument block that takes samples (asserted next to each), so a kernel reads its other
+// arguments where it did when these were four loose fields
+struct SampleOrigin {
     float ox, oy, oz;    // subtracted from every sample when `world` is set: the sensor position of the last update (current_position :131)
     int world;
-    float r2;            // fl(r * r)
+};
+static_assert(sizeof(SampleOrigin) == 16, "SampleOrigin is the 16 bytes of the four fields it replaces");
+struct QueryArgs {
+    SampleOrigin org;
+    float r2;           // fl(r * r)
     int K;               // lattice steps either side of a sample's own lattice cell the candidate box spans; 0 = the own voxel only (r == 0)
     float outside;       // what a lattice point outside the map, a point outside it or a NaN input contributes
     int fut_zero;        // 1: a clear of the future accumulators is pending -- t >= 0 reads 0
@@ -168,8 +177,7 @@ struct DistArgs {
 };
 void launch_distance_field(const LaunchCtx& c, const DistArgs& a);
 struct DistQueryArgs {
-    float ox, oy, oz;    // as QueryArgs
-    int world;
+    SampleOrigin org;
     float outside;       // what a point outside the map or a NaN sample reads
     const float* field;  // [L][V]
 };
@@ -187,8 +195,7 @@ struct CastGridArgs {
 };
 void launch_cast_grid(const LaunchCtx& c, const CastGridArgs& a);
 struct CastArgs {
-    float ox, oy, oz;    // as QueryArgs
-    int world;
+    SampleOrigin org;
     const u64* bits;     // [L][nz][ny][W]
 };
 struct dspmap_segment;
@@ -196,8 +203,7 @@ struct dspmap_cast_hit;
 void launch_cast(const LaunchCtx& c, const CastArgs& a, int n, const struct dspmap_segment* seg, struct dspmap_cast_hit* out);
 // axis-aligned free boxes grown in the cast grid, one wave per seed (dspmap_corridor.hip; semantics in include/dspmap.h, dspmap_grow_boxes)
 struct BoxArgs {
-    float ox, oy, oz;    // as QueryArgs
-    int world;
+    SampleOrigin org;
     int with_current;    // DSPMAP_BOX_WITH_CURRENT: layer 0 is tested in addition
     int grow[3];         // max_grow per axis, 0 .. DSPMAP_BOX_MAX_GROW
     const u64* bits;     // [L][nz][ny][W]
@@ -207,8 +213,7 @@ void launch_grow_boxes(const LaunchCtx& c, const BoxArgs& a, int n, const struct
 // arrival-time fields: a space-time wavefront through the cast grid, one workgroup per field (dspmap_reach.hip; semantics in include/dspmap.h,
 // dspmap_build_reach_fields)
 struct ReachArgs {
-    float ox, oy, oz;    // as QueryArgs
-    int world;
+    SampleOrigin org;
     int with_current;    // DSPMAP_REACH_WITH_CURRENT: layer 0 is tested in addition
     int timed;           // t_start >= 0 and T > 0: step n tests layer 1 + k(t_n); otherwise every step tests layer 0
     float t_start, step_seconds;
@@ -219,15 +224,14 @@ struct ReachArgs {
     unsigned short* field;   // [n_fields][V], preset to DSPMAP_REACH_UNREACHED
     u64* sets;           // [n_fields][2][nz * ny * W] device scratch of the two wave sets, or nullptr: they live in LDS
 };
-struct ReachPathArgs {
-    float ox, oy, oz;
-    int world;
+struct FieldPathArgs {           // dspmap_reach_paths and dspmap_cost_paths: the descent through a field's values
+    SampleOrigin org;
     int n_fields, max_len;
     const unsigned short* field;
+    const unsigned char* weight; // [V] the cost build's weights: the step out of cell g is weight[g]; not read by the reach paths (step 1)
 };
 struct ReachTimelinePathArgs {   // dspmap_reach_timeline_paths: backwards through the sets a timeline build kept
-    float ox, oy, oz;
-    int world;
+    SampleOrigin org;
     int n_fields, max_len;
     int max_steps;           // of the build: a field's history has max_steps + 1 rows
     const unsigned short* field;
@@ -240,7 +244,8 @@ void reach_init_device();   // per device, once (dspmap_init_device)
 void launch_reach(const LaunchCtx& c, const ReachArgs& a, const struct dspmap_reach_point* src, u64* hist, int* last);
 void launch_reach_timeline_paths(const LaunchCtx& c, const ReachTimelinePathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out,
                                  int* cells_out);
-void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const struct dspmap_reach_point* start, int* steps_out, int* cells_out);
+// weighted: the descent by the weight of the cell left (cost paths, a.weight set); otherwise the steepest descent by 1 (reach paths)
+void launch_field_paths(const LaunchCtx& c, const FieldPathArgs& a, bool weighted, int n, const struct dspmap_reach_point* start, int* steps_out, int* cells_out);
 // clearance-weighted cost-to-go fields: a bucketed wavefront through one layer of the cast grid, one workgroup per field (dspmap_cost.hip;
 // semantics in include/dspmap.h, dspmap_build_cost_fields)
 #define COST_MAX_BANDS 4    // == DSPMAP_COST_MAX_BANDS
@@ -257,8 +262,7 @@ struct CostWeightArgs {
     int* occ;                // bit k: weight k occurs (zeroed on the stream before the launch)
 };
 struct CostArgs {
-    float ox, oy, oz;    // as QueryArgs
-    int world;
+    SampleOrigin org;
     int max_cost;
     int n_fields, n_src;
     const u64* wk;       // as CostWeightArgs
@@ -266,16 +270,8 @@ struct CostArgs {
     unsigned short* field;   // [n_fields][V], preset to DSPMAP_COST_UNREACHED
     u64* sets;           // [n_fields][COST_SET_COUNT][nz * ny * W] device scratch
 };
-struct CostPathArgs {
-    float ox, oy, oz;
-    int world;
-    int n_fields, max_len;
-    const unsigned short* field;
-    const unsigned char* weight;
-};
 void launch_cost_weights(const LaunchCtx& c, const CostWeightArgs& a);
-void launch_cost_wave(const LaunchCtx& c, const CostArgs& a, const struct dspmap_reach_point* src);
-void launch_cost_paths(const LaunchCtx& c, const CostPathArgs& a, int n, const struct dspmap_reach_point* start, int* cost_out, int* cells_out);
+void launch_cost_wave(const LaunchCtx& c, const CostArgs& a, const struct dspmap_reach_point* src);   // (the paths: launch_field_paths)
 // cell paths shortened to line-of-sight waypoints, one wave per path (dspmap_shorten.hip; semantics in include/dspmap.h, dspmap_shorten_paths)
 struct ShortenArgs {
     float cx, cy, cz;    // as QueryArgs: dspmap_voxel_center
@@ -298,8 +294,7 @@ struct ForecastArgs {
 };
 void launch_forecast(const LaunchCtx& c, const ForecastArgs& a);
 struct ForecastQueryArgs {
-    float ox, oy, oz;    // as QueryArgs
-    int world;
+    SampleOrigin org;
     int lerp;            // DSPMAP_FORECAST_LERP
     float outside;       // what a point outside the map or a NaN sample reads
     int n;
@@ -320,14 +315,13 @@ struct KnownArgs {
 void launch_known_integrate(const MapDims& d, const DevState& s, hipStream_t stream, const KnownArgs& a, int n_cu);
 void launch_known_clear(const MapDims& d, hipStream_t stream, unsigned* stamp, const int slot0[3], const int count[3]);   // per axis: slots [slot0, slot0 + count) mod n
 void launch_known_ages(const MapDims& d, hipStream_t stream, const KnownArgs& a, int* out);   // [V] ages, the reference's voxel order
-void launch_known_query(const MapDims& d, hipStream_t stream, const KnownArgs& a, int world, const float cur[3], int n, const float4* q, int* out);
+void launch_known_query(const MapDims& d, hipStream_t stream, const KnownArgs& a, const SampleOrigin& org, int n, const float4* q, int* out);
 void launch_known_count(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, u64* sums);   // sums[2], zeroed by the caller
 void launch_known_mask(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, int L, u64* bits);
 // scores of candidate viewpoints (dspmap_view.hip; semantics in include/dspmap.h, dspmap_score_views).  As the known-space launchers: the
 // dimensions and the stream, no LaunchCtx
 struct ViewArgs {
-    float ox, oy, oz;    // as QueryArgs
-    int world;
+    SampleOrigin org;
     const u64* bits;     // [L][nz][ny][W] the cast grid
     KnownArgs kn;        // the synchronised known-space layer (max_range is not read: every view brings its own)
     int max_age;         // a seen cell is unknown iff its age is -1 or > max_age
@@ -335,6 +329,10 @@ struct ViewArgs {
     const float* dirs0;  // [np][3] unrotated central direction of every pyramid
     float reach;         // fl(res * (float)(nx + ny + nz)): no ray is longer
 };
+static_assert(offsetof(QueryArgs, org) == 0 && offsetof(DistQueryArgs, org) == 0 && offsetof(CastArgs, org) == 0 && offsetof(BoxArgs, org) == 0 &&
+                  offsetof(ReachArgs, org) == 0 && offsetof(FieldPathArgs, org) == 0 && offsetof(ReachTimelinePathArgs, org) == 0 &&
+                  offsetof(CostArgs, org) == 0 && offsetof(ForecastQueryArgs, org) == 0 && offsetof(ViewArgs, org) == 0,
+              "every argument block that takes samples starts with their SampleOrigin");
 struct dspmap_view;
 struct dspmap_view_score;
 int view_chunks(const MapDims& d, int n, int n_cu, int forced);   // workgroups per view for a batch of n (forced > 0: that many, capped)
@@ -393,7 +391,7 @@ struct ObjectArgs {
     long long* counts;   // out [OBJ_COUNTS], zeroed by the caller
 };
 void launch_objects(const LaunchCtx& c, const ObjectArgs& a);
-void launch_objects_query(const LaunchCtx& c, const int* labels, int world, const float cur[3], int n, const float4* q, int* out);
+void launch_objects_query(const LaunchCtx& c, const int* labels, const SampleOrigin& org, int n, const float4* q, int* out);
 // tracks: the objects of consecutive builds associated by voxel overlap (dspmap_track.hip; semantics in include/dspmap.h, dspmap_track_update)
 struct dspmap_track;
 #define TRK_COUNTS 6     // long longs of the counts: {n_tracks, n_matched, n_born, n_ended, n_pairs, next_id}

@@ -19,6 +19,7 @@
 //                       layer (a word belongs to one wave: no atomics)
 // Nothing of the map is written.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 #include "dspmap_known_slots.h"   // kn_slot, kn_cell, kn_age
 
@@ -35,7 +36,7 @@ __global__ void __launch_bounds__(KN_TPB) k_known_integrate(MapDims d, KnownArgs
     for (int i = threadIdx.x; i < d.np; i += KN_TPB) s_ml[i] = maxlen[i];
     __syncthreads();
     const int l = lane_id();
-    const int W = (d.nx + 63) >> 6;
+    const int W = (int)grid_row_words(d);
     for (int item = (int)blockIdx.x * KN_WAVES + ((int)threadIdx.x >> 6); item < n_items; item += (int)gridDim.x * KN_WAVES) {
         const int w = item % W, row = item / W, y = row % d.ny, z = row / d.ny;   // (wave-uniform)
         const int x = w * 64 + l;
@@ -84,15 +85,15 @@ __global__ void __launch_bounds__(KN_TPB) k_known_ages(MapDims d, KnownArgs a, i
 }
 
 // One thread per sample, as k_dist_query: the cell behind the point's own voxel.  t is not read.
-__global__ void __launch_bounds__(KN_TPB) k_known_query(MapDims d, KnownArgs a, int world, float cx, float cy, float cz, int n,
-                                                         const float4* __restrict__ q, int* __restrict__ out) {
+__global__ void __launch_bounds__(KN_TPB) k_known_query(MapDims d, KnownArgs a, SampleOrigin org, int n, const float4* __restrict__ q,
+                                                         int* __restrict__ out) {
     const unsigned i = blockIdx.x * KN_TPB + threadIdx.x;
     if (i >= (unsigned)n) return;
     const float4 s = q[i];
     int age = -1;
     if (!(s.x != s.x || s.y != s.y || s.z != s.z)) {
         float px = s.x, py = s.y, pz = s.z;
-        if (world) { px = __fsub_rn(px, cx); py = __fsub_rn(py, cy); pz = __fsub_rn(pz, cz); }
+        origin_apply(org, px, py, pz);
         int g;
         if (voxel_of(d, px, py, pz, g)) {
             const int zc = d.ny * d.nx;
@@ -120,7 +121,7 @@ __global__ void __launch_bounds__(KN_TPB) k_known_mask(MapDims d, KnownArgs a, i
     const int item = (int)blockIdx.x * KN_WAVES + ((int)threadIdx.x >> 6);
     if (item >= n_items) return;   // (wave-uniform)
     const int l = lane_id();
-    const int W = (d.nx + 63) >> 6;
+    const int W = (int)grid_row_words(d);
     const int w = item % W, row = item / W, y = row % d.ny, z = row / d.ny;
     const int x = w * 64 + l;
     bool unknown = false;
@@ -137,7 +138,7 @@ __global__ void __launch_bounds__(KN_TPB) k_known_mask(MapDims d, KnownArgs a, i
 }
 
 static unsigned kn_blocks(long long n) { return (unsigned)((n + KN_TPB - 1) / KN_TPB); }
-static int kn_words(const MapDims& d) { return d.nz * d.ny * ((d.nx + 63) >> 6); }
+static int kn_words(const MapDims& d) { return (int)grid_layer_words(d); }
 
 void launch_known_integrate(const MapDims& d, const DevState& s, hipStream_t stream, const KnownArgs& a, int n_cu) {
     const int n_items = kn_words(d);
@@ -156,9 +157,9 @@ void launch_known_clear(const MapDims& d, hipStream_t stream, unsigned* stamp, c
 void launch_known_ages(const MapDims& d, hipStream_t stream, const KnownArgs& a, int* out) {
     hipLaunchKernelGGL(k_known_ages, dim3(kn_blocks(d.v_glob)), dim3(KN_TPB), 0, stream, d, a, out);
 }
-void launch_known_query(const MapDims& d, hipStream_t stream, const KnownArgs& a, int world, const float cur[3], int n, const float4* q, int* out) {
+void launch_known_query(const MapDims& d, hipStream_t stream, const KnownArgs& a, const SampleOrigin& org, int n, const float4* q, int* out) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_known_query, dim3(kn_blocks(n)), dim3(KN_TPB), 0, stream, d, a, world, cur[0], cur[1], cur[2], n, q, out);
+    hipLaunchKernelGGL(k_known_query, dim3(kn_blocks(n)), dim3(KN_TPB), 0, stream, d, a, org, n, q, out);
 }
 void launch_known_count(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, u64* sums) {
     hipLaunchKernelGGL(k_known_count, dim3(kn_blocks(d.v_glob)), dim3(KN_TPB), 0, stream, d, a, max_age, sums);

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <vector>
 
+#include "dspmap_grid.h"   // SampleOrigin's users, grid_layer_words
 #include "dspmap_internal.h"
 
 // --------------------------------------------------- checks and argument fills every layer repeats
@@ -34,11 +35,17 @@ static int snapshot_ready(dspmap* m, bool valid, const char* what, const char* m
     if (m->device >= 0) (void)hipSetDevice(m->device);
     return DSPMAP_OK;
 }
-// the origin of the samples' coordinates: the sensor position of the last update when DSPMAP_QUERY_WORLD is set (QueryArgs::ox)
-// (every kernel argument block that takes samples starts with this quartet; the blocks are separate types, hence the template)
-template <class Args> static void origin_fill(const dspmap* m, int flags, Args* a) {
-    a->world = (flags & DSPMAP_QUERY_WORLD) ? 1 : 0;
-    a->ox = m->cur_pos[0]; a->oy = m->cur_pos[1]; a->oz = m->cur_pos[2];
+// the origin of the samples' coordinates: the sensor position of the last update when DSPMAP_QUERY_WORLD is set
+static SampleOrigin origin_fill(const dspmap* m, int flags) {
+    return SampleOrigin{m->cur_pos[0], m->cur_pos[1], m->cur_pos[2], (flags & DSPMAP_QUERY_WORLD) ? 1 : 0};
+}
+// a layer's scratch buffer of at least `need` items; the caller has drained the stream (an earlier call may still read the old one)
+template <class T> static int layer_buf_grow(dspmap* m, T** p, size_t* have, size_t need) {
+    if (need <= *have) return DSPMAP_OK;
+    if (*p) { HIPCHK(m, hipFree(*p)); *p = nullptr; *have = 0; }
+    HIPCHK(m, hipMalloc(p, sizeof(T) * need));
+    *have = need;
+    return DSPMAP_OK;
 }
 
 // --------------------------------------------------- staging of the host variants' arrays (LayerState::q_buf)
@@ -100,7 +107,7 @@ static int query_check(dspmap* m, long long n, const void* in, const void* out, 
 static QueryArgs query_args(const dspmap* m, float r, int flags, float outside) {
     const MapDims& d = m->d;
     QueryArgs a;
-    origin_fill(m, flags, &a);
+    a.org = origin_fill(m, flags);
     a.r2 = r * r;
     a.K = r > 0.f ? (int)ceilf(r / d.res) + 1 : 0;   // (a superset of the footprint: one lattice step of margin for the rounding)
     a.outside = outside;
@@ -232,7 +239,7 @@ static int dist_query_check(dspmap* m, int n, const void* in, const void* out, i
 }
 static DistQueryArgs dist_query_args(const dspmap* m, int flags, float outside) {
     DistQueryArgs a;
-    origin_fill(m, flags, &a);
+    a.org = origin_fill(m, flags);
     a.outside = outside;
     a.field = m->ly.df_field;
     return a;
@@ -259,7 +266,6 @@ extern "C" int dspmap_query_distance_device(dspmap_t* m, int n, const dspmap_que
 }
 
 // --------------------------------------------------- segment casts (dspmap_cast.hip; semantics in include/dspmap.h)
-static size_t cast_layer_words(const MapDims& d) { return (size_t)d.nz * d.ny * (size_t)((d.nx + 63) >> 6); }
 extern "C" int dspmap_build_cast_grid(dspmap_t* m, float thr, int inflate_voxels, int flags) {
     if (!m) return DSPMAP_E_ARG;
     if (thr != thr) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: threshold is NaN");
@@ -269,7 +275,7 @@ extern "C" int dspmap_build_cast_grid(dspmap_t* m, float thr, int inflate_voxels
     const int rc = whole_map_check(m, "cast grid", "casts cross slabs");
     if (rc != DSPMAP_OK) return rc;
     const MapDims& d = m->d;
-    const size_t words = (size_t)(d.T + 1) * cast_layer_words(d);
+    const size_t words = (size_t)(d.T + 1) * grid_layer_words(d);
     if (words > 0x7fffffffull) return dspmap_fail(m, DSPMAP_E_STATE, "cast grid: %zu words exceed INT_MAX", words);
     READY(m);
     BENIGN(m);
@@ -298,7 +304,7 @@ extern "C" int dspmap_get_cast_grid(dspmap_t* m, int layer, unsigned long long* 
     if (layer < 0 || layer > m->d.T) return dspmap_fail(m, DSPMAP_E_ARG, "cast grid: layer %d outside [0, %d)", layer, m->d.T + 1);
     const int rc = cast_grid_ready(m, "dspmap_get_cast_grid");
     if (rc != DSPMAP_OK) return rc;
-    const size_t lw = cast_layer_words(m->d);
+    const size_t lw = grid_layer_words(m->d);
     return read_back(m, out, m->ly.cg_bits + lw * layer, sizeof(u64) * lw);
 }
 static int cast_check(dspmap* m, int n, const void* in, const void* out, int flags) {
@@ -310,7 +316,7 @@ static int cast_check(dspmap* m, int n, const void* in, const void* out, int fla
 }
 static CastArgs cast_args(const dspmap* m, int flags) {
     CastArgs a;
-    origin_fill(m, flags, &a);
+    a.org = origin_fill(m, flags);
     a.bits = m->ly.cg_bits;
     return a;
 }
@@ -349,7 +355,7 @@ static int box_check(dspmap* m, int n, const void* in, const int* max_grow, int 
 }
 static BoxArgs box_args(const dspmap* m, const int* max_grow, int flags) {
     BoxArgs a;
-    origin_fill(m, flags, &a);
+    a.org = origin_fill(m, flags);
     a.with_current = (flags & DSPMAP_BOX_WITH_CURRENT) ? 1 : 0;
     for (int k = 0; k < 3; ++k) a.grow[k] = max_grow[k];
     a.bits = m->ly.cg_bits;
@@ -405,7 +411,7 @@ static int reach_build_check(dspmap* m, int n_fields, int n_src, const void* src
     const unsigned long long cells = (unsigned long long)n_fields * (unsigned long long)m->d.v_glob;
     if (cells > 0x80000000ull) return dspmap_fail(m, DSPMAP_E_ARG, "reach fields: %d fields of %d cells exceed 2^31 cells", n_fields, m->d.v_glob);
     if (timeline) {   // (n_fields <= 64, max_steps + 1 <= 4097, a layer's words < 2^31: no overflow in 64 bits)
-        const unsigned long long bytes = (unsigned long long)n_fields * (unsigned long long)(max_steps + 1) * cast_layer_words(m->d) * sizeof(u64);
+        const unsigned long long bytes = (unsigned long long)n_fields * (unsigned long long)(max_steps + 1) * grid_layer_words(m->d) * sizeof(u64);
         if (bytes > DSPMAP_REACH_TIMELINE_MAX_BYTES)
             return dspmap_fail(m, DSPMAP_E_ARG, "reach timeline: the sets of %d fields and %d steps take %llu bytes, more than "
                                                 "DSPMAP_REACH_TIMELINE_MAX_BYTES = %llu", n_fields, max_steps + 1, bytes,
@@ -421,32 +427,21 @@ static int reach_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_po
                        int flags, bool keep = false) {
     const MapDims& d = m->d;
     dspmap_layers_stale(m->ly, LAYERS_REACH_REBUILD);
-    const size_t cells = (size_t)n_fields * d.v_glob, lw = cast_layer_words(d);
+    const size_t cells = (size_t)n_fields * d.v_glob, lw = grid_layer_words(d);
     const bool lds = 2 * sizeof(u64) * lw <= (size_t)REACH_LDS_BYTES && !(flags & DSPMAP_REACH_DEVICE_SETS);
     const size_t set_words = lds ? 0 : 2 * lw * (size_t)n_fields;
     const size_t hist_words = keep ? (size_t)n_fields * ((size_t)max_steps + 1) * lw : 0;
     if (cells > m->ly.rf_field_cells || set_words > m->ly.rf_sets_words || hist_words > m->ly.tl_hist_words || (keep && !m->ly.tl_last)) {   // grown only after the stream has drained (an earlier call may still read them)
         HIPCHK(m, hipStreamSynchronize(m->stream));
         if (!m->ly.rf_field) reach_init_device();
-        if (cells > m->ly.rf_field_cells) {
-            if (m->ly.rf_field) { HIPCHK(m, hipFree(m->ly.rf_field)); m->ly.rf_field = nullptr; m->ly.rf_field_cells = 0; }
-            HIPCHK(m, hipMalloc(&m->ly.rf_field, sizeof(unsigned short) * cells));
-            m->ly.rf_field_cells = cells;
-        }
-        if (set_words > m->ly.rf_sets_words) {
-            if (m->ly.rf_sets) { HIPCHK(m, hipFree(m->ly.rf_sets)); m->ly.rf_sets = nullptr; m->ly.rf_sets_words = 0; }
-            HIPCHK(m, hipMalloc(&m->ly.rf_sets, sizeof(u64) * set_words));
-            m->ly.rf_sets_words = set_words;
-        }
-        if (hist_words > m->ly.tl_hist_words) {
-            if (m->ly.tl_hist) { HIPCHK(m, hipFree(m->ly.tl_hist)); m->ly.tl_hist = nullptr; m->ly.tl_hist_words = 0; }
-            HIPCHK(m, hipMalloc(&m->ly.tl_hist, sizeof(u64) * hist_words));
-            m->ly.tl_hist_words = hist_words;
-        }
+        int rc = layer_buf_grow(m, &m->ly.rf_field, &m->ly.rf_field_cells, cells);
+        if (rc == DSPMAP_OK) rc = layer_buf_grow(m, &m->ly.rf_sets, &m->ly.rf_sets_words, set_words);
+        if (rc == DSPMAP_OK) rc = layer_buf_grow(m, &m->ly.tl_hist, &m->ly.tl_hist_words, hist_words);
+        if (rc != DSPMAP_OK) return rc;
         if (keep && !m->ly.tl_last) HIPCHK(m, hipMalloc(&m->ly.tl_last, sizeof(int) * DSPMAP_REACH_MAX_FIELDS));
     }
     ReachArgs a;
-    origin_fill(m, flags, &a);
+    a.org = origin_fill(m, flags);
     a.with_current = (flags & DSPMAP_REACH_WITH_CURRENT) ? 1 : 0;
     const bool timed = !(t_start < 0.f) && d.T > 0;
     a.timed = timed ? 1 : 0;
@@ -550,7 +545,7 @@ extern "C" int dspmap_get_reach_sets(dspmap_t* m, int field, int first_step, int
     HIPCHK(m, hipMemcpyAsync(&last, m->ly.tl_last + field, sizeof(int), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));
     if (last < 0 || last > m->ly.tl_max_steps) return dspmap_fail(m, DSPMAP_E_DEVICE, "reach sets: field %d reports last step %d outside [0, %d]", field, last, m->ly.tl_max_steps);
-    const size_t lw = cast_layer_words(m->d);
+    const size_t lw = grid_layer_words(m->d);
     const u64* rows = m->ly.tl_hist + (size_t)field * ((size_t)m->ly.tl_max_steps + 1) * lw;
     const int n_own = first_step > last ? 0 : (first_step + n_steps - 1 > last ? last - first_step + 1 : n_steps);   // rows the build wrote
     if (n_own > 0) HIPCHK(m, hipMemcpyAsync(out, rows + (size_t)first_step * lw, sizeof(u64) * lw * (size_t)n_own, hipMemcpyDeviceToHost, m->stream));
@@ -559,77 +554,93 @@ extern "C" int dspmap_get_reach_sets(dspmap_t* m, int field, int first_step, int
     HIPCHK(m, hipStreamSynchronize(m->stream));
     return DSPMAP_OK;
 }
-// the argument checks of dspmap_reach_paths* and dspmap_reach_timeline_paths*
-static int reach_paths_args_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
+// the paths through the fields: dspmap_reach_paths*, dspmap_reach_timeline_paths* and dspmap_cost_paths* are one check, one enqueue and one
+// host / device pair; `what` and `out_name` keep every message what its entry point always said
+enum PathKind { PATHS_REACH, PATHS_TIMELINE, PATHS_COST };
+static int cost_ready(dspmap* m, const char* what);   // (with the cost fields, below)
+static int paths_args_check(dspmap* m, const char* what, const char* out_name, int n, const void* start, int max_len, int flags, const void* steps_out,
+                            const void* cells_out) {
     if (!m) return DSPMAP_E_ARG;
-    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: negative start count %d", n);
+    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative start count %d", what, n);
     if (max_len < 0 || max_len > DSPMAP_REACH_MAX_STEPS + 1)
-        return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: max_len %d outside [0, %d]", max_len, DSPMAP_REACH_MAX_STEPS + 1);
-    if (n > 0 && (!start || !steps_out)) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: NULL start or steps_out array");
-    if (n > 0 && max_len > 0 && !cells_out) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: NULL cells_out array with max_len %d", max_len);
-    if (flags & ~DSPMAP_QUERY_WORLD) return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: unknown flags 0x%x", flags);
+        return dspmap_fail(m, DSPMAP_E_ARG, "%s: max_len %d outside [0, %d]", what, max_len, DSPMAP_REACH_MAX_STEPS + 1);
+    if (n > 0 && (!start || !steps_out)) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL start or %s array", what, out_name);
+    if (n > 0 && max_len > 0 && !cells_out) return dspmap_fail(m, DSPMAP_E_ARG, "%s: NULL cells_out array with max_len %d", what, max_len);
+    const int rc = flags_check(m, what, flags, DSPMAP_QUERY_WORLD);
+    if (rc != DSPMAP_OK) return rc;
     if ((unsigned long long)n * (unsigned long long)max_len > 0x80000000ull)
-        return dspmap_fail(m, DSPMAP_E_ARG, "reach paths: %d paths of %d cells exceed 2^31 cells", n, max_len);
+        return dspmap_fail(m, DSPMAP_E_ARG, "%s: %d paths of %d cells exceed 2^31 cells", what, n, max_len);
     return DSPMAP_OK;
 }
-// ... then the state: the plain paths need time-invariant fields, the timeline's paths (`timeline`) the sets a timeline build kept
-static int reach_paths_check(dspmap* m, bool timeline, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
-    int rc = reach_paths_args_check(m, n, start, max_len, flags, steps_out, cells_out);
+// ... then the state: the plain reach paths need time-invariant fields, the timeline's paths the sets a timeline build kept, the cost paths
+// the cost fields
+static int paths_check(dspmap* m, PathKind kind, int n, const void* start, int max_len, int flags, const void* steps_out, const void* cells_out) {
+    const bool cost = kind == PATHS_COST;
+    int rc = paths_args_check(m, cost ? "cost paths" : "reach paths", cost ? "cost_out" : "steps_out", n, start, max_len, flags, steps_out, cells_out);
     if (rc != DSPMAP_OK) return rc;
-    if (timeline) return reach_timeline_ready(m, "dspmap_reach_timeline_paths");
+    if (cost) return cost_ready(m, "dspmap_cost_paths");
+    if (kind == PATHS_TIMELINE) return reach_timeline_ready(m, "dspmap_reach_timeline_paths");
     if ((rc = reach_ready(m, "dspmap_reach_paths")) != DSPMAP_OK) return rc;
     if (!m->ly.rf_invariant)
         return dspmap_fail(m, DSPMAP_E_STATE, "reach paths: the fields of the last build are not time-invariant (the tested layer changed "
                                               "during the steps): first arrivals alone do not determine a path");
     return DSPMAP_OK;
 }
-static int reach_paths_enqueue(dspmap* m, bool timeline, int n, const dspmap_reach_point* ds, int max_len, int flags, int* dt, int* dc) {
-    if (timeline) {
+static int paths_enqueue(dspmap* m, PathKind kind, int n, const dspmap_reach_point* ds, int max_len, int flags, int* dt, int* dc) {
+    if (kind == PATHS_TIMELINE) {
         ReachTimelinePathArgs a;
-        origin_fill(m, flags, &a);
+        a.org = origin_fill(m, flags);
         a.n_fields = m->ly.rf_n; a.max_len = max_len; a.max_steps = m->ly.tl_max_steps;
         a.field = m->ly.rf_field; a.hist = m->ly.tl_hist; a.last = m->ly.tl_last;
         launch_reach_timeline_paths(dspmap_ctx_of(m), a, n, ds, dt, dc);
     } else {
-        ReachPathArgs a;
-        origin_fill(m, flags, &a);
-        a.n_fields = m->ly.rf_n; a.max_len = max_len;
-        a.field = m->ly.rf_field;
-        launch_reach_paths(dspmap_ctx_of(m), a, n, ds, dt, dc);
+        const bool cost = kind == PATHS_COST;
+        FieldPathArgs a;
+        a.org = origin_fill(m, flags);
+        a.n_fields = cost ? m->ly.cf_n : m->ly.rf_n; a.max_len = max_len;
+        a.field = cost ? m->ly.cf_field : m->ly.rf_field;
+        a.weight = cost ? m->ly.cf_weight : nullptr;
+        launch_field_paths(dspmap_ctx_of(m), a, cost, n, ds, dt, dc);
     }
     HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;
 }
-// the two host entry points (max_len == 0: no cells section, the kernel gets NULL) ...
-static int reach_paths_host(dspmap* m, bool timeline, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
-    int rc = reach_paths_check(m, timeline, n, start, max_len, flags, steps_out, cells_out);
+// the host entry points (max_len == 0: no cells section, the kernel gets NULL) ...
+static int paths_host(dspmap* m, PathKind kind, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
+    int rc = paths_check(m, kind, n, start, max_len, flags, steps_out, cells_out);
     if (rc != DSPMAP_OK) return rc;
     if (n == 0) return DSPMAP_OK;
     StageSec s[3] = {{start, nullptr, sizeof(dspmap_reach_point) * (size_t)n}, {nullptr, steps_out, sizeof(int) * (size_t)n},
                      {nullptr, cells_out, sizeof(int) * (size_t)n * max_len}};
     if ((rc = stage_begin(m, s, 3)) != DSPMAP_OK) return rc;
-    if ((rc = reach_paths_enqueue(m, timeline, n, (const dspmap_reach_point*)s[0].dev, max_len, flags, (int*)s[1].dev, (int*)s[2].dev)) != DSPMAP_OK) return rc;
+    if ((rc = paths_enqueue(m, kind, n, (const dspmap_reach_point*)s[0].dev, max_len, flags, (int*)s[1].dev, (int*)s[2].dev)) != DSPMAP_OK) return rc;
     return stage_end(m, s, 3);
 }
-// ... and the two stream-ordered ones
-static int reach_paths_device(dspmap* m, bool timeline, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
-    const int rc = reach_paths_check(m, timeline, n, start, max_len, flags, steps_out, cells_out);
+// ... and the stream-ordered ones
+static int paths_device(dspmap* m, PathKind kind, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
+    const int rc = paths_check(m, kind, n, start, max_len, flags, steps_out, cells_out);
     if (rc != DSPMAP_OK) return rc;
-    return reach_paths_enqueue(m, timeline, n, start, max_len, flags, steps_out, cells_out);
+    return paths_enqueue(m, kind, n, start, max_len, flags, steps_out, cells_out);
 }
 extern "C" int dspmap_reach_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
-    return reach_paths_host(m, false, n, start, max_len, flags, steps_out, cells_out);
+    return paths_host(m, PATHS_REACH, n, start, max_len, flags, steps_out, cells_out);
 }
 extern "C" int dspmap_reach_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out, int* cells_out) {
-    return reach_paths_device(m, false, n, start, max_len, flags, steps_out, cells_out);
+    return paths_device(m, PATHS_REACH, n, start, max_len, flags, steps_out, cells_out);
 }
 extern "C" int dspmap_reach_timeline_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out,
                                            int* cells_out) {
-    return reach_paths_host(m, true, n, start, max_len, flags, steps_out, cells_out);
+    return paths_host(m, PATHS_TIMELINE, n, start, max_len, flags, steps_out, cells_out);
 }
 extern "C" int dspmap_reach_timeline_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* steps_out,
                                                   int* cells_out) {
-    return reach_paths_device(m, true, n, start, max_len, flags, steps_out, cells_out);
+    return paths_device(m, PATHS_TIMELINE, n, start, max_len, flags, steps_out, cells_out);
+}
+extern "C" int dspmap_cost_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* cost_out, int* cells_out) {
+    return paths_host(m, PATHS_COST, n, start, max_len, flags, cost_out, cells_out);
+}
+extern "C" int dspmap_cost_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* cost_out, int* cells_out) {
+    return paths_device(m, PATHS_COST, n, start, max_len, flags, cost_out, cells_out);
 }
 // --------------------------------------------------- shortened paths (dspmap_shorten.hip; semantics in include/dspmap.h)
 // needs the cast grid only: the paths may come from a reach snapshot, from a stale one or from the caller
@@ -701,7 +712,7 @@ extern "C" int dspmap_debug_set_cast_grid(dspmap_t* m, const unsigned long long*
     if (!m) return DSPMAP_E_ARG;
     if (!words) return dspmap_fail(m, DSPMAP_E_ARG, "set cast grid: NULL word array");
     const MapDims& d = m->d;
-    const size_t nw = (size_t)((d.nx + 63) >> 6), total = (size_t)(d.T + 1) * cast_layer_words(d);
+    const size_t nw = grid_row_words(d), total = (size_t)(d.T + 1) * grid_layer_words(d);
     if (d.nx & 63) {
         const unsigned long long pad = ~0ull << (d.nx & 63);
         for (size_t i = nw - 1; i < total; i += nw)
@@ -791,7 +802,7 @@ static int forecast_query_check(dspmap* m, int n, const void* in, const void* ou
 }
 static ForecastQueryArgs forecast_query_args(const dspmap* m, int flags, float outside) {
     ForecastQueryArgs a;
-    origin_fill(m, flags, &a);
+    a.org = origin_fill(m, flags);
     a.lerp = (flags & DSPMAP_FORECAST_LERP) ? 1 : 0;
     a.outside = outside;
     a.n = m->ly.fc_n;
@@ -938,7 +949,7 @@ static int known_query_check(dspmap* m, int n, const void* in, const void* out, 
 }
 // (the caller has synchronised the layer: known_sync queues work of its own, in front of the staging copies)
 static int known_query_enqueue(dspmap* m, const KnownArgs& a, int n, const float4* dq, int flags, int* dout) {
-    launch_known_query(m->d, m->stream, a, (flags & DSPMAP_QUERY_WORLD) ? 1 : 0, m->cur_pos, n, dq, dout);
+    launch_known_query(m->d, m->stream, a, origin_fill(m, flags), n, dq, dout);
     HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;
 }
@@ -1034,7 +1045,7 @@ static int view_dirs(dspmap* m) {
 }
 static void view_args_geometry(const dspmap* m, ViewArgs* a, int flags) {
     const MapDims& d = m->d;
-    origin_fill(m, flags, a);
+    a->org = origin_fill(m, flags);
     a->cx = -d.half_x + d.res * 0.5f; a->cy = -d.half_y + d.res * 0.5f; a->cz = -d.half_z + d.res * 0.5f;   // dspmap_voxel_center
     a->dirs0 = m->ly.vw_dirs0;
     a->reach = d.res * (float)(d.nx + d.ny + d.nz);
@@ -1116,7 +1127,7 @@ extern "C" int dspmap_debug_view_cells(dspmap_t* m, const dspmap_view* view, int
     if (rc != DSPMAP_OK) return rc;
     ViewArgs a;
     if ((rc = view_args(m, 0, flags, &a)) != DSPMAP_OK) return rc;
-    const size_t lw = cast_layer_words(m->d);
+    const size_t lw = grid_layer_words(m->d);
     StageSec s[4] = {{view, nullptr, sizeof(dspmap_view)}, {nullptr, nullptr, sizeof(dspmap_view_score)}, {nullptr, words_out, sizeof(u64) * lw},
                      {nullptr, ml_out, sizeof(float) * (size_t)m->d.np}};
     if ((rc = stage_begin(m, s, 4)) != DSPMAP_OK) return rc;
@@ -1133,7 +1144,7 @@ static int view_sel_check(dspmap* m, const char* what, long long n, int max_age,
     if (max_age < 0) return dspmap_fail(m, DSPMAP_E_ARG, "%s: negative max_age %d", what, max_age);
     int rc = flags_check(m, what, flags, DSPMAP_QUERY_WORLD);
     if (rc != DSPMAP_OK) return rc;
-    const unsigned long long mask = (unsigned long long)cast_layer_words(m->d) * sizeof(u64);   // (> 0)
+    const unsigned long long mask = (unsigned long long)grid_layer_words(m->d) * sizeof(u64);   // (> 0)
     if ((unsigned long long)n > DSPMAP_VIEW_MASK_MAX_BYTES / mask)   // (a division: n * mask is formed only where it is known to be small)
         return dspmap_fail(m, DSPMAP_E_ARG, "%s: the masks of %lld views take %llu bytes, more than DSPMAP_VIEW_MASK_MAX_BYTES = %llu", what, n,
                            (unsigned long long)n > ~0ull / mask ? ~0ull : (unsigned long long)n * mask, (unsigned long long)DSPMAP_VIEW_MASK_MAX_BYTES);
@@ -1167,7 +1178,7 @@ static int view_select_check(dspmap* m, int n, const void* views, int n_fixed, i
 struct ViewSelScratch { u64* masks; u64* unk; u64* avail; dspmap_view_set_score* fixed; dspmap_view_score* scores; int* gain; };
 static int view_sel_scratch(dspmap* m, int n, ViewSelScratch* s) {
     LayerState& l = m->ly;
-    const size_t lw = cast_layer_words(m->d);
+    const size_t lw = grid_layer_words(m->d);
     const size_t words = (size_t)n * lw;
     const size_t o_avail = q_align(sizeof(u64) * lw), o_fixed = o_avail + q_align(sizeof(u64) * lw), o_scores = o_fixed + q_align(sizeof(dspmap_view_set_score));
     const size_t o_gain = o_scores + q_align(sizeof(dspmap_view_score) * (size_t)n), bytes = o_gain + q_align(sizeof(int) * (size_t)n + sizeof(int));
@@ -1202,7 +1213,7 @@ static int view_masks_enqueue(dspmap* m, const ViewArgs& a, int n, const dspmap_
     if (rc != DSPMAP_OK) return rc;
     *scores = ds ? ds : s->scores;
     if (n > 0) {
-        HIPCHK(m, hipMemsetAsync(s->masks, 0, sizeof(u64) * (size_t)n * cast_layer_words(m->d), m->stream));
+        HIPCHK(m, hipMemsetAsync(s->masks, 0, sizeof(u64) * (size_t)n * grid_layer_words(m->d), m->stream));
         HIPCHK(m, hipMemsetAsync(*scores, 0, sizeof(dspmap_view_score) * (size_t)n, m->stream));
         launch_view_masks(m->d, m->s, m->stream, a, n, view_chunks(m->d, n, m->n_cu, m->ly.vw_chunks), dv, *scores, s->masks);
     }
@@ -1217,7 +1228,7 @@ static int view_sets_enqueue(dspmap* m, const ViewArgs& a, int n_sets, int set_s
     dspmap_view_score* scores;
     const int rc = view_masks_enqueue(m, a, n_sets * set_size, dv, ds, &s, &scores);
     if (rc != DSPMAP_OK) return rc;
-    const int lw = (int)cast_layer_words(m->d);
+    const int lw = (int)grid_layer_words(m->d);
     HIPCHK(m, hipMemsetAsync(dout, 0, sizeof(dspmap_view_set_score) * (size_t)n_sets, m->stream));
     launch_viewsel_sets(m->stream, lw, n_sets, set_size, viewsel_chunks(lw, n_sets, m->n_cu, m->ly.vw_chunks), s.masks, s.unk, scores, dout, nullptr);
     HIPCHK(m, hipGetLastError());
@@ -1231,7 +1242,7 @@ static int view_select_enqueue(dspmap* m, const ViewArgs& a, int n, const dspmap
     const int rc = view_masks_enqueue(m, a, n, dv, ds, &s, &scores);
     if (rc != DSPMAP_OK) return rc;
     if (k == 0) return DSPMAP_OK;
-    const int lw = (int)cast_layer_words(m->d), n_cand = n - n_fixed;
+    const int lw = (int)grid_layer_words(m->d), n_cand = n - n_fixed;
     HIPCHK(m, hipMemsetAsync(s.fixed, 0, sizeof(dspmap_view_set_score), m->stream));
     HIPCHK(m, hipMemsetAsync(s.gain, 0, sizeof(int) * (size_t)n_cand + sizeof(int), m->stream));
     launch_viewsel_sets(m->stream, lw, 1, n_fixed, viewsel_chunks(lw, 1, m->n_cu, m->ly.vw_chunks), s.masks, s.unk, scores, s.fixed, s.avail);
@@ -1300,7 +1311,7 @@ static int frontier_layer_host(const MapDims& d, float t) {
 // the buffers of a build with nb blocks: what does not depend on the block size once, the rest again when nb outgrows it
 static int frontier_alloc(dspmap* m, size_t nb) {
     const MapDims& d = m->d;
-    const size_t lw = cast_layer_words(d);
+    const size_t lw = grid_layer_words(d);
     if (!m->ly.fr_grid) HIPCHK(m, hipMalloc(&m->ly.fr_grid, sizeof(u64) * lw));
     if (!m->ly.fr_cells) HIPCHK(m, hipMalloc(&m->ly.fr_cells, sizeof(int) * (size_t)d.v_glob));
     if (!m->ly.fr_counts) HIPCHK(m, hipMalloc(&m->ly.fr_counts, 3 * sizeof(long long)));
@@ -1338,7 +1349,7 @@ extern "C" int dspmap_build_frontiers(dspmap_t* m, float t, int max_age, int min
     const size_t nb = (size_t)a.nbx * a.nby * (size_t)((d.nz + block - 1) / block);   // (<= V < 2^31)
     a.nb = (int)nb;
     if ((rc = frontier_alloc(m, nb)) != DSPMAP_OK) return rc;
-    const size_t lw = cast_layer_words(d);
+    const size_t lw = grid_layer_words(d);
     a.bits = m->ly.cg_bits + lw * (size_t)frontier_layer_host(d, t);
     a.max_age = max_age; a.min_unknown = min_unknown; a.block = block;
     a.grid = m->ly.fr_grid; a.cells = m->ly.fr_cells; a.dense = m->ly.fr_dense; a.blocks = m->ly.fr_blocks;
@@ -1369,7 +1380,7 @@ extern "C" int dspmap_get_frontier_grid(dspmap_t* m, unsigned long long* out) {
     if (!out) return dspmap_fail(m, DSPMAP_E_ARG, "dspmap_get_frontier_grid: NULL output array");
     const int rc = frontier_ready(m, "dspmap_get_frontier_grid");
     if (rc != DSPMAP_OK) return rc;
-    return read_back(m, out, m->ly.fr_grid, sizeof(u64) * cast_layer_words(m->d));
+    return read_back(m, out, m->ly.fr_grid, sizeof(u64) * grid_layer_words(m->d));
 }
 // the first min(cap, n) entries of list `which` (0: cells, 1: blocks) of `bytes` each, and n
 static int frontier_list(dspmap* m, const char* what, int which, const void* dev, size_t bytes, int cap, void* out, int* n_out) {
@@ -1466,7 +1477,7 @@ extern "C" int dspmap_build_objects(dspmap_t* m, float t, int connectivity, int 
     dspmap_layers_stale(m->ly, LAYERS_OBJECTS_REBUILD);
     if ((rc = objects_alloc(m, (size_t)max_objects < V ? (size_t)max_objects : V)) != DSPMAP_OK) return rc;
     ObjectArgs a;
-    a.bits = m->ly.cg_bits + cast_layer_words(d) * (size_t)frontier_layer_host(d, t);
+    a.bits = m->ly.cg_bits + grid_layer_words(d) * (size_t)frontier_layer_host(d, t);
     a.conn = connectivity; a.min_cells = min_cells; a.max_objects = max_objects;
     a.parent = m->ly.ob_parent; a.root_val = m->ly.ob_root; a.labels = m->ly.ob_labels; a.objects = m->ly.ob_objects;
     a.tile_sum = m->ly.ob_tiles; a.counts = m->ly.ob_counts;
@@ -1533,7 +1544,7 @@ static int objects_query_check(dspmap* m, int n, const void* in, const void* out
     return objects_ready(m, "dspmap_query_objects");
 }
 static int objects_query_enqueue(dspmap* m, int n, const float4* dq, int flags, int* dout) {
-    launch_objects_query(dspmap_ctx_of(m), m->ly.ob_labels, (flags & DSPMAP_QUERY_WORLD) ? 1 : 0, m->cur_pos, n, dq, dout);
+    launch_objects_query(dspmap_ctx_of(m), m->ly.ob_labels, origin_fill(m, flags), n, dq, dout);
     HIPCHK(m, hipGetLastError());
     return DSPMAP_OK;
 }
@@ -1741,23 +1752,16 @@ static int cost_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_poi
                       int flags) {
     const MapDims& d = m->d;
     dspmap_layers_stale(m->ly, LAYERS_COST_REBUILD);
-    const size_t V = (size_t)d.v_glob, cells = (size_t)n_fields * V, lw = cast_layer_words(d);
+    const size_t V = (size_t)d.v_glob, cells = (size_t)n_fields * V, lw = grid_layer_words(d);
     const size_t set_words = (size_t)COST_SET_COUNT * lw * (size_t)n_fields;
     if (!m->ly.cf_weight || cells > m->ly.cf_field_cells || set_words > m->ly.cf_sets_words) {   // grown only after the stream has drained (an earlier call may still read them)
         HIPCHK(m, hipStreamSynchronize(m->stream));
         if (!m->ly.cf_weight) HIPCHK(m, hipMalloc(&m->ly.cf_weight, V));
         if (!m->ly.cf_wk) HIPCHK(m, hipMalloc(&m->ly.cf_wk, sizeof(u64) * COST_MAX_WEIGHT * lw));
         if (!m->ly.cf_occ) HIPCHK(m, hipMalloc(&m->ly.cf_occ, sizeof(int)));
-        if (cells > m->ly.cf_field_cells) {
-            if (m->ly.cf_field) { HIPCHK(m, hipFree(m->ly.cf_field)); m->ly.cf_field = nullptr; m->ly.cf_field_cells = 0; }
-            HIPCHK(m, hipMalloc(&m->ly.cf_field, sizeof(unsigned short) * cells));
-            m->ly.cf_field_cells = cells;
-        }
-        if (set_words > m->ly.cf_sets_words) {
-            if (m->ly.cf_sets) { HIPCHK(m, hipFree(m->ly.cf_sets)); m->ly.cf_sets = nullptr; m->ly.cf_sets_words = 0; }
-            HIPCHK(m, hipMalloc(&m->ly.cf_sets, sizeof(u64) * set_words));
-            m->ly.cf_sets_words = set_words;
-        }
+        int rc = layer_buf_grow(m, &m->ly.cf_field, &m->ly.cf_field_cells, cells);
+        if (rc == DSPMAP_OK) rc = layer_buf_grow(m, &m->ly.cf_sets, &m->ly.cf_sets_words, set_words);
+        if (rc != DSPMAP_OK) return rc;
     }
     const int l = frontier_layer_host(d, t);   // ONE layer for the whole build: dspmap_build_objects' rule
     CostWeightArgs w;
@@ -1770,7 +1774,7 @@ static int cost_build(dspmap* m, int n_fields, int n_src, const dspmap_reach_poi
     w.dist = bands->n_bands > 0 ? m->ly.df_field + V * (size_t)l : nullptr;
     w.weight = m->ly.cf_weight; w.wk = m->ly.cf_wk; w.occ = m->ly.cf_occ;
     CostArgs a;
-    origin_fill(m, flags, &a);
+    a.org = origin_fill(m, flags);
     a.max_cost = max_cost; a.n_fields = n_fields; a.n_src = n_src;
     a.wk = m->ly.cf_wk; a.occ = m->ly.cf_occ; a.field = m->ly.cf_field; a.sets = m->ly.cf_sets;
     const LaunchCtx c = dspmap_ctx_of(m);
@@ -1822,44 +1826,7 @@ extern "C" int dspmap_get_cost_weights(dspmap_t* m, unsigned char* out) {
     if (rc != DSPMAP_OK) return rc;
     return read_back(m, out, m->ly.cf_weight, (size_t)m->d.v_glob);
 }
-// the checks of dspmap_cost_paths*: the arguments of dspmap_reach_paths, then the snapshot
-static int cost_paths_check(dspmap* m, int n, const void* start, int max_len, int flags, const void* cost_out, const void* cells_out) {
-    if (!m) return DSPMAP_E_ARG;
-    if (n < 0) return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: negative start count %d", n);
-    if (max_len < 0 || max_len > DSPMAP_REACH_MAX_STEPS + 1)
-        return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: max_len %d outside [0, %d]", max_len, DSPMAP_REACH_MAX_STEPS + 1);
-    if (n > 0 && (!start || !cost_out)) return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: NULL start or cost_out array");
-    if (n > 0 && max_len > 0 && !cells_out) return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: NULL cells_out array with max_len %d", max_len);
-    const int rc = flags_check(m, "cost paths", flags, DSPMAP_QUERY_WORLD);
-    if (rc != DSPMAP_OK) return rc;
-    if ((unsigned long long)n * (unsigned long long)max_len > 0x80000000ull)
-        return dspmap_fail(m, DSPMAP_E_ARG, "cost paths: %d paths of %d cells exceed 2^31 cells", n, max_len);
-    return cost_ready(m, "dspmap_cost_paths");
-}
-static int cost_paths_enqueue(dspmap* m, int n, const dspmap_reach_point* ds, int max_len, int flags, int* dt, int* dc) {
-    CostPathArgs a;
-    origin_fill(m, flags, &a);
-    a.n_fields = m->ly.cf_n; a.max_len = max_len;
-    a.field = m->ly.cf_field; a.weight = m->ly.cf_weight;
-    launch_cost_paths(dspmap_ctx_of(m), a, n, ds, dt, dc);
-    HIPCHK(m, hipGetLastError());
-    return DSPMAP_OK;
-}
-extern "C" int dspmap_cost_paths(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* cost_out, int* cells_out) {
-    int rc = cost_paths_check(m, n, start, max_len, flags, cost_out, cells_out);
-    if (rc != DSPMAP_OK) return rc;
-    if (n == 0) return DSPMAP_OK;
-    StageSec s[3] = {{start, nullptr, sizeof(dspmap_reach_point) * (size_t)n}, {nullptr, cost_out, sizeof(int) * (size_t)n},
-                     {nullptr, cells_out, sizeof(int) * (size_t)n * max_len}};   // (max_len == 0: no cells section, the kernel gets NULL)
-    if ((rc = stage_begin(m, s, 3)) != DSPMAP_OK) return rc;
-    if ((rc = cost_paths_enqueue(m, n, (const dspmap_reach_point*)s[0].dev, max_len, flags, (int*)s[1].dev, (int*)s[2].dev)) != DSPMAP_OK) return rc;
-    return stage_end(m, s, 3);
-}
-extern "C" int dspmap_cost_paths_device(dspmap_t* m, int n, const dspmap_reach_point* start, int max_len, int flags, int* cost_out, int* cells_out) {
-    const int rc = cost_paths_check(m, n, start, max_len, flags, cost_out, cells_out);
-    if (rc != DSPMAP_OK) return rc;
-    return cost_paths_enqueue(m, n, start, max_len, flags, cost_out, cells_out);
-}
+// (dspmap_cost_paths*: with the reach paths, paths_host / paths_device above)
 // test hook: all L layers of the VALID distance field are replaced by the caller's floats
 extern "C" int dspmap_debug_set_distance_field(dspmap_t* m, const float* layers) {
     if (!m) return DSPMAP_E_ARG;

@@ -24,6 +24,7 @@
 // meets a broken invariant or runs out of its trip bound ORs its code into the counts buffer's fault word and goes on; the synchronous
 // accessors turn a non-zero word into an error.  Nothing of the map or the grid is written.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 #include "dspmap_block_scan.h"
 #include "dspmap_unionfind.h"
@@ -43,7 +44,7 @@ struct ObLabels {
 // word item -> (w, y, z); row = z * ny + y
 struct ObItem { int w, row, y, z, x0; };
 __device__ __forceinline__ ObItem ob_item(const MapDims& d, int item) {
-    const int W = (d.nx + 63) >> 6;
+    const int W = (int)grid_row_words(d);
     ObItem it;
     it.w = item % W; it.row = item / W; it.y = it.row % d.ny; it.z = it.row / d.ny; it.x0 = it.w * 64;
     return it;
@@ -92,7 +93,7 @@ __global__ void __launch_bounds__(OB_TPB) k_objects_merge(MapDims d, ObjectArgs 
     const ObItem it = ob_item(d, item);
     const u64 word = ob_word(d, a.bits, item, it.w);
     if (!word) return;             // (wave-uniform)
-    const int W = (d.nx + 63) >> 6, V = d.v_glob;
+    const int W = (int)grid_row_words(d), V = d.v_glob;
     ObLabels m{a.parent};
     const int g = it.row * d.nx + it.x0 + l;
     int fault = UF_OK;
@@ -292,7 +293,7 @@ __global__ void __launch_bounds__(OB_TPB) k_objects_accumulate(MapDims d, DevSta
 }
 
 // one thread per sample: the label-grid entry of the voxel that holds it (k_known_query's shape)
-__global__ void __launch_bounds__(OB_TPB) k_objects_query(MapDims d, const int* __restrict__ labels, int world, float cx, float cy, float cz, int n,
+__global__ void __launch_bounds__(OB_TPB) k_objects_query(MapDims d, const int* __restrict__ labels, SampleOrigin org, int n,
                                                            const float4* __restrict__ q, int* __restrict__ out) {
     const unsigned i = blockIdx.x * OB_TPB + threadIdx.x;
     if (i >= (unsigned)n) return;
@@ -300,7 +301,7 @@ __global__ void __launch_bounds__(OB_TPB) k_objects_query(MapDims d, const int* 
     int ord = -1;
     if (!(sm.x != sm.x || sm.y != sm.y || sm.z != sm.z)) {
         float px = sm.x, py = sm.y, pz = sm.z;
-        if (world) { px = __fsub_rn(px, cx); py = __fsub_rn(py, cy); pz = __fsub_rn(pz, cz); }
+        origin_apply(org, px, py, pz);
         int g;
         if (voxel_of(d, px, py, pz, g)) ord = labels[g];
     }
@@ -309,7 +310,7 @@ __global__ void __launch_bounds__(OB_TPB) k_objects_query(MapDims d, const int* 
 
 void launch_objects(const LaunchCtx& c, const ObjectArgs& a) {
     const MapDims& d = c.d;
-    const int n_items = d.nz * d.ny * ((d.nx + 63) >> 6);
+    const int n_items = (int)grid_layer_words(d);
     const int n_tiles = frontier_tiles(d.v_glob);
     const dim3 tpb(OB_TPB), words((unsigned)((n_items + OB_WAVES - 1) / OB_WAVES)), cells((unsigned)n_tiles);
     hipLaunchKernelGGL(k_objects_init, words, tpb, 0, c.stream, d, a, n_items);
@@ -322,8 +323,7 @@ void launch_objects(const LaunchCtx& c, const ObjectArgs& a) {
     hipLaunchKernelGGL(k_objects_emit, cells, tpb, 0, c.stream, d, a);
     hipLaunchKernelGGL(k_objects_accumulate, words, tpb, 0, c.stream, d, c.s, a, n_items);
 }
-void launch_objects_query(const LaunchCtx& c, const int* labels, int world, const float cur[3], int n, const float4* q, int* out) {
+void launch_objects_query(const LaunchCtx& c, const int* labels, const SampleOrigin& org, int n, const float4* q, int* out) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_objects_query, dim3((unsigned)((n + OB_TPB - 1) / OB_TPB)), dim3(OB_TPB), 0, c.stream, c.d, labels, world, cur[0], cur[1],
-                       cur[2], n, q, out);
+    hipLaunchKernelGGL(k_objects_query, dim3((unsigned)((n + OB_TPB - 1) / OB_TPB)), dim3(OB_TPB), 0, c.stream, c.d, labels, org, n, q, out);
 }

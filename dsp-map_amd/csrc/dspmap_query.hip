@@ -18,6 +18,7 @@
 // neighbouring lanes, so their gathers share cache lines.
 // The r = 0 path is its own instantiation: one 16-B sample load, voxel_of, and the gathers of the own voxel.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 
 #define Q_TPB 256
@@ -44,7 +45,7 @@ template <bool LATTICE>
 __device__ __forceinline__ float q_value(const MapDims& d, const DevState& s, const QueryArgs& a, float4 q, bool& outside) {
     if (q.x != q.x || q.y != q.y || q.z != q.z || q.w != q.w) { outside = true; return a.outside; }   // (voxel_of lets NaN through)
     float px = q.x, py = q.y, pz = q.z;
-    if (a.world) { px = __fsub_rn(px, a.ox); py = __fsub_rn(py, a.oy); pz = __fsub_rn(pz, a.oz); }
+    origin_apply(a.org, px, py, pz);
     const int k = q_horizon(d, q.w);
     const int nzl = d.z_hi - d.z_lo;
     float best = -INFINITY;

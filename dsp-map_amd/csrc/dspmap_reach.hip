@@ -42,25 +42,11 @@
 //  - keeping the blocked words of the tested layer in LDS: the layer changes with n in the scheduled case, and in the static case the
 //    and-not is already skipped for every word the front does not touch.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 
 #define REACH_TPB 1024
 #define REACH_PATH_TPB 256
-
-__device__ __forceinline__ bool reach_finite(float v) { return fabsf(v) < INFINITY; }   // (false for NaN)
-
-// the cell of a source / start point (include/dspmap.h: the rules of the queries and of cast step 2): 0 = a cell, -2 = outside the map,
-// -3 = a non-finite coordinate
-__device__ __forceinline__ int reach_cell(const MapDims& d, float ox, float oy, float oz, int world, float px, float py, float pz, int& x, int& y,
-                                          int& z) {
-    if (!(reach_finite(px) && reach_finite(py) && reach_finite(pz))) return -3;
-    if (world) { px = __fsub_rn(px, ox); py = __fsub_rn(py, oy); pz = __fsub_rn(pz, oz); }
-    if (fabsf(px) >= d.half_x || fabsf(py) >= d.half_y || fabsf(pz) >= d.half_z) return -2;   // dspmap_point_voxel_index's test
-    x = (int)__fdiv_rn(__fadd_rn(px, d.half_x), d.res);                                       // (all >= 0: p > -half)
-    y = (int)__fdiv_rn(__fadd_rn(py, d.half_y), d.res);
-    z = (int)__fdiv_rn(__fadd_rn(pz, d.half_z), d.res);
-    return (x < d.nx && y < d.ny && z < d.nz) ? 0 : -2;
-}
 
 // the layer step n tests besides (with_current) layer 0
 __device__ __forceinline__ int reach_layer(const MapDims& d, const ReachArgs& a, int n) {
@@ -79,11 +65,12 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
     extern __shared__ u64 s_reach[];
     __shared__ int s_flag[3];   // bit 0: the step changed the set, bit 1: the set is not empty
     const unsigned tid = threadIdx.x, f = blockIdx.x;
-    const unsigned W = (unsigned)(d.nx + 63) >> 6, plane = (unsigned)d.ny * W, nwords = (unsigned)d.nz * plane;   // (< 2^31: the cast grid exists)
+    const GridWords gw(d);
+    const unsigned W = gw.W, plane = gw.plane, nwords = gw.nwords;
     u64* set = LDS ? s_reach : a.sets + (size_t)f * 2 * nwords;
     unsigned short* fld = a.field + (size_t)f * d.v_glob;
     const u64* __restrict__ bits = a.bits;
-    const u64 row_mask = (d.nx & 63) ? ~0ull >> (64 - (d.nx & 63)) : ~0ull;   // bits at x >= nx are never reached
+    const u64 row_mask = grid_row_mask(d);                                    // bits at x >= nx are never reached
     unsigned co = 0, no = nwords;                                             // R_{n-1} at set[co ..], R_n at set[no ..]
     u64* row = KEEP ? hist + (size_t)f * ((size_t)a.max_steps + 1) * nwords : nullptr;   // row n of this field's history, from row 0 on
     int done = a.max_steps;                                                   // (KEEP) the last step executed
@@ -95,8 +82,8 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
         const float4 p = src[i];
         if ((unsigned)__float_as_int(p.w) != f) continue;   // (a field outside [0, n_fields) matches no workgroup)
         int x, y, z;
-        if (reach_cell(d, a.ox, a.oy, a.oz, a.world, p.x, p.y, p.z, x, y, z) != 0) continue;
-        atomicOr((unsigned long long*)&set[co + ((unsigned)z * d.ny + y) * W + ((unsigned)x >> 6)], 1ull << (x & 63));
+        if (grid_cell(d, a.org, p.x, p.y, p.z, x, y, z) != 0) continue;
+        atomicOr((unsigned long long*)&set[co + gw.word_of(d, x, y, z)], GridWords::bit_of(x));
     }
     __syncthreads();
     {   // step 0: R_0 = S \ B_0, in place (a thread touches its own words only)
@@ -111,11 +98,7 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
             set[co + t] = v;
             if (KEEP) row[t] = v;
             const unsigned yz = t / W, w = t - yz * W;
-            unsigned short* cell = fld + (size_t)yz * d.nx + w * 64;
-            while (v) {
-                cell[__builtin_ctzll(v)] = 0;
-                v &= v - 1;
-            }
+            grid_store_bits(fld + (size_t)yz * d.nx + w * 64, v, 0);
         }
     }
     __syncthreads();
@@ -127,13 +110,7 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
             const unsigned z = t / plane, r = t - z * plane, y = r / W, w = r - y * W;
             const u64* cur = set + co + t;
             const u64 c = cur[0];
-            u64 g = c | (c << 1) | (c >> 1);
-            if (w > 0) g |= cur[-1] >> 63;             // the carries of the row's neighbouring words, never across rows
-            if (w + 1 < W) g |= cur[1] << 63;
-            if (y > 0) g |= cur[-(int)W];
-            if (y + 1 < (unsigned)d.ny) g |= cur[W];
-            if (z > 0) g |= cur[-(int)plane];
-            if (z + 1 < (unsigned)d.nz) g |= cur[plane];
+            u64 g = grid_grow6<true>(cur, c, w, y, z, gw, d);
             if (w + 1 == W) g &= row_mask;
             if (g) {
                 u64 b = bits[(size_t)l * nwords + t];
@@ -143,15 +120,9 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
             set[no + t] = g;
             if (KEEP) row[t] = g;
             verdict |= (g != c ? 1 : 0) | (g ? 2 : 0);
-            u64 fresh = g & ~c;                        // the front: cells of R_n that R_{n-1} did not hold
-            if (fresh) {
-                unsigned short* cell = fld + (size_t)(t / W) * d.nx + w * 64;
-                do {
-                    const int bit = __builtin_ctzll(fresh);
-                    fresh &= fresh - 1;
-                    if (cell[bit] == DSPMAP_REACH_UNREACHED) cell[bit] = (unsigned short)n;   // (a cell that comes back keeps its first arrival)
-                } while (fresh);
-            }
+            const u64 fresh = g & ~c;                  // the front: cells of R_n that R_{n-1} did not hold
+            if (fresh)                                 // (a cell that comes back keeps its first arrival)
+                grid_store_bits<true>(fld + (size_t)(t / W) * d.nx + w * 64, fresh, (unsigned short)n, DSPMAP_REACH_UNREACHED);
         }
         if (verdict) atomicOr(&s_flag[n % 3], verdict);
         if (tid == 0) s_flag[(n + 1) % 3] = 0;         // (its last readers, those of step n - 2, are past the barrier of step n - 1)
@@ -165,31 +136,46 @@ __global__ void __launch_bounds__(REACH_TPB) k_reach(MapDims d, ReachArgs a, con
     if (KEEP && tid == 0) last[f] = done;              // rows (done, max_steps] are never written: R_n = R_done there, for both exits
 }
 
-// one lane per start: the steepest descent through a time-invariant field, first neighbour of value v - 1 in the order -x, +x, -y, +y, -z, +z
-__global__ void __launch_bounds__(REACH_PATH_TPB) k_reach_paths(MapDims d, ReachPathArgs a, int n, const float4* __restrict__ start,
+static_assert(DSPMAP_COST_UNREACHED == DSPMAP_REACH_UNREACHED, "the paths of both kinds of field read one marker");
+// the head of every path: the start's field f and cell (x, y, z), the value v it reads there, and the path's status word -- v, -1 for an
+// unreached cell, -2 outside the map, -3 for a non-finite coordinate or a field outside [0, n_fields) (either wins over "outside")
+__device__ __forceinline__ int path_head(const MapDims& d, const SampleOrigin& org, int n_fields, const unsigned short* __restrict__ field, float4 p,
+                                         int& f, int& x, int& y, int& z, int& v) {
+    f = __float_as_int(p.w);
+    x = y = z = v = 0;
+    int st = grid_cell(d, org, p.x, p.y, p.z, x, y, z);
+    if ((unsigned)f >= (unsigned)n_fields) st = -3;
+    if (st == 0) {
+        v = field[(size_t)f * d.v_glob + ((size_t)z * d.ny + y) * d.nx + x];
+        st = v == DSPMAP_REACH_UNREACHED ? -1 : v;
+    }
+    return st;
+}
+// ... and its tail: the cells behind the path's last one read -1
+__device__ __forceinline__ void path_tail(int* out, int j, int max_len) {
+    for (; j < max_len; ++j) out[j] = -1;
+}
+
+// one lane per start: the steepest descent through a time-invariant field, first neighbour of the wanted value in the order -x, +x, -y, +y,
+// -z, +z.  The wanted value is v - 1 in an arrival field and, WEIGHTED, v - weight[g] in a cost field: the weight of the cell left
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(REACH_PATH_TPB) k_field_paths(MapDims d, FieldPathArgs a, int n, const float4* __restrict__ start,
                                                                 int* __restrict__ steps_out, int* __restrict__ cells_out) {
     const unsigned i = blockIdx.x * REACH_PATH_TPB + threadIdx.x;
     if (i >= (unsigned)n) return;
-    const float4 p = start[i];
-    const int f = __float_as_int(p.w);
-    int x = 0, y = 0, z = 0;
-    int st = reach_cell(d, a.ox, a.oy, a.oz, a.world, p.x, p.y, p.z, x, y, z);
-    if ((unsigned)f >= (unsigned)a.n_fields) st = -3;   // (a non-finite coordinate is -3 as well; either wins over "outside")
-    const unsigned short* __restrict__ fld = a.field + (size_t)(st == 0 ? f : 0) * d.v_glob;
-    int v = 0;
-    if (st == 0) {
-        v = fld[((size_t)z * d.ny + y) * d.nx + x];
-        st = v == DSPMAP_REACH_UNREACHED ? -1 : v;
-    }
+    int f, x, y, z, v;
+    const int st = path_head(d, a.org, a.n_fields, a.field, start[i], f, x, y, z, v);
     steps_out[i] = st;
     int* out = cells_out + (size_t)i * a.max_len;
     int j = 0;
     if (st >= 0) {
+        const unsigned short* __restrict__ fld = a.field + (size_t)f * d.v_glob;
         const int sy = d.nx, sz = d.nx * d.ny;
         int g = (z * d.ny + y) * d.nx + x;
-        for (; j < a.max_len;) {                       // (bounded by max_len; v falls by one per cell)
+        for (; j < a.max_len;) {                       // (bounded by max_len; v falls by at least one per cell)
             out[j++] = g;
             if (v == 0) break;
+            const int want = v - (WEIGHTED ? (int)a.weight[g] : 1);
             // the six neighbour loads of a step are issued together: independent addresses, one wait
             const bool ok[6] = {x > 0, x + 1 < d.nx, y > 0, y + 1 < d.ny, z > 0, z + 1 < d.nz};
             const int off[6] = {-1, 1, -sy, sy, -sz, sz};
@@ -199,16 +185,16 @@ __global__ void __launch_bounds__(REACH_PATH_TPB) k_reach_paths(MapDims d, Reach
             int pick = -1;
 #pragma unroll
             for (int k = 5; k >= 0; --k)
-                if (ok[k] && nv[k] == v - 1) pick = k;
-            if (pick < 0) break;                       // no such neighbour (never in a time-invariant field): stop, the rest is -1
+                if (ok[k] && nv[k] == want) pick = k;
+            if (pick < 0) break;                       // no such neighbour (never in a field the build made, time-invariant for arrivals): stop
             g += off[pick];
             x += pick == 1 ? 1 : (pick == 0 ? -1 : 0);
             y += pick == 3 ? 1 : (pick == 2 ? -1 : 0);
             z += pick == 5 ? 1 : (pick == 4 ? -1 : 0);
-            --v;
+            v = want;
         }
     }
-    for (; j < a.max_len; ++j) out[j] = -1;
+    path_tail(out, j, a.max_len);
 }
 
 // one lane per start: backwards through the sets a timeline build kept.  The cell at step s > 0 came from R_{s-1}: it waits where it is if
@@ -218,22 +204,14 @@ __global__ void __launch_bounds__(REACH_PATH_TPB) k_reach_timeline_paths(MapDims
                                                                          int* __restrict__ steps_out, int* __restrict__ cells_out) {
     const unsigned i = blockIdx.x * REACH_PATH_TPB + threadIdx.x;
     if (i >= (unsigned)n) return;
-    const float4 p = start[i];
-    const int f = __float_as_int(p.w);
-    int x = 0, y = 0, z = 0;
-    int st = reach_cell(d, a.ox, a.oy, a.oz, a.world, p.x, p.y, p.z, x, y, z);
-    if ((unsigned)f >= (unsigned)a.n_fields) st = -3;   // (a non-finite coordinate is -3 as well; either wins over "outside")
-    int v = 0;
-    if (st == 0) {
-        v = a.field[(size_t)f * d.v_glob + ((size_t)z * d.ny + y) * d.nx + x];
-        st = v == DSPMAP_REACH_UNREACHED ? -1 : v;
-    }
+    int f, x, y, z, v;
+    const int st = path_head(d, a.org, a.n_fields, a.field, start[i], f, x, y, z, v);
     steps_out[i] = st;
     int* out = cells_out + (size_t)i * a.max_len;
     int j = 0;
     if (st >= 0) {
-        const unsigned W = (unsigned)(d.nx + 63) >> 6;
-        const size_t nwords = (size_t)d.nz * d.ny * W;
+        const unsigned W = grid_row_words(d);
+        const size_t nwords = grid_layer_words(d);
         const u64* __restrict__ rows = a.hist + (size_t)f * ((size_t)a.max_steps + 1) * nwords;
         const int lastf = a.last[f];
         for (; j < a.max_len;) {                       // (bounded by max_len; v falls by one per cell)
@@ -258,7 +236,7 @@ __global__ void __launch_bounds__(REACH_PATH_TPB) k_reach_timeline_paths(MapDims
             --v;
         }
     }
-    for (; j < a.max_len; ++j) out[j] = -1;
+    path_tail(out, j, a.max_len);
 }
 
 void reach_init_device() {   // per device, once (dspmap_init_device)
@@ -270,7 +248,7 @@ void reach_init_device() {   // per device, once (dspmap_init_device)
 void launch_reach(const LaunchCtx& c, const ReachArgs& a, const dspmap_reach_point* src, u64* hist, int* last) {
     if (a.n_fields <= 0) return;
     const MapDims& d = c.d;
-    const size_t set_bytes = 2 * sizeof(u64) * (size_t)d.nz * d.ny * (size_t)((d.nx + 63) >> 6);
+    const size_t set_bytes = 2 * sizeof(u64) * grid_layer_words(d);
     const dim3 grid(a.n_fields), block(REACH_TPB);
     if (a.sets && hist)
         hipLaunchKernelGGL((k_reach<false, true>), grid, block, 0, c.stream, d, a, (const float4*)src, hist, last);
@@ -282,10 +260,11 @@ void launch_reach(const LaunchCtx& c, const ReachArgs& a, const dspmap_reach_poi
         hipLaunchKernelGGL((k_reach<true, false>), grid, block, set_bytes, c.stream, d, a, (const float4*)src, hist, last);
 }
 
-void launch_reach_paths(const LaunchCtx& c, const ReachPathArgs& a, int n, const dspmap_reach_point* start, int* steps_out, int* cells_out) {
+void launch_field_paths(const LaunchCtx& c, const FieldPathArgs& a, bool weighted, int n, const dspmap_reach_point* start, int* steps_out, int* cells_out) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_reach_paths, dim3((unsigned)(((long long)n + REACH_PATH_TPB - 1) / REACH_PATH_TPB)), dim3(REACH_PATH_TPB), 0, c.stream,
-                       c.d, a, n, (const float4*)start, steps_out, cells_out);
+    const dim3 grid((unsigned)(((long long)n + REACH_PATH_TPB - 1) / REACH_PATH_TPB)), block(REACH_PATH_TPB);
+    if (weighted) hipLaunchKernelGGL(k_field_paths<true>, grid, block, 0, c.stream, c.d, a, n, (const float4*)start, steps_out, cells_out);
+    else hipLaunchKernelGGL(k_field_paths<false>, grid, block, 0, c.stream, c.d, a, n, (const float4*)start, steps_out, cells_out);
 }
 
 void launch_reach_timeline_paths(const LaunchCtx& c, const ReachTimelinePathArgs& a, int n, const dspmap_reach_point* start, int* steps_out,

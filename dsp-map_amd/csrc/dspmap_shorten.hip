@@ -24,12 +24,11 @@
 //  - a workgroup per path with windows above 64: four waves would vote through LDS with two barriers per round for a window no planner
 //    asked for; a caller who wants longer pieces shortens the output once more (its vertices are cells again).
 #include "dspmap_cast_walk.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 
 #define SHORTEN_TPB 256
 #define SHORTEN_WAVES (SHORTEN_TPB / 64)
-
-__device__ __forceinline__ int sh_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // vertex of cell c at position j of a path whose first cell is occupied at step v: {voxel centre, time} (include/dspmap.h, "vertex", "time")
 __device__ __forceinline__ float4 sh_vertex(const MapDims& d, const ShortenArgs& a, int c, int v, int j) {
@@ -47,7 +46,7 @@ __global__ void __launch_bounds__(SHORTEN_TPB) k_shorten(MapDims d, ShortenArgs 
     const unsigned i = blockIdx.x * SHORTEN_WAVES + (threadIdx.x >> 6);   // the wave's path
     if (i >= (unsigned)n) return;                                         // (wave-uniform: the ballots below see whole waves)
     const int* path = cells + (size_t)i * a.max_len;
-    const int v = sh_uniform(steps[i]);
+    const int v = grid_uniform(steps[i]);
     // n_cells: the leading entries in [0, V), found 64 at a time
     int m = 0;
     if (v >= 0) {
@@ -59,7 +58,7 @@ __global__ void __launch_bounds__(SHORTEN_TPB) k_shorten(MapDims d, ShortenArgs 
             m = base + 64;
         }
     }
-    m = sh_uniform(m);
+    m = grid_uniform(m);
     float4* seg_i = seg + 2 * (size_t)i * a.max_seg;
     int* end_i = end + (size_t)i * a.max_seg;
     int p = 0, s = 0, n_blocked = 0, truncated = 0;
@@ -78,7 +77,7 @@ __global__ void __launch_bounds__(SHORTEN_TPB) k_shorten(MapDims d, ShortenArgs 
         int q = p + 1;
         if (mask) q += 63 - __builtin_clzll(mask);
         else ++n_blocked;
-        q = sh_uniform(q);
+        q = grid_uniform(q);
         if (lane == 0) {
             seg_i[2 * (size_t)s] = A;
             seg_i[2 * (size_t)s + 1] = sh_vertex(d, a, path[q], v, q);

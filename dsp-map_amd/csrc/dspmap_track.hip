@@ -19,6 +19,7 @@
 //                    the update void here.
 // Every probe loop is bounded by the table size.  Nothing of the map, the grid or the objects is written.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 #include "dspmap_block_scan.h"
 
@@ -86,7 +87,7 @@ __global__ void __launch_bounds__(TK_TPB) k_track_pairs(MapDims d, TrackArgs a, 
     const int item = (int)blockIdx.x * TK_WAVES + ((int)threadIdx.x >> 6);
     if (item >= n_items) return;   // (wave-uniform)
     const int l = lane_id();
-    const int W = (d.nx + 63) >> 6;
+    const int W = (int)grid_row_words(d);
     const int w = item % W, row = item / W, y = row % d.ny, z = row / d.ny;
     const int x = w * 64 + l;
     const int kp = tk_k_prev(a), kn = tk_k_now(a);
@@ -226,7 +227,7 @@ __global__ void k_track_keep(TrackArgs a) {
 
 void launch_track(const LaunchCtx& c, const TrackArgs& a) {
     const MapDims& d = c.d;
-    const int n_items = d.nz * d.ny * ((d.nx + 63) >> 6);
+    const int n_items = (int)grid_layer_words(d);
     const int n_tiles = frontier_tiles(a.cap);
     const dim3 tpb(TK_TPB), words((unsigned)((n_items + TK_WAVES - 1) / TK_WAVES)), recs((unsigned)n_tiles);
     if (!a.fresh) {

@@ -76,23 +76,23 @@ __global__ void __launch_bounds__(VW_TPB) k_view_score(MapDims d, DevState s, Vi
     // ---- head: the status (wave-uniform; nothing is walked for a view that is not OK)
     int status = DSPMAP_VIEW_OK, layer = 0, ix = 0, iy = 0, iz = 0;
     const float n2 = q[1] * q[1] + q[2] * q[2] + q[3] * q[3] + q[0] * q[0];   // rotate_by_quat's divisor
-    if (!(cast_finite(px) && cast_finite(py) && cast_finite(pz) && cast_finite(q[0]) && cast_finite(q[1]) && cast_finite(q[2]) &&
-          cast_finite(q[3])) || n2 == 0.f || t != t || !(R > 0.f)) {
+    if (!(grid_finite(px) && grid_finite(py) && grid_finite(pz) && grid_finite(q[0]) && grid_finite(q[1]) && grid_finite(q[2]) &&
+          grid_finite(q[3])) || n2 == 0.f || t != t || !(R > 0.f)) {
         status = DSPMAP_VIEW_INVALID;
     } else {
-        if (a.world) { px = __fsub_rn(px, a.ox); py = __fsub_rn(py, a.oy); pz = __fsub_rn(pz, a.oz); }
-        bool inside = !(fabsf(px) >= d.half_x || fabsf(py) >= d.half_y || fabsf(pz) >= d.half_z);   // dspmap_point_voxel_index's test
+        origin_apply(a.org, px, py, pz);
+        bool inside = !grid_beyond(d, px, py, pz);
         if (inside) {
-            ix = (int)__fdiv_rn(__fadd_rn(px, d.half_x), d.res);   // cast step 2
-            iy = (int)__fdiv_rn(__fadd_rn(py, d.half_y), d.res);
-            iz = (int)__fdiv_rn(__fadd_rn(pz, d.half_z), d.res);
+            ix = grid_axis_cell(px, d.half_x, d.res);   // cast step 2
+            iy = grid_axis_cell(py, d.half_y, d.res);
+            iz = grid_axis_cell(pz, d.half_z, d.res);
             inside = ix < d.nx && iy < d.ny && iz < d.nz;
         }
         if (!inside) {
             status = DSPMAP_VIEW_OUTSIDE;
         } else {
             layer = q_horizon(d, t) + 1;   // 0 for t < 0 or T == 0
-            const size_t nw = (size_t)(d.nx + 63) >> 6;
+            const size_t nw = (size_t)(d.nx + 63) >> 6;   // (the parent form of W in 64 bits, as cast_walk keeps it)
             const u64 word = a.bits[(((size_t)layer * d.nz + iz) * d.ny + iy) * nw + ((unsigned)ix >> 6)];
             if ((word >> (ix & 63)) & 1ull) status = DSPMAP_VIEW_BLOCKED;
         }
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(VW_TPB) k_view_score(MapDims d, DevState s, Vi
         rotate_by_quat(a.dirs0[3 * b], a.dirs0[3 * b + 1], a.dirs0[3 * b + 2], q, dir);
         const float ex = __fadd_rn(px, __fmul_rn(dir[0], ell)), ey = __fadd_rn(py, __fmul_rn(dir[1], ell)), ez = __fadd_rn(pz, __fmul_rn(dir[2], ell));
         float ml = -1.f;
-        if (cast_finite(ex) && cast_finite(ey) && cast_finite(ez)) {   // (cast step 1: a segment with a non-finite end is no cast)
+        if (grid_finite(ex) && grid_finite(ey) && grid_finite(ez)) {   // (cast step 1: a segment with a non-finite end is no cast)
             float sp;
             int voxel, lay, st;
             cast_walk(d, a.bits, px, py, pz, tc, ex, ey, ez, tc, sp, voxel, lay, st);
@@ -197,7 +197,7 @@ __global__ void __launch_bounds__(VW_TPB) k_view_rays(MapDims d, DevState s, Vie
 // workgroups per view: enough of them to give every CU a few, no more than the map has row items for (a chunk of fewer than VW_WAVES
 // items idles waves), and at most 64 -- every chunk repeats the rays
 int view_chunks(const MapDims& d, int n, int n_cu, int forced) {
-    const long long items = (long long)d.nz * d.ny * ((d.nx + 63) >> 6);
+    const long long items = (long long)grid_layer_words(d);
     long long most = (items + VW_WAVES - 1) / VW_WAVES;
     if (most > 64) most = 64;
     if (most < 1) most = 1;

@@ -18,6 +18,7 @@
 // All counts are integers of exactly defined predicates: no result depends on the chunking.  Nothing of the map, the grid or the layer is
 // written.
 #include "dspmap_device.h"
+#include "dspmap_grid.h"
 #include "dspmap_internal.h"
 #include "dspmap_known_slots.h"   // kn_cell, kn_age
 
@@ -28,7 +29,7 @@ __global__ void __launch_bounds__(VS_TPB) k_vs_unknown(MapDims d, KnownArgs a, i
     const int item = (int)blockIdx.x * VS_WAVES + ((int)threadIdx.x >> 6);
     if (item >= n_items) return;   // (wave-uniform)
     const int l = lane_id();
-    const int W = (d.nx + 63) >> 6;
+    const int W = (int)grid_row_words(d);
     const int w = item % W, row = item / W, y = row % d.ny, z = row / d.ny;
     const int x = w * 64 + l;
     bool unknown = false;
@@ -133,7 +134,7 @@ int viewsel_chunks(int lw, int n, int n_cu, int forced) {
 }
 
 void launch_viewsel_unknown(const MapDims& d, hipStream_t stream, const KnownArgs& a, int max_age, u64* unk) {
-    const int n_items = d.nz * d.ny * ((d.nx + 63) >> 6);
+    const int n_items = (int)grid_layer_words(d);
     hipLaunchKernelGGL(k_vs_unknown, dim3((unsigned)((n_items + VS_WAVES - 1) / VS_WAVES)), dim3(VS_TPB), 0, stream, d, a, max_age, unk, n_items);
 }
 void launch_viewsel_sets(hipStream_t stream, int lw, int n_sets, int set_size, int chunks, const u64* masks, const u64* unk,
