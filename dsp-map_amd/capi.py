@@ -645,60 +645,147 @@ class DSPMap:
         ext = torch.cuda.ExternalStream(s, device=dev)
         return (lambda: ext.wait_stream(cur)), (lambda: cur.wait_stream(ext))
 
+    # -- the one call path of the planning layers: every wrapper below states its inputs, outputs and flags and goes through these
+    def _input(self, a, width, what, want=None, ndim=None):
+        """(input made contiguous, its rows, its torch device or None for numpy) of rows of `width` numbers: float32 rows described by
+        `want` (the shape in the ValueError, `ndim` dimensions where that is fixed), or with want=None dspmap_reach_point rows.  The
+        only place that tells a GPU tensor from host data."""
+        dev = a.device if self._is_device_tensor(a) else None
+        if want is None:
+            q = self._reach_points(a, what) if dev is None else self._reach_points_device(a, what)
+            return q, (len(q) if dev is None else q.numel() // 4), dev
+        if dev is not None:
+            q = self._device_samples(a, (width,), what)
+            if ndim is not None and q.dim() != ndim:
+                raise ValueError("%s: %s" % (what, want))
+            return q, q.numel() // width, dev
+        q = np.ascontiguousarray(a, np.float32)
+        if (ndim is not None and q.ndim != ndim) or q.shape[-1:] != (width,):
+            raise ValueError("%s: %s" % (what, want))
+        return q, q.size // width, None
+
+    @staticmethod
+    def _alloc(dev, shape, dtype):
+        """an output where the input is: zeroed numpy of `dtype`, or an uninitialised tensor on `dev` -- float32 / int32, a structured
+        dtype as its int32 columns"""
+        if dev is None:
+            return np.zeros(shape, dtype)
+        import torch
+        dtype = np.dtype(dtype)
+        shape = shape if isinstance(shape, tuple) else (shape,)
+        if dtype.names:
+            return torch.empty(shape + (dtype.itemsize // 4,), dtype=torch.int32, device=dev)
+        return torch.empty(shape, dtype=torch.float32 if dtype == np.float32 else torch.int32, device=dev)
+
+    @staticmethod
+    def _p(a, when=True):
+        """the pointer argument of an array, a tensor or None; NULL also where `when` does not hold"""
+        if a is None or not when:
+            return None
+        return _ptr(a) if isinstance(a, np.ndarray) else a.data_ptr()
+
+    def _call(self, dev, symbol, *args, init_device=False):
+        """the host entry point `symbol` (dev None: synchronous), or `symbol`_device enqueued on the handle's stream and ordered with
+        torch's current stream both ways; init_device: dspmap_init_device first (the handle's stream exists from there on).  An
+        error raises before torch's stream is made to wait."""
+        if dev is None:
+            return self._chk(getattr(self.L, symbol)(self.h, *args))
+        if init_device:
+            self._chk(self.L.dspmap_init_device(self.h))
+        before, after = self._handle_stream_order(dev)
+        before()
+        rc = self._chk(getattr(self.L, symbol + "_device")(self.h, *args))
+        after()
+        return rc
+
+    @staticmethod
+    def _fields(raw, dtype, dev):
+        """a result of structured `dtype`: the numpy array as it is; the int32 block of a device call as a dict of views, one per field"""
+        if dev is None:
+            return raw
+        import torch
+        out = {}
+        for name in dtype.names:
+            ft, off = dtype.fields[name][:2]
+            col = raw[:, off // 4:(off + ft.itemsize) // 4] if ft.shape else raw[:, off // 4]
+            out[name] = col.view(torch.float32) if ft.base == np.float32 else col
+        return out
+
+    def _query(self, symbol, q, dtype, mid, init_device=False, grad=None):
+        """one value of `dtype` per sample {x, y, z, t} of q: symbol(h, n, q, *mid, out[, grad]); grad None: the entry point takes none"""
+        q, n, dev = self._input(q, 4, symbol[7:], "samples of shape [n, 4]")
+        out = self._alloc(dev, n, dtype)
+        g = self._alloc(dev, (n, 3), np.float32) if grad else None
+        self._call(dev, symbol, n, self._p(q), *mid, self._p(out), *(() if grad is None else (self._p(g),)), init_device=init_device)
+        return (out, g) if grad else out
+
+    def _paths(self, symbol, starts, max_len, world):
+        """reach_paths / reach_timeline_paths / cost_paths: (value [n] int32, cells [n, max_len] int32) from starts {x, y, z, field}.
+        The host entry points get NULL for an empty input, the device ones the tensor's address."""
+        max_len = int(max_len)
+        q, n, dev = self._input(starts, 4, symbol[7:])
+        value = self._alloc(dev, n, np.int32)
+        cells = self._alloc(dev, (n, max(max_len, 0)), np.int32)
+        some = n > 0 or dev is not None
+        self._call(dev, symbol, n, self._p(q, some), max_len, QUERY_WORLD if world else 0, self._p(value, some), self._p(cells, max_len > 0))
+        return value, cells
+
+    def _layers(self, symbol, which, n_all, shape, dtype):
+        """one layer / field of a grid as numpy `shape`, or with which=None the first n_all of them [n_all, *shape] (host copies)"""
+        idx = range(int(n_all)) if which is None else [int(which)]
+        out = np.zeros((len(idx),) + shape, dtype)
+        for j, l in enumerate(idx):
+            self._chk(getattr(self.L, symbol)(self.h, l, _ptr(out[j])))
+        return out if which is None else out[0]
+
+    def _counts(self, symbol, k, *args):
+        """the k 64-bit counts symbol(h, *args, out) writes, as a tuple of ints"""
+        out = (C.c_longlong * k)()
+        self._chk(getattr(self.L, symbol)(self.h, *args, C.cast(out, C.c_void_p)))
+        return tuple(int(v) for v in out)
+
+    def _list(self, symbol, dtype, device=None, device_symbol=None):
+        """the records of a list of the last build: asked for its length with no room (which synchronises the handle's stream and raises
+        on a stale snapshot), then copied to numpy `dtype` [n] -- or with device= handed out in place as int32 columns"""
+        n = C.c_int(0)
+        self._chk(getattr(self.L, symbol)(self.h, 0, None, C.byref(n)))
+        if device is not None:
+            return self._span(device, device_symbol, (n.value, dtype.itemsize // 4))
+        out = np.zeros(n.value, dtype)
+        if n.value:
+            self._chk(getattr(self.L, symbol)(self.h, n.value, _ptr(out), C.byref(n)))
+        return out
+
+    def _span(self, device, symbol, shape):
+        """an int32 tensor of `shape` over the buffer symbol(h) names, without a copy, torch's current stream ordered behind the handle's;
+        an empty tensor of its own where the shape holds nothing.  The caller has read the shape from a synchronised snapshot."""
+        import torch
+        dev = torch.device(device)
+        _, after = self._handle_stream_order(dev)
+        after()
+        if 0 in shape:
+            return torch.empty(shape, dtype=torch.int32, device=dev)
+        return torch.as_tensor(_DeviceSpan(getattr(self.L, symbol)(self.h), shape, "<i4"), device=dev)
+
     def query_occupancy(self, q, radius=0.0, world=False, outside=1.0):
         """value of every sample {x, y, z, t} of q ([n, 4] float32): the maximum over the own voxel and the voxel centres within
         `radius` of the current mass (t < 0) or of the future status at the first horizon >= t, `outside` for what lies outside
         the map.  A numpy array goes through the host entry point (synchronous) and returns numpy; a torch tensor on the GPU goes
         through the device entry point: the result is a tensor on the same device, enqueued on the handle's stream and ordered
         with torch's current stream both ways (no host synchronisation; none needed when the handle is on torch's stream)."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(q):
-            import torch
-            q = self._device_samples(q, (4,), "query_occupancy")
-            n = q.numel() // 4
-            out = torch.empty(n, dtype=torch.float32, device=q.device)
-            self._chk(self.L.dspmap_init_device(self.h))   # (the handle's stream exists from here on)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_query_occupancy_device(self.h, n, q.data_ptr(), float(radius), flags, float(outside), out.data_ptr()))
-            after()
-            return out
-        q = np.ascontiguousarray(q, np.float32)
-        if q.shape[-1:] != (4,):
-            raise ValueError("query_occupancy: samples of shape [n, 4]")
-        n = q.size // 4
-        out = np.zeros(n, np.float32)
-        self._chk(self.L.dspmap_query_occupancy(self.h, n, _ptr(q), float(radius), flags, float(outside), _ptr(out)))
-        return out
+        return self._query("dspmap_query_occupancy", q, np.float32, (float(radius), QUERY_WORLD if world else 0, float(outside)), init_device=True)
 
     def trajectory_risk(self, samples, radius=0.0, world=False, outside=1.0, threshold=0.5):
         """per trajectory of samples ([K, S, 4] float32, trajectory-major): sequential fp32 sum, max, first sample > threshold (-1:
         none) and the samples outside the map of the values query_occupancy gives.  numpy in -> structured numpy (RISK_DTYPE) out
         (synchronous); a torch tensor on the GPU -> dict of tensors 'sum', 'max' (float32), 'first_over', 'n_outside' (int32) on the
         same device, enqueued on the handle's stream."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(samples):
-            import torch
-            q = self._device_samples(samples, (4,), "trajectory_risk")
-            if q.dim() != 3:
-                raise ValueError("trajectory_risk: samples of shape [K, S, 4]")
-            k, s = int(q.shape[0]), int(q.shape[1])
-            raw = torch.empty((k, 4), dtype=torch.int32, device=q.device)
-            self._chk(self.L.dspmap_init_device(self.h))
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_trajectory_risk_device(self.h, k, s, q.data_ptr(), float(radius), flags, float(outside),
-                                                           float(threshold), raw.data_ptr()))
-            after()
-            return {"sum": raw[:, 0].view(torch.float32), "max": raw[:, 1].view(torch.float32),
-                    "first_over": raw[:, 2], "n_outside": raw[:, 3]}
-        q = np.ascontiguousarray(samples, np.float32)
-        if q.ndim != 3 or q.shape[2] != 4:
-            raise ValueError("trajectory_risk: samples of shape [K, S, 4]")
-        k, s = q.shape[0], q.shape[1]
-        out = np.zeros(k, RISK_DTYPE)
-        self._chk(self.L.dspmap_trajectory_risk(self.h, k, s, _ptr(q), float(radius), flags, float(outside), float(threshold), _ptr(out)))
-        return out
+        q, _, dev = self._input(samples, 4, "trajectory_risk", "samples of shape [K, S, 4]", ndim=3)
+        k, s = int(q.shape[0]), int(q.shape[1])
+        out = self._alloc(dev, k, RISK_DTYPE)
+        self._call(dev, "dspmap_trajectory_risk", k, s, self._p(q), float(radius), QUERY_WORLD if world else 0, float(outside), float(threshold),
+                   self._p(out), init_device=True)
+        return self._fields(out, RISK_DTYPE, dev)
 
     # -- distance fields (extension; semantics in include/dspmap.h next to dspmap_build_distance_field)
     def build_distance_field(self, threshold, max_voxels, outside_occupied=False):
@@ -709,12 +796,7 @@ class DSPMap:
 
     def distance_field(self, layer=None):
         """the field of one layer as numpy [nz, ny, nx], or of all layers [L, nz, ny, nx] (synchronous host copies)"""
-        shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
-        layers = range(self.T + 1) if layer is None else [int(layer)]
-        out = np.zeros((len(layers),) + shape, np.float32)
-        for j, l in enumerate(layers):
-            self._chk(self.L.dspmap_get_distance_field(self.h, l, _ptr(out[j])))
-        return out if layer is None else out[0]
+        return self._layers("dspmap_get_distance_field", layer, self.T + 1, (self.cfg.nz, self.cfg.ny, self.cfg.nx), np.float32)
 
     def distance_field_ptr(self):
         """device address of the [L][V] float32 field, or None when there is none / it is stale"""
@@ -726,27 +808,7 @@ class DSPMap:
         differences; `outside` and a zero gradient for what lies outside the map.  numpy in -> numpy out (synchronous); a torch tensor
         on the GPU -> tensors on the same device, enqueued on the handle's stream and ordered with torch's current stream like
         query_occupancy.  Returns (dist, grad) or dist."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(q):
-            import torch
-            q = self._device_samples(q, (4,), "query_distance")
-            n = q.numel() // 4
-            dist = torch.empty(n, dtype=torch.float32, device=q.device)
-            g = torch.empty((n, 3), dtype=torch.float32, device=q.device) if grad else None
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_query_distance_device(self.h, n, q.data_ptr(), flags, float(outside), dist.data_ptr(),
-                                                          g.data_ptr() if grad else None))
-            after()
-            return (dist, g) if grad else dist
-        q = np.ascontiguousarray(q, np.float32)
-        if q.shape[-1:] != (4,):
-            raise ValueError("query_distance: samples of shape [n, 4]")
-        n = q.size // 4
-        dist = np.zeros(n, np.float32)
-        g = np.zeros((n, 3), np.float32) if grad else None
-        self._chk(self.L.dspmap_query_distance(self.h, n, _ptr(q), flags, float(outside), _ptr(dist), _ptr(g)))
-        return (dist, g) if grad else dist
+        return self._query("dspmap_query_distance", q, np.float32, (QUERY_WORLD if world else 0, float(outside)), grad=bool(grad))
 
     # -- segment casts (extension; semantics in include/dspmap.h next to dspmap_build_cast_grid)
     def build_cast_grid(self, threshold, inflate_voxels=0):
@@ -758,12 +820,7 @@ class DSPMap:
     def cast_grid(self, layer=None):
         """the grid of one layer as numpy uint64 [nz, ny, W], W = ceil(nx / 64), bit (x & 63) of word (x >> 6) = voxel x of the row; or
         of all layers [L, nz, ny, W] (synchronous host copies)"""
-        shape = (self.cfg.nz, self.cfg.ny, (self.cfg.nx + 63) // 64)
-        layers = range(self.T + 1) if layer is None else [int(layer)]
-        out = np.zeros((len(layers),) + shape, np.uint64)
-        for j, l in enumerate(layers):
-            self._chk(self.L.dspmap_get_cast_grid(self.h, l, _ptr(out[j])))
-        return out if layer is None else out[0]
+        return self._layers("dspmap_get_cast_grid", layer, self.T + 1, (self.cfg.nz, self.cfg.ny, (self.cfg.nx + 63) // 64), np.uint64)
 
     def cast_grid_ptr(self):
         """device address of the [L][nz][ny][W] uint64 grid, or None when there is none / it is stale"""
@@ -775,24 +832,10 @@ class DSPMap:
         structured numpy (HIT_DTYPE: s, voxel, layer, status = CAST_*) out, synchronous; a torch tensor on the GPU -> dict of tensors
         's' (float32), 'voxel', 'layer', 'status' (int32) on the same device, enqueued on the handle's stream and ordered with torch's
         current stream like query_occupancy."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(seg):
-            import torch
-            q = self._device_samples(seg, (8,), "cast_segments")
-            n = q.numel() // 8
-            raw = torch.empty((n, 4), dtype=torch.int32, device=q.device)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_cast_segments_device(self.h, n, q.data_ptr(), flags, raw.data_ptr()))
-            after()
-            return {"s": raw[:, 0].view(torch.float32), "voxel": raw[:, 1], "layer": raw[:, 2], "status": raw[:, 3]}
-        q = np.ascontiguousarray(seg, np.float32)
-        if q.shape[-1:] != (8,):
-            raise ValueError("cast_segments: segments of shape [n, 8]")
-        n = q.size // 8
-        out = np.zeros(n, HIT_DTYPE)
-        self._chk(self.L.dspmap_cast_segments(self.h, n, _ptr(q), flags, _ptr(out)))
-        return out
+        q, n, dev = self._input(seg, 8, "cast_segments", "segments of shape [n, 8]")
+        out = self._alloc(dev, n, HIT_DTYPE)
+        self._call(dev, "dspmap_cast_segments", n, self._p(q), QUERY_WORLD if world else 0, self._p(out))
+        return self._fields(out, HIT_DTYPE, dev)
 
     # -- free boxes in the cast grid (extension; semantics in include/dspmap.h next to dspmap_grow_boxes)
     def grow_boxes(self, seeds, max_grow, world=False, with_current=False):
@@ -804,23 +847,10 @@ class DSPMap:
         enqueued on the handle's stream and ordered with torch's current stream like query_occupancy."""
         flags = (QUERY_WORLD if world else 0) | (BOX_WITH_CURRENT if with_current else 0)
         g = (C.c_int * 3)(*[int(v) for v in max_grow])
-        if self._is_device_tensor(seeds):
-            import torch
-            q = self._device_samples(seeds, (8,), "grow_boxes")
-            n = q.numel() // 8
-            raw = torch.empty((n, 8), dtype=torch.int32, device=q.device)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_grow_boxes_device(self.h, n, q.data_ptr(), C.cast(g, C.c_void_p), flags, raw.data_ptr()))
-            after()
-            return {"lo": raw[:, 0:3], "hi": raw[:, 3:6], "status": raw[:, 6], "stop": raw[:, 7]}
-        q = np.ascontiguousarray(seeds, np.float32)
-        if q.shape[-1:] != (8,):
-            raise ValueError("grow_boxes: seeds of shape [n, 8]")
-        n = q.size // 8
-        out = np.zeros(n, BOX_DTYPE)
-        self._chk(self.L.dspmap_grow_boxes(self.h, n, _ptr(q), C.cast(g, C.c_void_p), flags, _ptr(out)))
-        return out
+        q, n, dev = self._input(seeds, 8, "grow_boxes", "seeds of shape [n, 8]")
+        out = self._alloc(dev, n, BOX_DTYPE)
+        self._call(dev, "dspmap_grow_boxes", n, self._p(q), C.cast(g, C.c_void_p), flags, self._p(out))
+        return self._fields(out, BOX_DTYPE, dev)
 
     def box_bounds(self, boxes):
         """metric corners (lo_m, hi_m), float32 [n, 3] each, of boxes (BOX_DTYPE, or the dict grow_boxes returns for device input) in the
@@ -874,30 +904,16 @@ class DSPMap:
     def _build_reach(self, timeline, sources, n_fields, t_start, step_seconds, max_steps, world, with_current, device_sets):
         """build_reach_fields (timeline False) / build_reach_timeline (True): the same argument list on either pair of entry points"""
         flags = (QUERY_WORLD if world else 0) | (REACH_WITH_CURRENT if with_current else 0) | (REACH_DEVICE_SETS if device_sets else 0)
-        if self._is_device_tensor(sources):
-            q = self._reach_points_device(sources, "build_reach_fields")
-            n = q.numel() // 4
-            before, after = self._handle_stream_order(q.device)
-            before()
-            fn = self.L.dspmap_build_reach_timeline_device if timeline else self.L.dspmap_build_reach_fields_device
-            self._chk(fn(self.h, int(n_fields), n, q.data_ptr(), float(t_start), float(step_seconds), int(max_steps), flags))
-            after()
-            return
-        q = self._reach_points(sources, "build_reach_fields")
-        fn = self.L.dspmap_build_reach_timeline if timeline else self.L.dspmap_build_reach_fields
-        self._chk(fn(self.h, int(n_fields), len(q), _ptr(q) if len(q) else None, float(t_start), float(step_seconds), int(max_steps), flags))
+        q, n, dev = self._input(sources, 4, "build_reach_fields")
+        self._call(dev, "dspmap_build_reach_timeline" if timeline else "dspmap_build_reach_fields", int(n_fields), n,
+                   self._p(q, n > 0 or dev is not None), float(t_start), float(step_seconds), int(max_steps), flags)
 
     def reach_field(self, field=None, n_fields=None):
         """the values of one field of the last build as numpy uint16 [nz, ny, nx] (REACH_UNREACHED where the front never came), or with
         field=None those of the first n_fields fields [n_fields, nz, ny, nx] (synchronous host copies)"""
-        shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
         if field is None and n_fields is None:
             raise ValueError("reach_field: a field, or n_fields for all of them")
-        fields = range(int(n_fields)) if field is None else [int(field)]
-        out = np.zeros((len(fields),) + shape, np.uint16)
-        for j, f in enumerate(fields):
-            self._chk(self.L.dspmap_get_reach_field(self.h, f, _ptr(out[j])))
-        return out if field is None else out[0]
+        return self._layers("dspmap_get_reach_field", field, n_fields, (self.cfg.nz, self.cfg.ny, self.cfg.nx), np.uint16)
 
     def reach_fields_ptr(self):
         """device address of the [n_fields][V] uint16 values, or None when there are none / they are stale"""
@@ -905,34 +921,13 @@ class DSPMap:
 
     def reach_storage(self):
         """(fields of the last build whose wave sets lived in LDS, ... in device memory)"""
-        out = (C.c_longlong * 2)()
-        self._chk(self.L.dspmap_debug_reach_storage(self.h, C.cast(out, C.c_void_p)))
-        return int(out[0]), int(out[1])
+        return self._counts("dspmap_debug_reach_storage", 2)
 
     def reach_paths(self, starts, max_len, world=False):
         """descend a time-invariant build from starts {x, y, z, field}: (steps [n] int32: the start's value, -1 unreached, -2 outside the
         map, -3 invalid; cells [n, max_len] int32: voxel indices from the start's cell to a cell of value 0, -1 behind the end).  numpy in
         -> numpy out, synchronous; a torch tensor on the GPU -> tensors on the same device, enqueued like build_reach_fields."""
-        flags = QUERY_WORLD if world else 0
-        max_len = int(max_len)
-        if self._is_device_tensor(starts):
-            import torch
-            q = self._reach_points_device(starts, "reach_paths")
-            n = q.numel() // 4
-            steps = torch.empty(n, dtype=torch.int32, device=q.device)
-            cells = torch.empty((n, max(max_len, 0)), dtype=torch.int32, device=q.device)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_reach_paths_device(self.h, n, q.data_ptr(), max_len, flags, steps.data_ptr(),
-                                                       cells.data_ptr() if max_len > 0 else None))
-            after()
-            return steps, cells
-        q = self._reach_points(starts, "reach_paths")
-        steps = np.zeros(len(q), np.int32)
-        cells = np.zeros((len(q), max(max_len, 0)), np.int32)
-        self._chk(self.L.dspmap_reach_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags, _ptr(steps) if len(q) else None,
-                                            _ptr(cells) if max_len > 0 else None))
-        return steps, cells
+        return self._paths("dspmap_reach_paths", starts, max_len, world)
 
     # -- space-time paths (extension; semantics in include/dspmap.h next to dspmap_build_reach_timeline)
     def build_reach_timeline(self, sources, n_fields=1, t_start=-1.0, step_seconds=0.0, max_steps=REACH_MAX_STEPS, world=False,
@@ -967,26 +962,7 @@ class DSPMap:
         arrival v, -1 unreached, -2 outside the map, -3 invalid; cells [n, max_len] int32: the voxel occupied at step v - j, waits
         included, down to a source cell at step 0, -1 behind the end).  numpy in -> numpy out, synchronous; a torch tensor on the GPU ->
         tensors on the same device, enqueued like reach_paths."""
-        flags = QUERY_WORLD if world else 0
-        max_len = int(max_len)
-        if self._is_device_tensor(starts):
-            import torch
-            q = self._reach_points_device(starts, "reach_timeline_paths")
-            n = q.numel() // 4
-            steps = torch.empty(n, dtype=torch.int32, device=q.device)
-            cells = torch.empty((n, max(max_len, 0)), dtype=torch.int32, device=q.device)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_reach_timeline_paths_device(self.h, n, q.data_ptr(), max_len, flags, steps.data_ptr(),
-                                                                cells.data_ptr() if max_len > 0 else None))
-            after()
-            return steps, cells
-        q = self._reach_points(starts, "reach_timeline_paths")
-        steps = np.zeros(len(q), np.int32)
-        cells = np.zeros((len(q), max(max_len, 0)), np.int32)
-        self._chk(self.L.dspmap_reach_timeline_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags,
-                                                     _ptr(steps) if len(q) else None, _ptr(cells) if max_len > 0 else None))
-        return steps, cells
+        return self._paths("dspmap_reach_timeline_paths", starts, max_len, world)
 
     # -- cost-to-go fields (extension; semantics in include/dspmap.h next to dspmap_build_cost_fields)
     @staticmethod
@@ -1005,31 +981,17 @@ class DSPMap:
         value in the distance field lies under; a cell's value is its exact minimum cost if <= max_cost, else COST_UNREACHED.  Needs the
         cast grid and, with bands, the distance field.  numpy sources -> synchronous; a torch tensor on the GPU -> enqueued like
         build_reach_fields.  Read the result with cost_field / cost_fields_ptr / cost_weights, descend it with cost_paths."""
-        flags = QUERY_WORLD if world else 0
         b = self._cost_bands(bands)
-        if self._is_device_tensor(sources):
-            q = self._reach_points_device(sources, "build_cost_fields")
-            n = q.numel() // 4
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_build_cost_fields_device(self.h, int(n_fields), n, q.data_ptr(), float(t), C.addressof(b), int(max_cost), flags))
-            after()
-            return
-        q = self._reach_points(sources, "build_cost_fields")
-        self._chk(self.L.dspmap_build_cost_fields(self.h, int(n_fields), len(q), _ptr(q) if len(q) else None, float(t), C.addressof(b),
-                                                  int(max_cost), flags))
+        q, n, dev = self._input(sources, 4, "build_cost_fields")
+        self._call(dev, "dspmap_build_cost_fields", int(n_fields), n, self._p(q, n > 0 or dev is not None), float(t), C.addressof(b), int(max_cost),
+                   QUERY_WORLD if world else 0)
 
     def cost_field(self, field=None, n_fields=None):
         """the values of one field of the last cost build as numpy uint16 [nz, ny, nx] (COST_UNREACHED where the cost exceeds max_cost or
         no path exists), or with field=None those of the first n_fields fields [n_fields, nz, ny, nx] (synchronous host copies)"""
-        shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
         if field is None and n_fields is None:
             raise ValueError("cost_field: a field, or n_fields for all of them")
-        fields = range(int(n_fields)) if field is None else [int(field)]
-        out = np.zeros((len(fields),) + shape, np.uint16)
-        for j, f in enumerate(fields):
-            self._chk(self.L.dspmap_get_cost_field(self.h, f, _ptr(out[j])))
-        return out if field is None else out[0]
+        return self._layers("dspmap_get_cost_field", field, n_fields, (self.cfg.nz, self.cfg.ny, self.cfg.nx), np.uint16)
 
     def cost_fields_ptr(self):
         """device address of the [n_fields][V] uint16 values, or None when there are none / they are stale"""
@@ -1046,26 +1008,7 @@ class DSPMap:
         map, -3 invalid; cells [n, max_len] int32: voxel indices from the start's cell to a cell of value 0, -1 behind the end) -- what
         shorten_paths takes as (steps, cells).  numpy in -> numpy out, synchronous; a torch tensor on the GPU -> tensors on the same
         device, enqueued like build_cost_fields."""
-        flags = QUERY_WORLD if world else 0
-        max_len = int(max_len)
-        if self._is_device_tensor(starts):
-            import torch
-            q = self._reach_points_device(starts, "cost_paths")
-            n = q.numel() // 4
-            cost = torch.empty(n, dtype=torch.int32, device=q.device)
-            cells = torch.empty((n, max(max_len, 0)), dtype=torch.int32, device=q.device)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_cost_paths_device(self.h, n, q.data_ptr(), max_len, flags, cost.data_ptr(),
-                                                      cells.data_ptr() if max_len > 0 else None))
-            after()
-            return cost, cells
-        q = self._reach_points(starts, "cost_paths")
-        cost = np.zeros(len(q), np.int32)
-        cells = np.zeros((len(q), max(max_len, 0)), np.int32)
-        self._chk(self.L.dspmap_cost_paths(self.h, len(q), _ptr(q) if len(q) else None, max_len, flags, _ptr(cost) if len(q) else None,
-                                           _ptr(cells) if max_len > 0 else None))
-        return cost, cells
+        return self._paths("dspmap_cost_paths", starts, max_len, world)
 
     # -- shortened paths (extension; semantics in include/dspmap.h next to dspmap_shorten_paths)
     def shorten_paths(self, steps, cells, t_start=-1.0, step_seconds=0.0, window=SHORTEN_MAX_WINDOW, max_seg=None):
@@ -1083,32 +1026,18 @@ class DSPMap:
             if cells.dtype != torch.int32 or cells.dim() != 2 or not self._is_device_tensor(steps) or steps.dtype != torch.int32 or \
                     steps.device != cells.device or steps.numel() != cells.shape[0]:
                 raise ValueError("shorten_paths: int32 tensors steps [n] and cells [n, max_len] on one device")
-            c, s = cells.contiguous(), steps.contiguous().view(-1)
-            n, max_len = int(c.shape[0]), int(c.shape[1])
-            ms = max(max_len - 1, 0) if max_seg is None else int(max_seg)
-            info = torch.empty((n, 4), dtype=torch.int32, device=c.device)
-            seg = torch.empty((n, max(ms, 0), 8), dtype=torch.float32, device=c.device)
-            end = torch.empty((n, max(ms, 0)), dtype=torch.int32, device=c.device)
-            before, after = self._handle_stream_order(c.device)
-            before()
-            self._chk(self.L.dspmap_shorten_paths_device(self.h, n, max_len, s.data_ptr() if n else None, c.data_ptr() if n else None,
-                                                         float(t_start), float(step_seconds), int(window), ms, 0,
-                                                         info.data_ptr() if n else None, seg.data_ptr() if n and ms > 0 else None,
-                                                         end.data_ptr() if n and ms > 0 else None))
-            after()
-            return info, seg, end
-        c = np.ascontiguousarray(cells, np.int32)
-        s = np.ascontiguousarray(steps, np.int32).reshape(-1)
-        if c.ndim != 2 or len(s) != c.shape[0]:
-            raise ValueError("shorten_paths: steps [n] and cells [n, max_len]")
-        n, max_len = c.shape
+            c, s, dev = cells.contiguous(), steps.contiguous().view(-1), cells.device
+        else:
+            c, s, dev = np.ascontiguousarray(cells, np.int32), np.ascontiguousarray(steps, np.int32).reshape(-1), None
+            if c.ndim != 2 or len(s) != c.shape[0]:
+                raise ValueError("shorten_paths: steps [n] and cells [n, max_len]")
+        n, max_len = int(c.shape[0]), int(c.shape[1])
         ms = max(max_len - 1, 0) if max_seg is None else int(max_seg)
-        info = np.zeros(n, PATH_INFO_DTYPE)
-        seg = np.zeros((n, max(ms, 0), 8), np.float32)
-        end = np.zeros((n, max(ms, 0)), np.int32)
-        self._chk(self.L.dspmap_shorten_paths(self.h, n, max_len, _ptr(s) if n else None, _ptr(c) if n else None, float(t_start),
-                                              float(step_seconds), int(window), ms, 0, _ptr(info) if n else None,
-                                              _ptr(seg) if n and ms > 0 else None, _ptr(end) if n and ms > 0 else None))
+        info = self._alloc(dev, n, PATH_INFO_DTYPE)
+        seg = self._alloc(dev, (n, max(ms, 0), 8), np.float32)
+        end = self._alloc(dev, (n, max(ms, 0)), np.int32)
+        self._call(dev, "dspmap_shorten_paths", n, max_len, self._p(s, n), self._p(c, n), float(t_start), float(step_seconds), int(window), ms, 0,
+                   self._p(info, n), self._p(seg, n and ms > 0), self._p(end, n and ms > 0))
         return info, seg, end
 
     # -- occupancy forecast at caller-chosen times (extension; semantics in include/dspmap.h next to dspmap_build_forecast)
@@ -1130,11 +1059,7 @@ class DSPMap:
     def forecast(self, layer=None):
         """one layer as numpy [V] (the reference's voxel order), or all layers [n, V] (synchronous host copies)"""
         V = self.L.dspmap_voxel_num(self.h)
-        layers = range(len(self.forecast_times())) if layer is None else [int(layer)]
-        out = np.zeros((len(layers), V), np.float32)
-        for j, l in enumerate(layers):
-            self._chk(self.L.dspmap_get_forecast(self.h, l, _ptr(out[j])))
-        return out if layer is None else out[0]
+        return self._layers("dspmap_get_forecast", layer, len(self.forecast_times()) if layer is None else 0, (V,), np.float32)
 
     def forecast_ptr(self):
         """device address of the [n][V] float32 layers, or None when there are none / they are stale"""
@@ -1146,23 +1071,7 @@ class DSPMap:
         numpy in -> numpy out (synchronous); a torch tensor on the GPU -> a tensor on the same device, enqueued on the handle's stream
         and ordered with torch's current stream like query_occupancy."""
         flags = (QUERY_WORLD if world else 0) | (FORECAST_LERP if lerp else 0)
-        if self._is_device_tensor(q):
-            import torch
-            q = self._device_samples(q, (4,), "query_forecast")
-            n = q.numel() // 4
-            out = torch.empty(n, dtype=torch.float32, device=q.device)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_query_forecast_device(self.h, n, q.data_ptr(), flags, float(outside), out.data_ptr()))
-            after()
-            return out
-        q = np.ascontiguousarray(q, np.float32)
-        if q.shape[-1:] != (4,):
-            raise ValueError("query_forecast: samples of shape [n, 4]")
-        n = q.size // 4
-        out = np.zeros(n, np.float32)
-        self._chk(self.L.dspmap_query_forecast(self.h, n, _ptr(q), flags, float(outside), _ptr(out)))
-        return out
+        return self._query("dspmap_query_forecast", q, np.float32, (flags, float(outside)))
 
     # -- known-space layer (extension; semantics in include/dspmap.h next to dspmap_known_integrate)
     def integrate_known(self, max_range=float("inf")):
@@ -1185,25 +1094,7 @@ class DSPMap:
         """age of the cell that holds every sample {x, y, z, t} of q ([n, 4] float32; t is ignored), -1 outside the map, for a NaN
         coordinate or for a cell never seen.  numpy in -> numpy int32 out (synchronous); a torch tensor on the GPU -> an int32 tensor on
         the same device, enqueued on the handle's stream and ordered with torch's current stream like query_occupancy."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(q):
-            import torch
-            q = self._device_samples(q, (4,), "query_known")
-            n = q.numel() // 4
-            out = torch.empty(n, dtype=torch.int32, device=q.device)
-            self._chk(self.L.dspmap_init_device(self.h))   # (the handle's stream exists from here on)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_query_known_device(self.h, n, q.data_ptr(), flags, out.data_ptr()))
-            after()
-            return out
-        q = np.ascontiguousarray(q, np.float32)
-        if q.shape[-1:] != (4,):
-            raise ValueError("query_known: samples of shape [n, 4]")
-        n = q.size // 4
-        out = np.zeros(n, np.int32)
-        self._chk(self.L.dspmap_query_known(self.h, n, _ptr(q), flags, _ptr(out)))
-        return out
+        return self._query("dspmap_query_known", q, np.int32, (QUERY_WORLD if world else 0,), init_device=True)
 
     def mask_cast_grid(self, max_age):
         """OR "unknown" into every layer of the valid cast grid: the bit of each voxel never seen or seen more than max_age frames ago.
@@ -1212,9 +1103,7 @@ class DSPMap:
 
     def known_stats(self, max_age):
         """(cells with 0 <= age <= max_age, cells stamped by the current frame)"""
-        out = (C.c_longlong * 2)()
-        self._chk(self.L.dspmap_known_stats(self.h, int(max_age), C.cast(out, C.c_void_p)))
-        return int(out[0]), int(out[1])
+        return self._counts("dspmap_known_stats", 2, int(max_age))
 
     def view(self):
         """(planes_h [np_h + 1, 3], planes_v [np_v + 1, 3], maxlen [np_h, np_v]) of the last frame: the rotated boundary-plane normals and
@@ -1234,23 +1123,9 @@ class DSPMap:
         numpy in -> structured numpy (VIEW_SCORE_DTYPE, status = VIEW_*) out, synchronous; a torch tensor on the GPU -> an int32 [n, 4]
         tensor {n_seen, n_unknown, n_returns, status} on the same device, enqueued on the handle's stream and ordered with torch's
         current stream like query_known."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(views):
-            import torch
-            q = self._device_samples(views, (9,), "score_views")
-            n = q.numel() // 9
-            out = torch.empty((n, 4), dtype=torch.int32, device=q.device)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_score_views_device(self.h, n, q.data_ptr(), int(max_age), flags, out.data_ptr()))
-            after()
-            return out
-        q = np.ascontiguousarray(views, np.float32)
-        if q.shape[-1:] != (9,):
-            raise ValueError("score_views: views of shape [n, 9]")
-        n = q.size // 9
-        out = np.zeros(n, VIEW_SCORE_DTYPE)
-        self._chk(self.L.dspmap_score_views(self.h, n, _ptr(q), int(max_age), flags, _ptr(out)))
+        q, n, dev = self._input(views, 9, "score_views", "views of shape [n, 9]")
+        out = self._alloc(dev, n, VIEW_SCORE_DTYPE)
+        self._call(dev, "dspmap_score_views", n, self._p(q), int(max_age), QUERY_WORLD if world else 0, self._p(out))
         return out
 
     # -- joint gain of views (extension; semantics in include/dspmap.h next to dspmap_score_view_sets)
@@ -1261,28 +1136,11 @@ class DSPMap:
         (VIEW_SET_SCORE_DTYPE [n_sets], and VIEW_SCORE_DTYPE [n_sets, set_size]) out, synchronous; a torch tensor on the GPU -> int32
         tensors [n_sets, 4] (and [n_sets, set_size, 4]) on the same device, enqueued on the handle's stream and ordered with torch's
         current stream like score_views."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(views):
-            import torch
-            q = self._device_samples(views, (9,), "score_view_sets")
-            if q.dim() != 3:
-                raise ValueError("score_view_sets: views of shape [n_sets, set_size, 9]")
-            ns, sz = int(q.shape[0]), int(q.shape[1])
-            out = torch.empty((ns, 4), dtype=torch.int32, device=q.device)
-            sc = torch.empty((ns, sz, 4), dtype=torch.int32, device=q.device) if scores else None
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_score_view_sets_device(self.h, ns, sz, q.data_ptr(), int(max_age), flags, out.data_ptr(),
-                                                           sc.data_ptr() if scores else None))
-            after()
-            return (out, sc) if scores else out
-        q = np.ascontiguousarray(views, np.float32)
-        if q.ndim != 3 or q.shape[-1] != 9:
-            raise ValueError("score_view_sets: views of shape [n_sets, set_size, 9]")
-        ns, sz = q.shape[:2]
-        out = np.zeros(ns, VIEW_SET_SCORE_DTYPE)
-        sc = np.zeros((ns, sz), VIEW_SCORE_DTYPE) if scores else None
-        self._chk(self.L.dspmap_score_view_sets(self.h, ns, sz, _ptr(q), int(max_age), flags, _ptr(out), _ptr(sc) if scores else None))
+        q, _, dev = self._input(views, 9, "score_view_sets", "views of shape [n_sets, set_size, 9]", ndim=3)
+        ns, sz = int(q.shape[0]), int(q.shape[1])
+        out = self._alloc(dev, ns, VIEW_SET_SCORE_DTYPE)
+        sc = self._alloc(dev, (ns, sz), VIEW_SCORE_DTYPE) if scores else None
+        self._call(dev, "dspmap_score_view_sets", ns, sz, self._p(q), int(max_age), QUERY_WORLD if world else 0, self._p(out), self._p(sc))
         return (out, sc) if scores else out
 
     def select_views(self, views, k, max_age, n_fixed=0, min_gain=1, world=False, scores=False):
@@ -1292,29 +1150,11 @@ class DSPMap:
         the first empty round on.  scores=True: also every view's score_views score [n].  numpy in -> structured numpy out,
         synchronous; a torch tensor on the GPU -> int32 tensors [k, 4] (and [n, 4]) on the same device, every round enqueued on the
         handle's stream without a host read in between, ordered with torch's current stream like score_views."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(views):
-            import torch
-            q = self._device_samples(views, (9,), "select_views")
-            if q.dim() != 2:
-                raise ValueError("select_views: views of shape [n, 9]")
-            n = int(q.shape[0])
-            out = torch.empty((max(int(k), 0), 4), dtype=torch.int32, device=q.device)
-            sc = torch.empty((n, 4), dtype=torch.int32, device=q.device) if scores else None
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_select_views_device(self.h, n, q.data_ptr(), int(n_fixed), int(max_age), flags, int(k), int(min_gain),
-                                                        out.data_ptr(), sc.data_ptr() if scores else None))
-            after()
-            return (out, sc) if scores else out
-        q = np.ascontiguousarray(views, np.float32)
-        if q.ndim != 2 or q.shape[1] != 9:
-            raise ValueError("select_views: views of shape [n, 9]")
-        n = q.shape[0]
-        out = np.zeros(max(int(k), 0), VIEW_PICK_DTYPE)
-        sc = np.zeros(n, VIEW_SCORE_DTYPE) if scores else None
-        self._chk(self.L.dspmap_select_views(self.h, n, _ptr(q), int(n_fixed), int(max_age), flags, int(k), int(min_gain), _ptr(out),
-                                             _ptr(sc) if scores else None))
+        q, n, dev = self._input(views, 9, "select_views", "views of shape [n, 9]", ndim=2)
+        out = self._alloc(dev, max(int(k), 0), VIEW_PICK_DTYPE)
+        sc = self._alloc(dev, n, VIEW_SCORE_DTYPE) if scores else None
+        self._call(dev, "dspmap_select_views", n, self._p(q), int(n_fixed), int(max_age), QUERY_WORLD if world else 0, int(k), int(min_gain),
+                   self._p(out), self._p(sc))
         return (out, sc) if scores else out
 
     def view_rays(self, quat):
@@ -1350,9 +1190,7 @@ class DSPMap:
 
     def frontier_counts(self):
         """(n_cells, n_blocks, n_free) of the last build (synchronous)"""
-        out = (C.c_longlong * 3)()
-        self._chk(self.L.dspmap_frontier_counts(self.h, C.cast(out, C.c_void_p)))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._counts("dspmap_frontier_counts", 3)
 
     def frontier_grid(self):
         """the frontier bits as numpy uint64 [nz, ny, W] in the cast grid's word layout (synchronous host copy)"""
@@ -1360,45 +1198,21 @@ class DSPMap:
         self._chk(self.L.dspmap_get_frontier_grid(self.h, _ptr(out)))
         return out
 
-    def _frontier_device(self, device, which, ptr_fn, cols):
-        """the first n entries of a list of the last build as an int32 tensor over the handle's own buffer (no copy); n is read from
-        the device, which synchronises the handle's stream; torch's current stream is ordered behind it"""
-        import torch
-        n = self.frontier_counts()[which]   # (raises on a stale snapshot)
-        ptr = ptr_fn(self.h)
-        dev = torch.device(device)
-        _, after = self._handle_stream_order(dev)
-        after()
-        shape = (n, cols) if cols > 1 else (n,)
-        if n == 0:
-            return torch.empty(shape, dtype=torch.int32, device=dev)
-        return torch.as_tensor(_DeviceSpan(ptr, shape, "<i4"), device=dev)
-
     def frontier_cells(self, device=None):
         """the voxel indices of the frontier cells in ascending order: numpy int32 [n] (synchronous host copy); with device= (e.g. "cuda")
         an int32 tensor [n] over the handle's own device buffer, without a copy, ordered with torch's current stream like score_views.
         The tensor is valid until the next build_frontiers or close()."""
-        if device is not None:
-            return self._frontier_device(device, 0, self.L.dspmap_frontier_cells_device, 1)
-        n = C.c_int(0)
-        self._chk(self.L.dspmap_get_frontier_cells(self.h, 0, None, C.byref(n)))
-        out = np.zeros(n.value, np.int32)
-        if n.value:
-            self._chk(self.L.dspmap_get_frontier_cells(self.h, n.value, _ptr(out), C.byref(n)))
-        return out
+        if device is not None:   # (the count is read from the device, which synchronises the handle's stream and raises on a stale snapshot)
+            return self._span(device, "dspmap_frontier_cells_device", (self.frontier_counts()[0],))
+        return self._list("dspmap_get_frontier_cells", np.dtype(np.int32))
 
     def frontier_blocks(self, device=None):
         """the records of the non-empty blocks in ascending block index: structured numpy (FRONTIER_BLOCK_DTYPE) [k] (synchronous host
         copy); with device= an int32 tensor [k, 6] {block, count, sum_x, sum_y, sum_z, unknown_faces} over the handle's own device
         buffer, without a copy, as frontier_cells"""
         if device is not None:
-            return self._frontier_device(device, 1, self.L.dspmap_frontier_blocks_device, 6)
-        n = C.c_int(0)
-        self._chk(self.L.dspmap_get_frontier_blocks(self.h, 0, None, C.byref(n)))
-        out = np.zeros(n.value, FRONTIER_BLOCK_DTYPE)
-        if n.value:
-            self._chk(self.L.dspmap_get_frontier_blocks(self.h, n.value, _ptr(out), C.byref(n)))
-        return out
+            return self._span(device, "dspmap_frontier_blocks_device", (self.frontier_counts()[1], 6))
+        return self._list("dspmap_get_frontier_blocks", FRONTIER_BLOCK_DTYPE)
 
     def frontier_block_centers(self, min_count=1):
         """float32 [k, 3]: the centroid of the frontier cells of every block with at least min_count of them, in the map frame:
@@ -1422,29 +1236,14 @@ class DSPMap:
     def object_counts(self):
         """(n_objects, n_components, n_occupied) of the last build (synchronous): components with count >= min_cells -- also those past
         max_objects --, all components, set bits of the layer"""
-        out = (C.c_longlong * 3)()
-        self._chk(self.L.dspmap_object_counts(self.h, C.cast(out, C.c_void_p)))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._counts("dspmap_object_counts", 3)
 
     def objects(self, device=None):
         """the records the last build kept, in ascending label: structured numpy (OBJECT_DTYPE) [k], k = min(n_objects, max_objects)
         (synchronous host copy); with device= (e.g. "cuda") an int32 tensor [k, 22] over the handle's own device buffer, without a copy
         -- columns 0 .. 7 the ints, then the seven 64-bit fields as (low, high) pairs; `t[:, 8:].view(torch.int64)` gives them as [k, 7] --,
         ordered with torch's current stream like frontier_cells and valid until the next build_objects or close()."""
-        n = C.c_int(0)
-        self._chk(self.L.dspmap_get_objects(self.h, 0, None, C.byref(n)))   # (synchronises the handle's stream; raises on a stale snapshot)
-        if device is not None:
-            import torch
-            dev = torch.device(device)
-            _, after = self._handle_stream_order(dev)
-            after()
-            if n.value == 0:
-                return torch.empty((0, 22), dtype=torch.int32, device=dev)
-            return torch.as_tensor(_DeviceSpan(self.L.dspmap_objects_device(self.h), (n.value, 22), "<i4"), device=dev)
-        out = np.zeros(n.value, OBJECT_DTYPE)
-        if n.value:
-            self._chk(self.L.dspmap_get_objects(self.h, n.value, _ptr(out), C.byref(n)))
-        return out
+        return self._list("dspmap_get_objects", OBJECT_DTYPE, device, "dspmap_objects_device")
 
     def object_labels(self, device=None):
         """the label grid of the last build: numpy int32 [nz, ny, nx], per voxel the ordinal of its record in the list of objects (also an
@@ -1452,12 +1251,8 @@ class DSPMap:
         of that shape over the handle's own device buffer, without a copy, as objects()"""
         shape = (self.cfg.nz, self.cfg.ny, self.cfg.nx)
         if device is not None:
-            import torch
             self.object_counts()   # (synchronises the handle's stream; raises on a stale snapshot)
-            dev = torch.device(device)
-            _, after = self._handle_stream_order(dev)
-            after()
-            return torch.as_tensor(_DeviceSpan(self.L.dspmap_object_labels_device(self.h), shape, "<i4"), device=dev)
+            return self._span(device, "dspmap_object_labels_device", shape)
         out = np.zeros(shape, np.int32)
         self._chk(self.L.dspmap_get_object_labels(self.h, _ptr(out)))
         return out
@@ -1466,24 +1261,7 @@ class DSPMap:
         """the label-grid entry of the voxel that holds every sample {x, y, z, t} of q ([n, 4] float32; t is ignored), -1 outside the map
         or for a NaN coordinate.  numpy in -> numpy int32 out (synchronous); a torch tensor on the GPU -> an int32 tensor on the same
         device, enqueued on the handle's stream and ordered with torch's current stream like query_known."""
-        flags = QUERY_WORLD if world else 0
-        if self._is_device_tensor(q):
-            import torch
-            q = self._device_samples(q, (4,), "query_objects")
-            n = q.numel() // 4
-            out = torch.empty(n, dtype=torch.int32, device=q.device)
-            before, after = self._handle_stream_order(q.device)
-            before()
-            self._chk(self.L.dspmap_query_objects_device(self.h, n, q.data_ptr(), flags, out.data_ptr()))
-            after()
-            return out
-        q = np.ascontiguousarray(q, np.float32)
-        if q.shape[-1:] != (4,):
-            raise ValueError("query_objects: samples of shape [n, 4]")
-        n = q.size // 4
-        out = np.zeros(n, np.int32)
-        self._chk(self.L.dspmap_query_objects(self.h, n, _ptr(q), flags, _ptr(out)))
-        return out
+        return self._query("dspmap_query_objects", q, np.int32, (QUERY_WORLD if world else 0,))
 
     def object_states(self, objs):
         """what a planner takes from the records objs (OBJECT_DTYPE, what objects() returns), in the map frame: (centre [k, 3], box_lo
@@ -1517,29 +1295,14 @@ class DSPMap:
 
     def track_counts(self):
         """(n_tracks, n_matched, n_born, n_ended, n_pairs, next_id) of the last update (synchronous)"""
-        out = (C.c_longlong * 6)()
-        self._chk(self.L.dspmap_track_counts(self.h, C.cast(out, C.c_void_p)))
-        return tuple(int(v) for v in out)
+        return self._counts("dspmap_track_counts", 6)
 
     def tracks(self, device=None):
         """the tracks of the last update, one per record of objects(): structured numpy (TRACK_DTYPE) [k] (synchronous host copy); with
         device= (e.g. "cuda") an int32 tensor [k, 18] over the handle's own device buffer, without a copy -- columns 0 .. 9 the five
         64-bit fields as (low, high) pairs, `t[:, :10].view(torch.int64)` gives them as [k, 5], then the eight ints --, ordered with
         torch's current stream like objects() and valid until the next update_tracks, reset_tracks or close()."""
-        n = C.c_int(0)
-        self._chk(self.L.dspmap_get_tracks(self.h, 0, None, C.byref(n)))   # (synchronises the handle's stream; raises without an update)
-        if device is not None:
-            import torch
-            dev = torch.device(device)
-            _, after = self._handle_stream_order(dev)
-            after()
-            if n.value == 0:
-                return torch.empty((0, 18), dtype=torch.int32, device=dev)
-            return torch.as_tensor(_DeviceSpan(self.L.dspmap_tracks_device(self.h), (n.value, 18), "<i4"), device=dev)
-        out = np.zeros(n.value, TRACK_DTYPE)
-        if n.value:
-            self._chk(self.L.dspmap_get_tracks(self.h, n.value, _ptr(out), C.byref(n)))
-        return out
+        return self._list("dspmap_get_tracks", TRACK_DTYPE, device, "dspmap_tracks_device")
 
     def track_states(self, tracks, objs, dt):
         """what a planner takes from the tracks (TRACK_DTYPE) and their records objs (OBJECT_DTYPE) of the same update: (displacement

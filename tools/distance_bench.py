@@ -11,21 +11,15 @@ script with --builds-only).  Prints one JSON line per workload.  bench.py is not
 
     python tools/distance_bench.py [--reps 200] [--warmup 20] [--host-reps 5] [--builds-only] [--only B|L]
 """
-import argparse
-import importlib
 import json
-import os
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "dsp-map_amd"))
+import layer_bench as harness
+from layer_bench import WORKLOADS
 
-WORKLOADS = {"B": dict(nx=66, ny=66, nz=40, res=0.15, ppv=24), "L": dict(nx=132, ny=132, nz=60, res=0.15, ppv=9)}
 THRESHOLD = 0.2
 
 
@@ -48,40 +42,19 @@ def pass_bytes(V, T, R, ts=32):
 
 def run(D, scene, name, args):
     w = WORKLOADS[name]
-    m = D.DSPMap(D.make_config(seed=1234, **w))
-    m._chk(m.L.dspmap_init_device(m.h))
-    sc = scene.CorridorScene(w["nx"] * w["res"], w["ny"] * w["res"], w["nz"] * w["res"], seed=1234, device="cuda")
-    torch.use_deterministic_algorithms(True)
-    frames = [sc.frame(f / 30.0) + (f / 30.0,) for f in range(args.frames + args.host_reps)]
-    torch.use_deterministic_algorithms(False)
-    torch.cuda.synchronize()
-    st = torch.cuda.Stream()
-    m._chk(m.L.dspmap_set_stream(m.h, st.cuda_stream))
+    m, st = harness.open_map(D, scene, name, args.frames, spare=args.host_reps)
 
     def frame(f):
-        pts, pos, quat, t = frames[f]
+        """one of the frames behind the fill, for the host route"""
+        pts, pos, quat, t = m.scene_frames[f]
         if f:
             m.clearOccupancyMapPrediction()
         assert m.update_device(pts.data_ptr(), pts.shape[0], pos, t, quat) == 1
 
     def timed(fn, reps):
         """device time (us) of each of reps calls: events on the handle's stream around every call -> (median, min)"""
-        with torch.cuda.stream(st):
-            for _ in range(args.warmup):
-                fn()
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-            for e0, e1 in ev:
-                e0.record(st)
-                fn()
-                e1.record(st)
-            st.synchronize()
-        t = np.array([e0.elapsed_time(e1) * 1000.0 for e0, e1 in ev])
-        return round(float(np.median(t)), 2), round(float(t.min()), 2)
+        return harness.timed(st, [fn], reps, args.warmup)[0]
 
-    with torch.cuda.stream(st):
-        for f in range(args.frames):
-            frame(f)
-        st.synchronize()
     V, T = m.V, m.T
     out = {"workload": "%s: %dx%dx%d @ %.2f m, %d particles/voxel, %d frames of scene.py" % (name, w["nx"], w["ny"], w["nz"], w["res"], w["ppv"], args.frames),
            "layers": T + 1, "threshold": THRESHOLD}
@@ -138,20 +111,9 @@ def run(D, scene, name, args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--frames", type=int, default=20)
-    ap.add_argument("--host-reps", type=int, default=5)
+    ap = harness.parser(reps=200, warmup=20, frames=20, host_reps=5)
     ap.add_argument("--builds-only", action="store_true")
-    ap.add_argument("--only", choices=sorted(WORKLOADS), default=None)
-    args = ap.parse_args()
-    import build_ext
-    build_ext.build()
-    import dsp_map_amd as D
-    scene = importlib.import_module("dsp-map_amd.scene")
-    for name in ([args.only] if args.only else ["B", "L"]):
-        run(D, scene, name, args)
+    harness.main(run, ap)
 
 
 if __name__ == "__main__":

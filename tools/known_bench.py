@@ -12,63 +12,30 @@ the tool asserts that both routes stamp the same cells.  Prints one JSON line pe
 
     python tools/known_bench.py [--reps 200] [--warmup 3] [--host-reps 3] [--only B|L]
 """
-import argparse
-import importlib
 import json
-import os
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "dsp-map_amd"))
+import layer_bench as harness
+from layer_bench import WORKLOADS
 
-WORKLOADS = {"B": dict(nx=66, ny=66, nz=40, res=0.15, ppv=24), "L": dict(nx=132, ny=132, nz=60, res=0.15, ppv=9)}
 N_QUERY = 131072
 
 
 def run(D, scene, name, args):
     from tests import known_ref
     w = WORKLOADS[name]
-    m = D.DSPMap(D.make_config(seed=1234, **w))
-    m._chk(m.L.dspmap_init_device(m.h))
-    sc = scene.CorridorScene(w["nx"] * w["res"], w["ny"] * w["res"], w["nz"] * w["res"], seed=1234, device="cuda")
-    torch.use_deterministic_algorithms(True)
-    frames = [sc.frame(f / 30.0) + (f / 30.0,) for f in range(args.frames)]
-    torch.use_deterministic_algorithms(False)
-    torch.cuda.synchronize()
-    st = torch.cuda.Stream()
-    m._chk(m.L.dspmap_set_stream(m.h, st.cuda_stream))
+    m, st = harness.open_map(D, scene, name, args.frames)
     out = {"workload": "%s: %dx%dx%d @ %.2f m, %d particles/voxel" % (name, w["nx"], w["ny"], w["nz"], w["res"], w["ppv"]),
            "state": "%d frames of scene.py" % args.frames, "stamp_bytes": 4 * m.V}
-    with torch.cuda.stream(st):
-        for f, (pts, pos, quat, t) in enumerate(frames):
-            if f:
-                m.clearOccupancyMapPrediction()
-            assert m.update_device(pts.data_ptr(), pts.shape[0], pos, t, quat) == 1
-        st.synchronize()
-    cur = np.array(frames[-1][1], np.float32)
+    cur = np.array(m.scene_frames[-1][1], np.float32)
     counter = int(m.get_param(D.capi.P_UPDATE_COUNTER))
     margin = float(m.get_param(D.capi.P_OCCLUSION_MARGIN))
 
     def timed(fns, reps):
-        """device time (us) of each of reps calls of every arm, the arms interleaved call by call -> [(median, min)] per arm"""
-        with torch.cuda.stream(st):
-            for _ in range(args.warmup):
-                for fn in fns:
-                    fn()
-            ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in fns] for _ in range(reps)]
-            for row in ev:
-                for fn, (e0, e1) in zip(fns, row):
-                    e0.record(st)
-                    fn()
-                    e1.record(st)
-            st.synchronize()
-        t = np.array([[e0.elapsed_time(e1) * 1000.0 for e0, e1 in row] for row in ev])
-        return [(round(float(np.median(t[:, j])), 2), round(float(t[:, j].min()), 2)) for j in range(len(fns))]
+        return harness.timed(st, fns, reps, args.warmup)
 
     # the route without the feature: the frame's observations and view over the bus, every cell classified on the CPU
     tc, tg = [], []
@@ -110,19 +77,8 @@ def run(D, scene, name, args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--frames", type=int, default=20)
-    ap.add_argument("--host-reps", type=int, default=3)
-    ap.add_argument("--only", choices=sorted(WORKLOADS), default=None)
-    args = ap.parse_args()
-    import build_ext
-    build_ext.build()
-    import dsp_map_amd as D
-    scene = importlib.import_module("dsp-map_amd.scene")
-    for name in ([args.only] if args.only else ["B", "L"]):
-        run(D, scene, name, args)
+    ap = harness.parser(reps=200, warmup=3, frames=20, host_reps=3)
+    harness.main(run, ap)
 
 
 if __name__ == "__main__":

@@ -6,42 +6,19 @@ timed on the wall clock.  Prints one JSON line.  bench.py is not involved.
 
     python tools/query_bench.py [--reps 200] [--warmup 20]
 """
-import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "dsp-map_amd"))
+import layer_bench as harness
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--frames", type=int, default=20)
-    args = ap.parse_args()
-    import build_ext
-    build_ext.build()
-    import dsp_map_amd as D
-    import importlib
-    scene = importlib.import_module("dsp-map_amd.scene")
-
-    w = dict(nx=66, ny=66, nz=40, res=0.15, ppv=24)
-    m = D.DSPMap(D.make_config(seed=1234, **w))
-    m._chk(m.L.dspmap_init_device(m.h))
-    sc = scene.CorridorScene(w["nx"] * w["res"], w["ny"] * w["res"], w["nz"] * w["res"], seed=1234, device="cuda")
-    torch.use_deterministic_algorithms(True)
-    frames = [sc.frame(f / 30.0) + (f / 30.0,) for f in range(args.frames)]
-    torch.use_deterministic_algorithms(False)
-    torch.cuda.synchronize()
-    st = torch.cuda.Stream()
-    m._chk(m.L.dspmap_set_stream(m.h, st.cuda_stream))
+def run(D, scene, name, args):
+    w = harness.WORKLOADS[name]
+    m, st = harness.open_map(D, scene, name, args.frames)   # (the frames clear the prediction before every frame but never after the last one:
+    # the timed queries read its live prediction; a pending clear would make every t >= 0 sample read 0 without touching the accumulators)
 
     rng = np.random.default_rng(0)
     half = np.array([w["nx"], w["ny"], w["nz"]], np.float32) * np.float32(w["res"]) * np.float32(0.5)
@@ -73,12 +50,6 @@ def main():
             e1.synchronize()
         return e0.elapsed_time(e1) * 1000.0 / args.reps
 
-    with torch.cuda.stream(st):
-        for f, (pts, pos, quat, t) in enumerate(frames):
-            if f:   # once per frame (:429-438), never after the last one: the timed queries read its live prediction (a pending
-                m.clearOccupancyMapPrediction()   # clear would make every t >= 0 sample read 0 without touching the accumulators)
-            assert m.update_device(pts.data_ptr(), pts.shape[0], pos, t, quat) == 1
-        st.synchronize()
     q = samples(131072)
     tr = trajectories(4096, 32)
     torch.cuda.synchronize()
@@ -111,6 +82,10 @@ def main():
     out["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
     m.close()
+
+
+def main():
+    harness.main(run, harness.parser(reps=200, warmup=20, frames=20, only=False), names=("B",))
 
 
 if __name__ == "__main__":
