@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdspmap_hip.so")
 SOURCES = ["dspmap_kernels.hip", "dspmap_sweep.hip", "dspmap_api.hip", "dspmap_layers.hip", "dspmap_frame.hip", "dspmap_mgpu.hip", "dspmap_preprocess.hip", "dspmap_velest.hip", "dspmap_dist.hip",
-           "dspmap_query.hip", "dspmap_distance.hip", "dspmap_cast.hip", "dspmap_corridor.hip", "dspmap_reach.hip", "dspmap_cost.hip", "dspmap_shorten.hip", "dspmap_forecast.hip", "dspmap_known.hip", "dspmap_view.hip", "dspmap_viewsel.hip", "dspmap_frontier.hip", "dspmap_objects.hip", "dspmap_track.hip", "dspmap_depth.hip", "velocity_estimator.cpp"]
+           "dspmap_query.hip", "dspmap_distance.hip", "dspmap_nearest.hip", "dspmap_cast.hip", "dspmap_corridor.hip", "dspmap_reach.hip", "dspmap_cost.hip", "dspmap_shorten.hip", "dspmap_forecast.hip", "dspmap_known.hip", "dspmap_view.hip", "dspmap_viewsel.hip", "dspmap_frontier.hip", "dspmap_objects.hip", "dspmap_track.hip", "dspmap_depth.hip", "velocity_estimator.cpp"]
 HEADERS = ["dspmap_internal.h", "dspmap_types.h", "dspmap_device.h", "dspmap_kernels.h", "dspmap_birth.h", "dspmap_cast_walk.h", "dspmap_grid.h", "dspmap_known_slots.h", "dspmap_block_scan.h", "dspmap_unionfind.h", "velocity_estimator.h",
            os.path.join("..", "..", "include", "dspmap.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",

@@ -81,6 +81,9 @@ VPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"),
 RISK_DTYPE = np.dtype([("sum", "f4"), ("max", "f4"), ("first_over", "i4"), ("n_outside", "i4")])
 QUERY_WORLD = 1   # DSPMAP_QUERY_WORLD
 DIST_OUTSIDE_OCCUPIED = 1   # DSPMAP_DIST_OUTSIDE_OCCUPIED
+# dspmap_nearest (dspmap_query_nearest) and the DSPMAP_NEAREST_* flags
+NEAREST_DTYPE = np.dtype([("dist", "f4"), ("voxel", "i4"), ("offset", "f4", (3,)), ("velocity", "f4", (3,))])
+NEAREST_SIGNED, NEAREST_FROM_CAST_GRID = 1, 2
 # dspmap_segment / dspmap_cast_hit (dspmap_cast_segments) and the DSPMAP_CAST_* statuses
 SEGMENT_DTYPE = np.dtype([("ax", "f4"), ("ay", "f4"), ("az", "f4"), ("ta", "f4"), ("bx", "f4"), ("by", "f4"), ("bz", "f4"), ("tb", "f4")])
 HIT_DTYPE = np.dtype([("s", "f4"), ("voxel", "i4"), ("layer", "i4"), ("status", "i4")])
@@ -179,6 +182,12 @@ SIGNATURES = {
     "dspmap_get_distance_field": (_i, [_P, _i, _P]),
     "dspmap_query_distance": (_i, [_P, _i, _P, _i, _f, _P, _P]),
     "dspmap_query_distance_device": (_i, [_P, _i, _P, _i, _f, _P, _P]),
+    "dspmap_build_nearest_field": (_i, [_P, _f, _i, _i]),
+    "dspmap_nearest_field_device": (_P, [_P]),
+    "dspmap_nearest_distance_device": (_P, [_P]),
+    "dspmap_get_nearest_field": (_i, [_P, _i, _P, _P]),
+    "dspmap_query_nearest": (_i, [_P, _i, _P, _i, _f, _P]),
+    "dspmap_query_nearest_device": (_i, [_P, _i, _P, _i, _f, _P]),
     "dspmap_build_cast_grid": (_i, [_P, _f, _i, _i]),
     "dspmap_cast_grid_device": (_P, [_P]),
     "dspmap_get_cast_grid": (_i, [_P, _i, _P]),
@@ -809,6 +818,52 @@ class DSPMap:
         on the GPU -> tensors on the same device, enqueued on the handle's stream and ordered with torch's current stream like
         query_occupancy.  Returns (dist, grad) or dist."""
         return self._query("dspmap_query_distance", q, np.float32, (QUERY_WORLD if world else 0, float(outside)), grad=bool(grad))
+
+    # -- nearest-obstacle fields (extension; semantics in include/dspmap.h next to dspmap_build_nearest_field)
+    def build_nearest_field(self, threshold, max_voxels, signed=False, from_cast_grid=False):
+        """enqueue the nearest-obstacle fields of all T + 1 layers on the handle's stream: per voxel the global index of the nearest
+        occupied voxel within max_voxels voxels (ties: the smallest index; -1: none) and the distance to it in metres.  signed: an
+        occupied voxel gets its nearest FREE voxel and a negative distance instead of itself and 0.  from_cast_grid: the occupied set
+        is the valid cast grid as it is now (threshold is not read), else mass > threshold.  Read-only towards the map; a snapshot like
+        the distance field, which also goes stale with the cast grid when built from it."""
+        flags = (NEAREST_SIGNED if signed else 0) | (NEAREST_FROM_CAST_GRID if from_cast_grid else 0)
+        self._chk(self.L.dspmap_build_nearest_field(self.h, float(threshold), int(max_voxels), flags))
+
+    def _nearest_layers(self, layer, dtype, second):
+        """_layers for the getter with two outputs: the first (int32 indices) or the second (float32 distances)"""
+        idx = range(self.T + 1) if layer is None else [int(layer)]
+        out = np.zeros((len(idx), self.cfg.nz, self.cfg.ny, self.cfg.nx), dtype)
+        for j, l in enumerate(idx):
+            self._chk(self.L.dspmap_get_nearest_field(self.h, l, None if second else _ptr(out[j]), _ptr(out[j]) if second else None))
+        return out if layer is None else out[0]
+
+    def nearest_field(self, layer=None):
+        """the nearest-voxel indices of one layer as numpy int32 [nz, ny, nx], or of all layers [L, nz, ny, nx] (synchronous host copies)"""
+        return self._nearest_layers(layer, np.int32, False)
+
+    def nearest_distance(self, layer=None):
+        """the (signed) distances of one layer as numpy float32 [nz, ny, nx], or of all layers [L, nz, ny, nx] (synchronous host copies)"""
+        return self._nearest_layers(layer, np.float32, True)
+
+    def nearest_field_ptr(self):
+        """device address of the [L][V] int32 indices, or None when there are none / they are stale"""
+        return self.L.dspmap_nearest_field_device(self.h) or None
+
+    def nearest_distance_ptr(self):
+        """device address of the [L][V] float32 distances, or None when there are none / they are stale"""
+        return self.L.dspmap_nearest_distance_device(self.h) or None
+
+    def query_nearest(self, q, world=False, outside=0.0):
+        """the nearest obstacle of every sample {x, y, z, t} of q ([n, 4] float32) in the layer its t selects: the own voxel's distance
+        and nearest voxel, the offset from the point to that voxel's centre and, in the current layer, the velocity of the occupied
+        voxel of the pair; {outside, -1, 0 ...} for what lies outside the map.  numpy in -> structured numpy (NEAREST_DTYPE: dist, voxel,
+        offset[3], velocity[3]) out, synchronous; a torch tensor on the GPU -> dict of tensors 'dist' (float32), 'voxel' (int32),
+        'offset', 'velocity' ([n, 3] float32) on the same device, enqueued on the handle's stream and ordered with torch's current
+        stream like query_occupancy."""
+        q, n, dev = self._input(q, 4, "query_nearest", "samples of shape [n, 4]")
+        out = self._alloc(dev, n, NEAREST_DTYPE)
+        self._call(dev, "dspmap_query_nearest", n, self._p(q), QUERY_WORLD if world else 0, float(outside), self._p(out))
+        return self._fields(out, NEAREST_DTYPE, dev)
 
     # -- segment casts (extension; semantics in include/dspmap.h next to dspmap_build_cast_grid)
     def build_cast_grid(self, threshold, inflate_voxels=0):

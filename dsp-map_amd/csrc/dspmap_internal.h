@@ -24,6 +24,14 @@ struct LayerState {
     // device state.  df_valid: the field is a snapshot of the map as it is -- cleared by everything that computes a frame or replaces state
     float* df_field = nullptr; unsigned char* df_g8 = nullptr; unsigned short* df_h16 = nullptr;
     bool df_valid = false;
+    // nearest-obstacle fields (dspmap_build_nearest_field): the indices and distances [L][V], allocated by the first build, and the two passes'
+    // scratch [VL][V] of 1 and 4 bytes per cell (VL = L, or 2 L for a signed build), grown on demand after the stream has drained; freed
+    // with the device state.  nr_valid: the life cycle of df_valid, and with nr_from_grid (the build read the cast grid, not the masses) also
+    // cleared by every call that replaces or changes the cast grid
+    int* nr_near = nullptr; float* nr_dist = nullptr;
+    signed char* nr_x8 = nullptr; size_t nr_x8_cells = 0;
+    unsigned* nr_key32 = nullptr; size_t nr_key32_cells = 0;
+    bool nr_valid = false, nr_from_grid = false;
     // cast grid (dspmap_build_cast_grid): one bit per voxel, [L][nz][ny][W] words, and the inflation's scratch grid of the same size; allocated
     // by the first build, freed with the device state.  cg_valid: the life cycle of df_valid (dspmap_snapshots_stale)
     u64* cg_bits = nullptr; u64* cg_tmp = nullptr;
@@ -113,7 +121,8 @@ struct LayerState {
     bool tk_have = false, tk_valid = false;
 };
 // What a change makes stale.  The snapshots depend on each other like this:
-//     map -> distance field, forecast, cast grid, objects;   cast grid -> arrival fields, frontiers, objects, cost fields;
+//     map -> distance field, nearest field, forecast, cast grid, objects;   cast grid -> arrival fields, frontiers, objects, cost fields,
+//     a nearest field built from it;
 //     arrival fields -> timeline;                   distance field -> cost fields;
 //     known-space layer -> frontiers;               position -> frontiers
 // LAYERS_x_CHANGED: x has changed under the snapshots taken of it.  LAYERS_x_REBUILD: a build of x starts -- x itself is stale too, until the
@@ -130,13 +139,14 @@ enum LayerChange {
     LAYERS_DISTANCE_CHANGED,    // replaced in place (dspmap_debug_set_distance_field): the field itself stays valid
     LAYERS_COST_REBUILD,
     LAYERS_FORECAST_REBUILD,
-    LAYERS_OBJECTS_REBUILD
+    LAYERS_OBJECTS_REBUILD,
+    LAYERS_NEAREST_REBUILD
 };
 inline void dspmap_layers_stale(LayerState& l, LayerChange c) {
     switch (c) {   // (the first four cases are one chain: each falls through to what depends on it)
-    case LAYERS_MAP_CHANGED: l.df_valid = false; l.fc_valid = false; [[fallthrough]];
+    case LAYERS_MAP_CHANGED: l.df_valid = false; l.fc_valid = false; l.nr_valid = false; [[fallthrough]];
     case LAYERS_CAST_GRID_REBUILD: l.cg_valid = false; [[fallthrough]];
-    case LAYERS_CAST_GRID_CHANGED: l.fr_valid = false; l.ob_valid = false; l.cf_valid = false; [[fallthrough]];
+    case LAYERS_CAST_GRID_CHANGED: l.fr_valid = false; l.ob_valid = false; l.cf_valid = false; if (l.nr_from_grid) l.nr_valid = false; [[fallthrough]];
     case LAYERS_REACH_REBUILD: l.rf_valid = false; l.tl_valid = false; break;
     case LAYERS_KNOWN_CHANGED:
     case LAYERS_POSITION_CHANGED:
@@ -146,6 +156,7 @@ inline void dspmap_layers_stale(LayerState& l, LayerChange c) {
     case LAYERS_COST_REBUILD: l.cf_valid = false; break;
     case LAYERS_FORECAST_REBUILD: l.fc_valid = false; break;
     case LAYERS_OBJECTS_REBUILD: l.ob_valid = false; break;
+    case LAYERS_NEAREST_REBUILD: l.nr_valid = false; break;
     }
 }
 

@@ -183,6 +183,30 @@ struct DistQueryArgs {
 };
 // dist[i] = the field at sample q[i]'s own voxel in the layer its t selects, grad[3 i ..] (optional) = its central / one-sided differences
 void launch_distance_query(const LaunchCtx& c, const DistQueryArgs& a, int n, const float4* q, float* dist, float* grad);
+// nearest-obstacle fields: the distance transform with its argmin carried through the passes (dspmap_nearest.hip; semantics in
+// include/dspmap.h, dspmap_build_nearest_field).  VL virtual layers per launch: the L layers and, signed, their L complements behind them
+struct NearArgs {
+    float thr;           // a voxel is occupied iff its mass > thr (as DistArgs); not read when `grid` is set
+    int R;               // truncation radius in voxels, 1 .. 64
+    int sgn;             // DSPMAP_NEAREST_SIGNED: occupied cells target the free voxels, their distance is negated
+    int fut_zero;        // 1: a clear of the future accumulators is pending -- the layers >= 1 are empty
+    int L;               // layers: T + 1
+    const u64* grid;     // DSPMAP_NEAREST_FROM_CAST_GRID: [L][nz][ny][W] the cast grid, else NULL (the masses decide)
+    signed char* x8;     // [VL][V] pass 1: ux - x of the row's nearest target, NEAR_NONE8 beyond R
+    unsigned* key32;     // [VL][V] pass 2: (D2 within the z plane << 16) | (uy - y) << 8 | (ux - x), D2 = 0x7fff for none
+    int* near;           // [L][V] pass 3: global index of the nearest target, -1 for none
+    float* dist;         // [L][V] pass 3: the (signed) distance
+};
+void launch_nearest_field(const LaunchCtx& c, const NearArgs& a);
+struct NearQueryArgs {
+    SampleOrigin org;
+    float outside;       // what a point outside the map or a NaN sample reads
+    float cx, cy, cz;    // as QueryArgs: dspmap_voxel_center
+    const int* near;     // [L][V]
+    const float* dist;   // [L][V]
+};
+struct dspmap_nearest;
+void launch_nearest_query(const LaunchCtx& c, const NearQueryArgs& a, int n, const float4* q, struct dspmap_nearest* out);
 // segment casts through a bit grid of the current and the predicted occupancy (dspmap_cast.hip; semantics in include/dspmap.h,
 // dspmap_build_cast_grid).  The grid is in the reference's voxel order: [L][nz][ny][W] words, W = ceil(nx / 64)
 struct CastGridArgs {
@@ -331,7 +355,8 @@ struct ViewArgs {
 };
 static_assert(offsetof(QueryArgs, org) == 0 && offsetof(DistQueryArgs, org) == 0 && offsetof(CastArgs, org) == 0 && offsetof(BoxArgs, org) == 0 &&
                   offsetof(ReachArgs, org) == 0 && offsetof(FieldPathArgs, org) == 0 && offsetof(ReachTimelinePathArgs, org) == 0 &&
-                  offsetof(CostArgs, org) == 0 && offsetof(ForecastQueryArgs, org) == 0 && offsetof(ViewArgs, org) == 0,
+                  offsetof(CostArgs, org) == 0 && offsetof(ForecastQueryArgs, org) == 0 && offsetof(ViewArgs, org) == 0 &&
+                  offsetof(NearQueryArgs, org) == 0,
               "every argument block that takes samples starts with their SampleOrigin");
 struct dspmap_view;
 struct dspmap_view_score;

@@ -265,6 +265,97 @@ extern "C" int dspmap_query_distance_device(dspmap_t* m, int n, const dspmap_que
     return dist_query_enqueue(m, n, (const float4*)q, flags, outside, dist, grad);
 }
 
+// --------------------------------------------------- nearest-obstacle fields (dspmap_nearest.hip; semantics in include/dspmap.h)
+static_assert(sizeof(dspmap_nearest) == 32, "dspmap_nearest is 32 bytes");
+static int cast_grid_ready(dspmap* m, const char* what);
+extern "C" int dspmap_build_nearest_field(dspmap_t* m, float thr, int max_voxels, int flags) {
+    const char* what = "dspmap_build_nearest_field";
+    if (!m) return DSPMAP_E_ARG;
+    const bool from_grid = (flags & DSPMAP_NEAREST_FROM_CAST_GRID) != 0, sgn = (flags & DSPMAP_NEAREST_SIGNED) != 0;
+    if (!from_grid && thr != thr) return dspmap_fail(m, DSPMAP_E_ARG, "%s: threshold is NaN", what);
+    if (max_voxels < 1 || max_voxels > 64) return dspmap_fail(m, DSPMAP_E_ARG, "%s: max_voxels %d outside [1, 64]", what, max_voxels);
+    int rc = flags_check(m, what, flags, DSPMAP_NEAREST_SIGNED | DSPMAP_NEAREST_FROM_CAST_GRID);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = whole_map_check(m, what, "distances cross slabs")) != DSPMAP_OK) return rc;
+    if (from_grid && (rc = cast_grid_ready(m, what)) != DSPMAP_OK) return rc;
+    READY(m);
+    BENIGN(m);
+    const MapDims& d = m->d;
+    const int L = d.T + 1;
+    const size_t cells = (size_t)L * d.v_glob, scratch = cells * (sgn ? 2 : 1);
+    dspmap_layers_stale(m->ly, LAYERS_NEAREST_REBUILD);
+    if (!m->ly.nr_near) {
+        HIPCHK(m, hipMalloc(&m->ly.nr_near, sizeof(int) * cells));
+        HIPCHK(m, hipMalloc(&m->ly.nr_dist, sizeof(float) * cells));
+    }
+    if (scratch > m->ly.nr_x8_cells || scratch > m->ly.nr_key32_cells) {   // grown only after the stream has drained (an earlier build may still use them)
+        HIPCHK(m, hipStreamSynchronize(m->stream));
+        if ((rc = layer_buf_grow(m, &m->ly.nr_x8, &m->ly.nr_x8_cells, scratch)) != DSPMAP_OK) return rc;
+        if ((rc = layer_buf_grow(m, &m->ly.nr_key32, &m->ly.nr_key32_cells, scratch)) != DSPMAP_OK) return rc;
+    }
+    NearArgs a;
+    a.thr = thr; a.R = max_voxels; a.sgn = sgn ? 1 : 0;
+    a.fut_zero = m->fut_clear_pending ? 1 : 0;   // read, never changed (as the queries)
+    a.L = L;
+    a.grid = from_grid ? m->ly.cg_bits : nullptr;
+    a.x8 = m->ly.nr_x8; a.key32 = m->ly.nr_key32; a.near = m->ly.nr_near; a.dist = m->ly.nr_dist;
+    launch_nearest_field(dspmap_ctx_of(m), a);
+    HIPCHK(m, hipGetLastError());
+    m->ly.nr_from_grid = from_grid;
+    m->ly.nr_valid = true;
+    return DSPMAP_OK;
+}
+extern "C" const int* dspmap_nearest_field_device(dspmap_t* m) { return (m && m->ly.nr_valid) ? m->ly.nr_near : nullptr; }
+extern "C" const float* dspmap_nearest_distance_device(dspmap_t* m) { return (m && m->ly.nr_valid) ? m->ly.nr_dist : nullptr; }
+static int nearest_ready(dspmap* m, const char* what) {
+    return snapshot_ready(m, m->ly.nr_valid, what,
+                          "no nearest field, or the map or the cast grid it was built from has changed since (dspmap_build_nearest_field)");
+}
+extern "C" int dspmap_get_nearest_field(dspmap_t* m, int layer, int* near_out, float* dist_out) {
+    if (!m) return DSPMAP_E_ARG;
+    if (!near_out && !dist_out) return dspmap_fail(m, DSPMAP_E_ARG, "nearest field: both output arrays are NULL");
+    if (layer < 0 || layer > m->d.T) return dspmap_fail(m, DSPMAP_E_ARG, "nearest field: layer %d outside [0, %d)", layer, m->d.T + 1);
+    int rc = nearest_ready(m, "dspmap_get_nearest_field");
+    if (rc != DSPMAP_OK) return rc;
+    const size_t V = (size_t)m->d.v_glob;
+    if (near_out && (rc = read_back(m, near_out, m->ly.nr_near + V * layer, sizeof(int) * V)) != DSPMAP_OK) return rc;
+    if (dist_out && (rc = read_back(m, dist_out, m->ly.nr_dist + V * layer, sizeof(float) * V)) != DSPMAP_OK) return rc;
+    return DSPMAP_OK;
+}
+static int nearest_query_check(dspmap* m, int n, const void* in, const void* out, int flags, float outside) {
+    if (!m) return DSPMAP_E_ARG;
+    int rc = samples_check(m, "nearest query", "sample", n, in, out);
+    if (rc != DSPMAP_OK) return rc;
+    if ((rc = flags_check(m, "nearest query", flags, DSPMAP_QUERY_WORLD)) != DSPMAP_OK) return rc;
+    if (outside != outside) return dspmap_fail(m, DSPMAP_E_ARG, "nearest query: outside_value is NaN");
+    return nearest_ready(m, "dspmap_query_nearest");
+}
+static int nearest_query_enqueue(dspmap* m, int n, const float4* dq, int flags, float outside, dspmap_nearest* dout) {
+    const MapDims& d = m->d;
+    NearQueryArgs a;
+    a.org = origin_fill(m, flags);
+    a.outside = outside;
+    a.cx = -d.half_x + d.res * 0.5f; a.cy = -d.half_y + d.res * 0.5f; a.cz = -d.half_z + d.res * 0.5f;   // dspmap_voxel_center
+    a.near = m->ly.nr_near; a.dist = m->ly.nr_dist;
+    launch_nearest_query(dspmap_ctx_of(m), a, n, dq, dout);
+    HIPCHK(m, hipGetLastError());
+    return DSPMAP_OK;
+}
+extern "C" int dspmap_query_nearest(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, dspmap_nearest* out) {
+    int rc = nearest_query_check(m, n, q, out, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    if (n == 0) return DSPMAP_OK;
+    StageSec s[2] = {{q, nullptr, sizeof(dspmap_query) * (size_t)n}, {nullptr, out, sizeof(dspmap_nearest) * (size_t)n}};
+    if ((rc = stage_begin(m, s, 2)) != DSPMAP_OK) return rc;
+    if ((rc = nearest_query_enqueue(m, n, (const float4*)s[0].dev, flags, outside, (dspmap_nearest*)s[1].dev)) != DSPMAP_OK) return rc;
+    return stage_end(m, s, 2);
+}
+extern "C" int dspmap_query_nearest_device(dspmap_t* m, int n, const dspmap_query* q, int flags, float outside, dspmap_nearest* out) {
+    const int rc = nearest_query_check(m, n, q, out, flags, outside);
+    if (rc != DSPMAP_OK) return rc;
+    return nearest_query_enqueue(m, n, (const float4*)q, flags, outside, out);
+}
+
 // --------------------------------------------------- segment casts (dspmap_cast.hip; semantics in include/dspmap.h)
 extern "C" int dspmap_build_cast_grid(dspmap_t* m, float thr, int inflate_voxels, int flags) {
     if (!m) return DSPMAP_E_ARG;
@@ -1847,7 +1938,7 @@ extern "C" int dspmap_debug_set_distance_field(dspmap_t* m, const float* layers)
 // --------------------------------------------------- the end of the handle
 void dspmap_layers_free(dspmap* m, const std::function<void(hipError_t, const char*)>& chk) {
     const LayerState& l = m->ly;
-    for (void* q : {(void*)l.q_buf, (void*)l.df_field, (void*)l.df_g8, (void*)l.df_h16, (void*)l.cg_bits, (void*)l.cg_tmp, (void*)l.rf_field,
+    for (void* q : {(void*)l.q_buf, (void*)l.df_field, (void*)l.df_g8, (void*)l.df_h16, (void*)l.nr_near, (void*)l.nr_dist, (void*)l.nr_x8, (void*)l.nr_key32, (void*)l.cg_bits, (void*)l.cg_tmp, (void*)l.rf_field,
                     (void*)l.rf_sets, (void*)l.tl_hist, (void*)l.tl_last, (void*)l.cf_field, (void*)l.cf_sets, (void*)l.cf_weight, (void*)l.cf_wk, (void*)l.cf_occ, (void*)l.fc_field, (void*)l.fc_acc, (void*)l.kn_stamp, (void*)l.vw_dirs0, (void*)l.vs_masks, (void*)l.vs_aux,
                     (void*)l.fr_grid, (void*)l.fr_cells, (void*)l.fr_counts, (void*)l.fr_item_free, (void*)l.fr_dense, (void*)l.fr_blocks,
                     (void*)l.fr_tiles, (void*)l.ob_parent, (void*)l.ob_root, (void*)l.ob_labels, (void*)l.ob_tiles, (void*)l.ob_counts,

@@ -269,6 +269,19 @@ public:
                       float outside_value = 0.f) {
         return dspmap_query_distance(h_, n, samples, world_frame ? DSPMAP_QUERY_WORLD : 0, outside_value, distances, gradients);
     }
+    /* extensions: nearest-obstacle fields of the same layers (dspmap_build_nearest_field in dspmap.h): per voxel the global index of the
+     * nearest occupied voxel within max_voxels voxels (-1: none; ties: the smallest index) and the distance to it.  is_signed: an occupied
+     * voxel gets its nearest free voxel and a negative distance; from_cast_grid: occupied is what buildCastGrid() left (threshold unread).
+     * queryNearest gives per sample the own voxel's pair, the offset to that voxel's centre and, in the current layer, its velocity.
+     * Read-only towards the map; a snapshot like the distance field.  Return DSPMAP_OK or a negative error code. */
+    int buildNearestField(const float threshold = 0.7, int max_voxels = 20, bool is_signed = false, bool from_cast_grid = false) {
+        return dspmap_build_nearest_field(h_, threshold, max_voxels,
+                                          (is_signed ? DSPMAP_NEAREST_SIGNED : 0) | (from_cast_grid ? DSPMAP_NEAREST_FROM_CAST_GRID : 0));
+    }
+    int getNearestField(int layer, int* nearest, float* distances = nullptr) { return dspmap_get_nearest_field(h_, layer, nearest, distances); }
+    int queryNearest(int n, const dspmap_query* samples, dspmap_nearest* out, bool world_frame = false, float outside_value = 0.f) {
+        return dspmap_query_nearest(h_, n, samples, world_frame ? DSPMAP_QUERY_WORLD : 0, outside_value, out);
+    }
     /* extensions: segment casts through bit grids of the current (layer 0) and the predicted (layer 1 + k) occupancy, built and kept on the
      * device (dspmap_build_cast_grid in dspmap.h): hits[i] = the first cell of segs[i] = {a, ta, b, tb} whose bit is set, tested in the
      * horizon of the time the segment enters it.  Read-only towards the map; a grid is a snapshot and goes stale with the next update().

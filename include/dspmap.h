@@ -390,6 +390,70 @@ int dspmap_query_distance(dspmap_t* m, int n, const dspmap_query* q_host, int fl
 int dspmap_query_distance_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, float outside_value, float* dist_out_dev,
                                  float* grad_out_dev);
 
+/* ---- nearest-obstacle fields: WHICH voxel the closest obstacle is, and the signed distance to it (no counterpart in the reference; what a
+ * gradient-based avoider, a velocity-obstacle or a CBF constraint joins to the per-voxel velocities of dspmap_get_results, instead of a
+ * whole-grid copy and a CPU distance transform with indices per layer).  The distance field above is zero, with a zero gradient, inside
+ * obstacles and names no obstacle; this layer does both.
+ *
+ * Layers: those of the distance field.  L = T + 1, layer 0 the current mass, layer 1 + k horizon k; each a dense [nz][ny][nx] grid in the
+ * reference's global voxel index order (:1081), whatever DSPMAP_P_TILING stores internally.
+ *  - occupied set of a layer.  Without DSPMAP_NEAREST_FROM_CAST_GRID: the distance field's rule -- layer 0: voxels_objects_number[v][0] >
+ *    threshold; layer 1 + k: future[v][k] > threshold, bit for bit what dspmap_get_future returns, and 0 everywhere while a clear is pending.
+ *    With DSPMAP_NEAREST_FROM_CAST_GRID: the bits of the VALID cast grid as it is now -- inflated, masked with unknown space
+ *    (dspmap_mask_cast_grid) or replaced by dspmap_debug_set_cast_grid; `threshold` is then not read.  The nearest obstacle is then
+ *    consistent with what casts, boxes and wavefronts call blocked.
+ *  - target set of a cell.  A free cell targets the occupied voxels of its layer.  An occupied cell without DSPMAP_NEAREST_SIGNED targets
+ *    itself (D2 = 0).  An occupied cell with DSPMAP_NEAREST_SIGNED targets the FREE voxels inside the map; padding bits at x >= nx and the
+ *    lattice outside the map belong to neither set.
+ *  - near[i].  With integer voxel indices D2(i) = min over the targets u of (ix - ux)^2 + (iy - uy)^2 + (iz - uz)^2.  If D2 > R^2 with
+ *    R = max_voxels, or there is no target, near = -1 (D2 == R^2 is a valid target).  Otherwise near is the global index of the minimiser;
+ *    among several, the smallest global voxel index: smallest uz, then smallest uy, then smallest ux.
+ *  - dist[i].  d2c = min(D2, R^2), R^2 when there is no target; the value is fl(fl(sqrtf((float)d2c)) * voxel_resolution), sqrt correctly
+ *    rounded, NEGATED for an occupied cell under DSPMAP_NEAREST_SIGNED (its D2 is at least 1: there is no -0).  Without either flag dist
+ *    equals the field of dspmap_build_distance_field(threshold, max_voxels, 0) bit for bit.  All integers involved are <= 4096: both
+ *    grids are defined bit for bit.
+ *  - arguments, checked in the order of dspmap_build_objects: a NULL handle, a NaN threshold without DSPMAP_NEAREST_FROM_CAST_GRID,
+ *    max_voxels outside 1 .. 64 or unknown flags are DSPMAP_E_ARG; then a sharded handle (slab) is DSPMAP_E_STATE; then
+ *    DSPMAP_NEAREST_FROM_CAST_GRID without a valid cast grid is DSPMAP_E_STATE with a text naming dspmap_build_cast_grid; without a usable
+ *    device a valid call is DSPMAP_E_DEVICE.
+ *  - snapshot: the life cycle of the distance field.  The build is enqueued on the handle's stream behind everything queued there before
+ *    and does not synchronise (except where a first or a larger build has to allocate).  It writes two [L][V] grids the handle owns
+ *    (allocated by the first build, with scratch of 1 and 4 bytes per cell and layer, twice that for a signed build; a handle that never
+ *    builds one allocates nothing).  READ-ONLY towards the map in every sense listed for the distance field, and towards the cast grid
+ *    and the distance field of the handle.  It stays valid through readouts and dspmap_clear_future and becomes STALE with every call
+ *    that makes a distance field stale.  A snapshot built with DSPMAP_NEAREST_FROM_CAST_GRID also becomes stale with everything that
+ *    replaces or changes the cast grid: dspmap_build_cast_grid, dspmap_mask_cast_grid, dspmap_debug_set_cast_grid; a snapshot built from
+ *    the masses does not depend on the cast grid.  On a stale or never-built snapshot dspmap_nearest_field_device and
+ *    dspmap_nearest_distance_device return NULL, dspmap_get_nearest_field and dspmap_query_nearest* return DSPMAP_E_STATE with a text
+ *    naming dspmap_build_nearest_field.  dspmap_get_nearest_field: either output may be NULL, not both (DSPMAP_E_ARG); a `layer`
+ *    outside [0, L) is DSPMAP_E_ARG.
+ * dspmap_query_nearest*: samples, frame convention, DSPMAP_QUERY_WORLD, the NaN rule and the layer k(t) are those of dspmap_query_distance.
+ *  - a point outside the map, or a sample with a NaN, gives {outside_value, -1, 0, 0, 0, 0, 0, 0}.
+ *  - otherwise, with g the point's own voxel (dspmap_point_voxel_index's voxel) and p the reduced point: dist = dist[g], voxel = near[g];
+ *    the offset to the centre of the nearest voxel o_a = fl(c_a(voxel) - p_a) per axis, c = dspmap_voxel_center's
+ *    fl(fl((float)i * res) + (-half + res / 2)), and (0, 0, 0) when voxel == -1.
+ *  - velocity: columns 1 .. 3 of dspmap_get_results at the OCCUPIED voxel of the pair, bit for bit, whatever storage order the handle
+ *    uses: that voxel is `voxel` for a free own cell and g for an occupied one.  Filled only when the selected layer is 0 and that voxel
+ *    exists (a free cell with voxel == -1 has none); (0, 0, 0) otherwise.
+ *  - a NULL handle, n < 0, a NULL array with n > 0, unknown flags or a NaN outside_value are DSPMAP_E_ARG. */
+#define DSPMAP_NEAREST_SIGNED 1
+#define DSPMAP_NEAREST_FROM_CAST_GRID 2
+int dspmap_build_nearest_field(dspmap_t* m, float threshold, int max_voxels, int flags);
+const int* dspmap_nearest_field_device(dspmap_t* m);        /* [L][V] int32 device memory, NULL if none / stale */
+const float* dspmap_nearest_distance_device(dspmap_t* m);   /* [L][V] float device memory, NULL if none / stale */
+/* V ints and / or V floats of one layer (either may be NULL, not both); synchronous */
+int dspmap_get_nearest_field(dspmap_t* m, int layer, int* near_out_host, float* dist_out_host);
+typedef struct dspmap_nearest {
+    float dist;         /* the (signed) distance of the own voxel, metres */
+    int voxel;          /* global index of its nearest target, -1 if none within max_voxels */
+    float ox, oy, oz;   /* centre of `voxel` minus the point */
+    float vx, vy, vz;   /* velocity of the occupied voxel of the pair (layer 0 only) */
+} dspmap_nearest;       /* 32 bytes */
+/* out_host[i] of q_host[i]; synchronous */
+int dspmap_query_nearest(dspmap_t* m, int n, const dspmap_query* q_host, int flags, float outside_value, dspmap_nearest* out_host);
+/* the same on device arrays; enqueued on the handle's stream, no synchronisation */
+int dspmap_query_nearest_device(dspmap_t* m, int n, const dspmap_query* q_dev, int flags, float outside_value, dspmap_nearest* out_dev);
+
 /* ---- segment casts through the current and the predicted occupancy (no counterpart in the reference; a planner's edge check, a
  * line-of-sight test or a first hit along a ray, answered where the map lives instead of by sampling dspmap_trajectory_risk every half
  * voxel -- which misses voxels a segment only clips -- or by copying the whole grid out and walking it on the host).
